@@ -2,7 +2,7 @@
 # every bench line of the round (run on the GPU box from the repo root); lines land in gpurun_out/r05_bench_*.json
 cd $GRAFT_REPO_ROOT
 O=gpurun_out
-run() { name=$1; shift; python bench.py "$@" 2>$O/r05_bench_$name.err | tail -1 > $O/r05_bench_$name.json; }
+run() { name=$1; shift; python bench.py --full "$@" 2>$O/r05_bench_$name.err | tail -1 > $O/r05_bench_$name.json; }
 run tracking
 run tracking_s1 --streams 1 --no-others --no-cpu-baseline
 run tracking_b65536 --batch 65536 --steps 20 --no-others --no-cpu-baseline

@@ -1,14 +1,14 @@
 """The reference's ROS 2 parameter files -> lmpc_vehicle / lmpc_config (ros_params.py) -- CPU only.
 
 The files written here are this repository's own, in the reference's format (`/**: ros__parameters:` trees with the keys
-its loaders declare).  When the reference checkout is present (this container, not the GPU box) its shipped files are
-read as well, which pins `presets.py` -- the values every parity test and bench line runs on -- to them."""
+its loaders declare).  The reference's shipped files for the two cars and their four controllers are read as well, from the
+copies under tests/golden/ros_params/, which pins `presets.py` -- the values every parity test and bench line runs on -- to them."""
 from pathlib import Path
 
 import pytest
 import yaml
 
-REF_PARAM = Path("/root/reference/src/launch/racing_lmpc_launch/param")
+REF_PARAM = Path(__file__).resolve().parent / "golden" / "ros_params"  # src/launch/racing_lmpc_launch/param/ of the reference, unchanged
 
 VEHICLE_KEYS = {  # lmpc_vehicle field -> the reference's parameter (where single_track_planar_model.cpp reads it)
     "m": "chassis.total_mass", "Jzz": "chassis.moi", "l": "chassis.wheel_base", "cg_ratio": "chassis.cg_ratio",
@@ -156,7 +156,6 @@ def test_what_the_device_path_does_not_build_is_refused(pkg, tmp_path):
         rp.load_ros_params(tmp_path / "bad.yaml")
 
 
-@pytest.mark.skipif(not REF_PARAM.is_dir(), reason="the reference checkout is not on this machine")
 def test_presets_equal_the_reference_shipped_files(pkg):
     rp, pr = pkg.ros_params, pkg.presets
     for car, preset in (("barc", pr.barc_vehicle), ("iac_car", pr.iac_vehicle)):
