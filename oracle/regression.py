@@ -68,3 +68,38 @@ def regress(veh: Vehicle, laps: list, in_state, in_ctrl, out_rows, dist_max: flo
         B[r, in_ctrl] += R[ns:-1]
         C[r] += R[-1]
     return A, B, C
+
+
+def regress_batch(veh: Vehicle, laps: list, in_state, in_ctrl, out_rows, dist_max: float, q_x: np.ndarray, q_u: np.ndarray,
+                  A: np.ndarray, B: np.ndarray, C: np.ndarray, as_written: bool = False, chunk: int = 128):
+    """`regress` for many linearisation points at once (same arithmetic, vectorised over the queries; the residuals are
+    computed once).  q_x [n, 6], q_u [n, 2], A [n, 6, 6], B [n, 6, 2], C [n, 6]; returns updated copies and touched [n]
+    (the query had at least one candidate; untouched rows are returned bit-identical)."""
+    A, B, C = A.copy(), B.copy(), C.copy()
+    in_state, in_ctrl, out_rows = list(in_state), list(in_ctrl), list(out_rows)
+    ns = len(in_state)
+    Z = np.concatenate([np.concatenate([x[:-1][:, in_state], u[:-1][:, in_ctrl]], axis=1) for (x, u, k, t) in laps])
+    Y = np.concatenate([lap_residuals(veh, x, u, k, t, as_written) for (x, u, k, t) in laps])[:, out_rows]
+    M = np.concatenate([Z, np.ones((Z.shape[0], 1))], axis=1)
+    sgn = -1.0 if as_written else 1.0
+    q_all = np.concatenate([q_x[:, in_state], q_u[:, in_ctrl]], axis=1)
+    touched = np.zeros(q_all.shape[0], dtype=bool)
+    for c0 in range(0, q_all.shape[0], chunk):
+        q = q_all[c0:c0 + chunk]
+        d = np.sqrt(((Z[None, :, :] - q[:, None, :]) ** 2).sum(axis=2))           # [m, samples]
+        m = d < dist_max
+        K = np.where(m, 0.75 / dist_max * (1 - (d / dist_max) ** 2) ** 2, 0.0)
+        hit = m.any(axis=1)
+        touched[c0:c0 + chunk] = hit
+        if not hit.any():
+            continue
+        KM = K[hit][:, :, None] * M[None]                                            # [h, samples, NF + 1]
+        Q = np.einsum("hvi,vj->hij", KM, M) + 1e-3 * np.eye(M.shape[1])
+        R = np.linalg.solve(Q, sgn * np.einsum("hvi,vo->hio", KM, Y))               # [h, NF + 1, rows]
+        idx = np.nonzero(hit)[0] + c0
+        for o, r in enumerate(out_rows):
+            A[idx[:, None], r, np.asarray(in_state)[None, :]] += R[:, :ns, o]
+            if in_ctrl:
+                B[idx[:, None], r, np.asarray(in_ctrl)[None, :]] += R[:, ns:-1, o]
+            C[idx, r] += R[:, -1, o]
+    return A, B, C, touched

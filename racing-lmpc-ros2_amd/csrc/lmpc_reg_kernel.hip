@@ -85,7 +85,10 @@ __global__ void lmpc_reg_pack_kernel(lmpc_regression_spec spec, int nvalid, int 
 }
 
 // WS_LAYOUT: update the handle's linearisation workspace [B][N-1][54]; otherwise the A/B/g arrays of lmpc_linearize_batch.
-template <int NF, int NOUT, bool WS_LAYOUT>
+// EXACT: the features are large against the bandwidth (lmpc_set_regression_laps decides: the abscissa s of the IAC track runs to
+// 2849 m), where the expanded d^2 below loses the weight to cancellation -- it stays the bandwidth screen, and inside the hit
+// branch each lane recomputes its weight from sum_f (z_f - q_f)^2.
+template <int NF, int NOUT, bool WS_LAYOUT, bool EXACT>
 __global__ __launch_bounds__(64) void lmpc_regress_kernel(int N, int B, lmpc_regression_spec spec, int npad,
                                                           const double* __restrict__ tab, const double* __restrict__ zz, const double* __restrict__ X_ref,
                                                           const double* __restrict__ U_ref, double* __restrict__ outA,
@@ -150,7 +153,21 @@ __global__ __launch_bounds__(64) void lmpc_regress_kernel(int N, int B, lmpc_reg
 #pragma unroll
     for (int t = 0; t < UNR; ++t) {
       if (!__any(sq[t] > 0.0)) continue;
-      const double w = sq[t] * sq[t];
+      double wt = sq[t];
+      if constexpr (EXACT) {
+        // |q|^2 + |z|^2 - 2 z.q carries a rounding error of a few ulp of |q|^2 + |z|^2 (4e-9 at s = 2849 m against h^2 = 0.36).
+        // A sample one form puts inside the bandwidth and the other outside weighs (delta / h^2)^2: negligible either way.
+        // (z_f - q_f from qm2 = -2 q, exactly: q itself need not stay live across the loop -- it would take the (8, 6) instance past
+        // the 256-VGPR budget and halve its occupancy)
+        double s = 0.0;
+#pragma unroll
+        for (int f = 0; f < NF; ++f) {
+          const double df = __builtin_fma(qm2[f], 0.5, row[t][f]);
+          s = __builtin_fma(df, df, s);
+        }
+        wt = fmax(__builtin_fma(s, nih2, 1.0), 0.0);
+      }
+      const double w = wt * wt;
       double wm[NM];
 #pragma unroll
       for (int r = 0; r < NF; ++r) wm[r] = w * row[t][r];
@@ -242,10 +259,14 @@ __global__ __launch_bounds__(64) void lmpc_regress_kernel(int N, int B, lmpc_reg
   }
 }
 
-#define LMPC_REG_INSTANTIATE(NF, NOUT, WS)                                                                                    \
-  template __global__ void lmpc_regress_kernel<NF, NOUT, WS>(int, int, lmpc_regression_spec, int, const double*, const double*, const double*, \
-                                                             const double*, double*, double*, double*);
-LMPC_REG_INSTANTIATE(5, 3, true)
-LMPC_REG_INSTANTIATE(5, 3, false)
-LMPC_REG_INSTANTIATE(8, 6, true)
-LMPC_REG_INSTANTIATE(8, 6, false)
+#define LMPC_REG_INSTANTIATE(NF, NOUT, WS, EXACT)                                                                             \
+  template __global__ void lmpc_regress_kernel<NF, NOUT, WS, EXACT>(int, int, lmpc_regression_spec, int, const double*, const double*,      \
+                                                                    const double*, const double*, double*, double*, double*);
+LMPC_REG_INSTANTIATE(5, 3, true, false)
+LMPC_REG_INSTANTIATE(5, 3, false, false)
+LMPC_REG_INSTANTIATE(8, 6, true, false)
+LMPC_REG_INSTANTIATE(8, 6, false, false)
+LMPC_REG_INSTANTIATE(5, 3, true, true)
+LMPC_REG_INSTANTIATE(5, 3, false, true)
+LMPC_REG_INSTANTIATE(8, 6, true, true)
+LMPC_REG_INSTANTIATE(8, 6, false, true)

@@ -102,3 +102,96 @@ def digest(inp: dict, ss_x=None, ss_j=None) -> np.ndarray:
     if ss_x is not None:
         d = d + np.abs(ss_x).sum(axis=(0, 1)) + np.abs(ss_j).sum(axis=0)
     return d
+
+
+# ---- regressed solves (BASELINE configs[4]: the error-dynamics regression in front of every stage) -----------------------------------
+# A table of its own: tests/test_dense_fixtures.py runs the serial twin over CASES, and the twin has no regression.  The reference model
+# comes from the oracle alone -- oracle.qp.linearise, corrected by oracle.regression, handed to build_qp(lin=...) -- never from the
+# product's regress().  The regression samples are the bench's two-sample laps (workloads.regression_sample_pairs) with successors from
+# a CPU plant: the oracle's RK4 with 15 % less grip.
+BENCH_REG = ((3, 4, 5), (0, 1), (3, 4, 5))
+S01234_REG = ((0, 1, 2, 3, 4), (), (2, 4, 5))
+ALL_REG = ((0, 1, 2, 3, 4, 5), (0, 1), (0, 1, 2, 3, 4, 5))
+REG_DIST_MAX = 0.6
+
+# name: (family, N, count, feature spec, dist_max, what it pins).  Which kernel instance runs follows from the spec (5 features / 3 rows
+# or 8 / 6) and from the scale of the features against dist_max (lmpc_set_regression_laps: EXACT weights where max |z| > 16 dist_max).
+REG_CASES = {
+    "reg_barc_lmpc_spec_n20_s160": ("spc", 20, 512, BENCH_REG, REG_DIST_MAX, "configs[4] as benched: spec laps, configs[1]'s random x0 (rank 0)"),
+    "reg_barc_lmpc_near_n20_s160": ("near", 20, 512, BENCH_REG, REG_DIST_MAX, "configs[4] on states drawn near the stored laps (bench.py --lmpc-data near)"),
+    "reg_barc_tracking_n20": ("trk", 20, 96, BENCH_REG, REG_DIST_MAX, "tracking, one-wave kernel; <5, 3> screened weights"),
+    "reg_barc_tracking_n60": ("trk", 60, 64, BENCH_REG, REG_DIST_MAX, "tracking, two-wave kernel (reads the regressed records through its own loader)"),
+    "reg_barc_tracking_all_n20": ("trk", 20, 64, ALL_REG, 1.5, "<8, 6> with screened weights inside a solve (BARC: max |z| ~ 17 < 16 x 1.5)"),
+    "reg_iac_tracking_n40": ("iac", 40, 64, ALL_REG, REG_DIST_MAX, "<8, 6> with exact weights inside a solve, IAC scale"),
+    "reg_iac_tracking_s01234_n40": ("iac", 40, 64, S01234_REG, REG_DIST_MAX, "<5, 3> with exact weights inside a solve (the abscissa at IAC scale)"),
+}
+
+
+def reg_exact(samples, spec, dist_max) -> bool:
+    """The rule lmpc_set_regression_laps applies (csrc/lmpc_capi.hip): exact weights where the largest squared feature norm over the
+    samples exceeds 256 dist_max^2."""
+    ins, inc = list(spec[0]), list(spec[1])
+    z2 = max(float(((np.asarray(x)[:, ins] ** 2).sum(axis=1) + (np.asarray(u)[:, inc] ** 2).sum(axis=1)).max()) for (x, u, k, t) in samples)
+    return not (z2 <= 256.0 * dist_max * dist_max)
+
+
+def regression_samples(pkg, tr, veh, stored):
+    """Two-sample laps around `stored` state laps, successors one 30 ms step of the CPU plant (mu x 0.85)."""
+    import dataclasses
+
+    from oracle import scenario as S2
+    from oracle.dynamics import rk4
+
+    plant = dataclasses.replace(veh, mu=0.85 * veh.mu)
+    return pkg.workloads.regression_sample_pairs(
+        tr, stored, lambda xa, ua: rk4(xa, ua, S2.track_lookup(tr["curvature"], xa[:, 0], tr["L"]), 0.03, plant))
+
+
+def oracle_regressed_model(cfg, veh, inp, samples, spec, dist_max=REG_DIST_MAX):
+    """Per problem (A [N-1,6,6], B [N-1,6,2], g [N-1,6]) as build_qp(lin=...) takes them, stacked on a leading batch axis: the oracle's
+    linearisation about (X_ref, U_ref) plus the oracle's regression at every stage."""
+    from oracle import qp as Q, regression as R
+
+    N, Bn = cfg.N, inp["x_ic"].shape[1]
+    lin = [Q.linearise(cfg, veh, S.problem(inp, b)) for b in range(Bn)]
+    A0 = np.stack([l[0] for l in lin]).reshape(Bn * (N - 1), 6, 6)
+    B0 = np.stack([l[1] for l in lin]).reshape(Bn * (N - 1), 6, 2)
+    g0 = np.stack([l[2] for l in lin]).reshape(Bn * (N - 1), 6)
+    qx = inp["X_ref"][:, : N - 1, :].transpose(2, 1, 0).reshape(-1, 6)
+    qu = inp["U_ref"].transpose(2, 1, 0).reshape(-1, 2)
+    A, B, g, touched = R.regress_batch(veh, samples, *spec, dist_max, qx, qu, A0, B0, g0)
+    return A.reshape(Bn, N - 1, 6, 6), B.reshape(Bn, N - 1, 6, 2), g.reshape(Bn, N - 1, 6), touched.reshape(Bn, N - 1)
+
+
+def build_reg(pkg, name: str):
+    """-> cfg, veh, inp, ss_x, ss_j (None for tracking), samples (the regression's laps), spec, (A, B, g, touched) of the oracle"""
+    family, N, count, spec, dist_max, _ = REG_CASES[name]
+    wl = pkg.workloads
+    if family in ("spc", "near"):
+        tr = wl.synthetic_track("barc")
+        cfg, veh = P.barc_lmpc(N, 5), P.barc_vehicle()
+        # (a) the spec laps and configs[1]'s x0 (the problems of dense_barc_lmpc_spec_n20_s160); (b) bench.py --lmpc-data near: the
+        # synthetic laps and states drawn near them (the problems of dense_barc_lmpc_n20_s160)
+        stored = spec_laps() if family == "spc" else wl.synthetic_laps(tr, 5)
+        _, _, inp, ss_x, ss_j = build(pkg, "barc_lmpc_spec_n20_s160" if family == "spc" else "barc_lmpc_n20_s160")
+    elif family == "trk":
+        cfg, veh, inp, ss_x, ss_j = build(pkg, "barc_tracking_n%d" % N)
+        inp = {k: (v[..., :count] if isinstance(v, np.ndarray) else v) for k, v in inp.items()}
+        tr = wl.synthetic_track("barc")
+        stored = spec_laps()
+    elif family == "iac":
+        cfg, veh, inp, ss_x, ss_j = build(pkg, "iac_tracking_n%d" % N)
+        inp = {k: (v[..., :count] if isinstance(v, np.ndarray) else v) for k, v in inp.items()}
+        tr = wl.synthetic_track("putnam")
+        stored = [inp["X_ref"][:, :, b].T.copy() for b in range(0, count, 2)]   # samples around every other problem's cold start
+    else:
+        raise KeyError(name)
+    samples = regression_samples(pkg, tr, veh, stored)
+    return cfg, veh, inp, ss_x, ss_j, samples, spec, oracle_regressed_model(cfg, veh, inp, samples, spec, dist_max)
+
+
+def reg_digests(samples, model):
+    """(per-problem sum |.| of the oracle's corrected A, B, g; one number for the regression samples)"""
+    A, B, g = model[:3]
+    return (np.abs(A).sum(axis=(1, 2, 3)) + np.abs(B).sum(axis=(1, 2, 3)) + np.abs(g).sum(axis=(1, 2)),
+            float(sum(np.abs(np.asarray(a)).sum() for lap in samples for a in lap)))

@@ -80,3 +80,40 @@ def test_scaled_dense_iteration_against_the_unscaled_one(pkg):
         it_u.append(info_u["iters"])
         assert np.abs((yu - ys) / Q.variable_scales(qp)).max() < 1e-10
     assert gave_up >= 1 and np.mean(it_u) > np.mean(it_s) + 3
+
+
+@pytest.mark.parametrize("name", list(DC.REG_CASES))
+def test_regressed_fixture_inputs_digest_and_certificate(pkg, name):
+    """The regressed fixtures (tests/golden/dense_reg_*.npz) on every machine: the inputs, the regression samples and the ORACLE's
+    corrected model rebuilt from the seeds match the digests the optima were computed on; the dense solver solved every problem; and a
+    sample of the stored optima is KKT-certified on the oracle-regressed QP (build_qp(lin=...)), independently of the solver."""
+    d = np.load(f"{GOLD}/dense_{name}.npz")
+    fx = {k: d[k] for k in d.files}
+    cfg, veh, inp, ss_x, ss_j, samples, spec, model = DC.build_reg(pkg, name)
+    B = DC.REG_CASES[name][2]
+    assert fx["status"].size == B >= 64
+    md, sd = DC.reg_digests(samples, model)
+    np.testing.assert_allclose(DC.digest(inp, ss_x, ss_j), fx["digest"], rtol=1e-11, atol=0)
+    np.testing.assert_allclose(md, fx["model_digest"], rtol=1e-11, atol=0)
+    np.testing.assert_allclose(sd, fx["samples_digest"], rtol=1e-11, atol=0)
+    assert np.array_equal(model[3].sum(axis=1), fx["touched"]) and fx["touched"].sum() >= 10 * B   # the regression reaches the QPs
+    assert (fx["status"] == 0).all(), np.nonzero(fx["status"])[0]
+    unregressed = None
+    for b in (0, B // 3, B - 1):
+        A, Bm, g = (m[b] for m in model[:3])
+        kw = {} if ss_x is None else {"ss_x": ss_x[:, :, b], "ss_j": ss_j[:, b]}
+        qp = Q.build_qp(cfg, veh, S.problem(inp, b), lin=(A, Bm, g), **kw)
+        if ss_x is None:
+            y = Q.pack(qp, fx["X_optm"][..., b], fx["U_optm"][..., b], fx["dU_optm"][..., b], sigma=fx["sigma"][b])
+        else:   # (the simplex weights are not stored: a fresh dense solve, held to the stored answer, supplies them)
+            y, info = Q.solve_dense(qp)
+            o = qp.split(y)
+            exu, ed = per_problem_err({k: o[k][..., None] for k in ("X_optm", "U_optm", "dU_optm")},
+                                      {k: fx[k][..., b:b + 1] for k in ("X_optm", "U_optm", "dU_optm")})
+            assert info["status"] == 0 and exu.max() < 1e-9 and ed.max() < 1e-8, (name, b, exu, ed)
+        c = Q.kkt_certificate(qp, y)
+        gs = max(1.0, float(np.abs(qp.H @ y + qp.h).max()))
+        assert c["stat"] / gs < 1e-9 and c["eq"] < 1e-9 and c["ineq"] < 1e-9, (name, b, c)
+        if unregressed is None:   # the stored optimum is not the unregressed model's: the correction matters on this data
+            unregressed = Q.kkt_certificate(Q.build_qp(cfg, veh, S.problem(inp, b), **kw), y)["eq"]
+            assert unregressed > 1e-6, unregressed
