@@ -555,6 +555,60 @@ int lmpc_last_solve_precision(const lmpc_handle* h, int32_t* precision);
 int lmpc_enable_timing(lmpc_handle* h, int32_t on);
 int lmpc_last_kernel_ms(lmpc_handle* h, float* linearize_ms, float* solve_ms);
 
+/* Fleet safe set: one SafeSetRecorder and one SafeSetManager PER CAR, on the device.  Upstream every controller owns both
+ * (RacingMPC::solve calls ss_recorder_->step and ss_manager_->query on its own members, racing_mpc.cpp:246-255), so a fleet of B
+ * controllers is B recorders and B stores; lmpc_set_safe_set above is ONE store shared by every query of a handle.
+ *   per car: a ring of lmpc_config.max_lap_stored closed laps (boost::circular_buffer, safe_set.cpp:139-151), the open lap being
+ *   recorded (last_x_ / last_u_ / last_k_ / last_t_, :278-322), the recorder's flags and lap_count, and -- no counterpart upstream --
+ *   n_dropped and the durations of the last closed laps; per sample x[6], u[2], k, t, what the reference writes to its lap files.
+ * lmpc_fleet_ss_create allocates batch x (max_lap_stored + 1) x max_pts_per_lap samples of 80 bytes (4096 cars x 6 x 1024: 2.0 GB;
+ * lmpc_fleet_ss_bytes tells what it took) and replaces an earlier store; sizes that would overflow are LMPC_ERR_ARGUMENT, an
+ * allocation the device refuses LMPC_ERR_RUNTIME (no store is left then).  max_lap_stored must be positive.  lmpc_destroy frees the
+ * store; lmpc_fleet_ss_reset empties every car without reallocating (asynchronous, on the handle's stream).
+ * DEPARTURE from the reference, whose laps are unbounded: a lap slot holds max_pts_per_lap samples.  An open lap that reaches that
+ * many stops storing and is marked overflowed; when it closes it is NOT added to the ring, evicts nothing, and n_dropped[b] goes up
+ * by one (lap_count and the duration are kept as for any lap).  Nothing is ever written outside a car's slots.
+ * Every call names the store's own batch (LMPC_ERR_ARGUMENT otherwise, and without a store).  The store serves the array form of the
+ * safe set only: the by-reference codes (lmpc_ss_query_idx_batch, lmpc_solve_batch_ss_idx, lmpc_solve_batch_warm_ss with ss_idx,
+ * lmpc_shift_lambda_batch) name rows of the shared store and have no fleet form; lmpc_set_regression_laps stays one store per handle. */
+int lmpc_fleet_ss_create(lmpc_handle* h, int32_t batch, int32_t max_pts_per_lap);
+int lmpc_fleet_ss_destroy(lmpc_handle* h);
+int lmpc_fleet_ss_reset(lmpc_handle* h);
+int lmpc_fleet_ss_bytes(const lmpc_handle* h, int64_t* bytes); /* 0 without a store */
+
+/* SafeSetRecorder::step (safe_set.cpp:278-322) for every car, one launch, one thread per car, asynchronous on the handle's stream
+ * without a host round trip (legal inside a captured control period): x [6][B], u [2][B], k [B] (curvature) DEVICE, t and
+ * total_length host values.  The first sample of a car only seeds its abscissa; a lap closes when s_prev - s > total_length / 2;
+ * the first, partial lap is discarded; a closed lap is pushed into the car's ring (the oldest leaves a full ring) and the closing
+ * sample starts the next lap -- including the reference's quirk that jitter across the start line makes very short laps.
+ * active [B] (DEVICE, may be NULL): 0 skips the car for this sample (e.g. a diverged state, at the caller's choice). */
+int lmpc_fleet_ss_record_batch(lmpc_handle* h, int32_t batch, const double* x, const double* u, const double* k, double t,
+                               double total_length, const int32_t* active);
+
+/* lmpc_ss_query_batch with query b run against car b's ring, newest lap first: same outputs (ss_x [6][S][B], ss_j [S][B] = J - J[0],
+ * n_found [B]), padding, truncation, tie rule and NaN behaviour, bit-equal on equal stores; a car without a closed lap gives
+ * n_found = 0 and zero-filled outputs.  The results go to lmpc_solve_batch / lmpc_solve_batch_mixed as ss_x, ss_j.  The laps are
+ * unrolled by the total_length of the last lmpc_fleet_ss_record_batch / lmpc_fleet_ss_load.  num_ss_pts_per_lap <= 64. */
+int lmpc_fleet_ss_query_batch(lmpc_handle* h, int32_t batch, const double* query, double* ss_x, double* ss_j, int32_t* n_found);
+
+/* SafeSetRecorder::load (safe_set.cpp:260-276) for car `car`, or for every car with car = -1.  HOST pointers, laps oldest first and
+ * concatenated as in lmpc_set_regression_laps: x [n][6], u [n][2], k [n], t [n].  The laps are pushed into the ring behind those it
+ * holds (an open lap stays open); lap_count grows by n_laps; no duration is recorded for them.  A lap longer than the store's
+ * max_pts_per_lap is refused (LMPC_ERR_ARGUMENT, nothing loaded).  Synchronises the handle's stream. */
+int lmpc_fleet_ss_load(lmpc_handle* h, int32_t car, int32_t n_laps, const int32_t* n_pts, const double* x, const double* u,
+                       const double* k, const double* t, double total_length);
+
+/* One car's closed laps, oldest first, to HOST arrays (tests, lap files, inspection): *n_laps, n_pts [max_lap_stored], and the
+ * concatenated x [n][6], u [n][2], k [n], t [n], each optional.  Call it with the sample arrays NULL for the sizes, then with
+ * arrays of sum(n_pts) samples.  Synchronises the handle's stream. */
+int lmpc_fleet_ss_get_laps(lmpc_handle* h, int32_t car, int32_t* n_laps, int32_t* n_pts, double* x, double* u, double* k, double* t);
+
+/* Per-car counters to DEVICE arrays [B], any of them NULL: laps in the ring, the recorder's lap_count (every crossing and every
+ * loaded lap), laps dropped for their length, and the duration of the last lap closed by the recorder -- t at the closing crossing
+ * minus t of the lap's first sample, 0 before the first.  Asynchronous on the handle's stream. */
+int lmpc_fleet_ss_stats(lmpc_handle* h, int32_t batch, int32_t* laps_in_ring, int32_t* lap_count, int32_t* n_dropped,
+                        double* last_lap_time);
+
 #ifdef __cplusplus
 }
 #endif

@@ -23,7 +23,9 @@ _ABI_SYMBOLS = ("lmpc_create", "lmpc_destroy", "lmpc_last_error", "lmpc_set_stre
                 "lmpc_solve_batch_mixed", "lmpc_prepare_failed_batch", "lmpc_set_launch_order", "lmpc_set_warm_rounds", "lmpc_loop_advance_batch", "lmpc_launch_order_from_iters", "lmpc_set_output_layout",
                 "lmpc_ss_query_idx_batch", "lmpc_solve_batch_ss_idx", "lmpc_solve_batch_warm", "lmpc_solve_host_warm",
                 "lmpc_last_solve_precision", "lmpc_solve_batch_warm_ss", "lmpc_solve_host_warm_ss", "lmpc_shift_lambda_batch",
-                "lmpc_get_warm_accepted", "lmpc_set_waves_per_problem")
+                "lmpc_get_warm_accepted", "lmpc_set_waves_per_problem",
+                "lmpc_fleet_ss_create", "lmpc_fleet_ss_destroy", "lmpc_fleet_ss_reset", "lmpc_fleet_ss_bytes", "lmpc_fleet_ss_record_batch",
+                "lmpc_fleet_ss_query_batch", "lmpc_fleet_ss_load", "lmpc_fleet_ss_get_laps", "lmpc_fleet_ss_stats")
 
 
 class LmpcError(RuntimeError):
@@ -573,3 +575,100 @@ class Solver:
         rc = self.lib.lmpc_ss_query_batch(self._h, C.c_int32(B), _ptr(q), _ptr(ss_x), _ptr(ss_j), _ptr(nf))
         self._check(rc, "lmpc_ss_query_batch")
         return ss_x, ss_j, nf
+
+    # ---- fleet safe set: one recorder and one ring of laps per car, on the device (include/lmpc_hip.h) ----
+    def fleet_ss_create(self, batch: int, max_pts_per_lap: int) -> int:
+        """lmpc_fleet_ss_create: a store for `batch` cars, max_lap_stored laps of at most max_pts_per_lap samples each (replaces an
+        earlier one).  Returns the bytes it allocated."""
+        self.use_current_stream()
+        self._check(self.lib.lmpc_fleet_ss_create(self._h, C.c_int32(int(batch)), C.c_int32(int(max_pts_per_lap))), "lmpc_fleet_ss_create")
+        return self.fleet_ss_bytes()
+
+    def fleet_ss_destroy(self):
+        self._check(self.lib.lmpc_fleet_ss_destroy(self._h), "lmpc_fleet_ss_destroy")
+
+    def fleet_ss_reset(self):
+        """Empties every car's recorder and ring without reallocating."""
+        self.use_current_stream()
+        self._check(self.lib.lmpc_fleet_ss_reset(self._h), "lmpc_fleet_ss_reset")
+
+    def fleet_ss_bytes(self) -> int:
+        n = C.c_int64(0)
+        self._check(self.lib.lmpc_fleet_ss_bytes(self._h, C.byref(n)), "lmpc_fleet_ss_bytes")
+        return int(n.value)
+
+    def fleet_ss_record(self, x, u, k, t: float, total_length: float, active=None):
+        """lmpc_fleet_ss_record_batch: SafeSetRecorder.step for every car -- x [6][B], u [2][B], k [B] device tensors, t the time stamp;
+        active (int32 [B], optional): 0 skips the car.  Asynchronous."""
+        self.use_current_stream()
+        x, u, k = self._t(x), self._t(u), self._t(k)
+        if active is not None:
+            active = self._torch.as_tensor(active, dtype=self._torch.int32, device=self.device).contiguous()
+        rc = self.lib.lmpc_fleet_ss_record_batch(self._h, C.c_int32(x.shape[1]), _ptr(x), _ptr(u), _ptr(k), C.c_double(float(t)),
+                                                 C.c_double(float(total_length)), _ptr(active))
+        self._check(rc, "lmpc_fleet_ss_record_batch")
+
+    def fleet_ss_query(self, query, out=None):
+        """lmpc_fleet_ss_query_batch: ss_query with query b run against car b's own ring.  `out` = (ss_x [6][S][B], ss_j [S][B],
+        n_found [B]) reuses the caller's buffers (the kernel writes every entry); otherwise they are allocated."""
+        torch = self._torch
+        self.use_current_stream()
+        q = self._t(query)
+        B = q.shape[1]
+        S = int(self.config["num_ss_pts"])
+        if out is not None:
+            ss_x, ss_j, nf = out
+        else:
+            ss_x = torch.zeros((6, S, B), dtype=torch.float64, device=self.device)
+            ss_j = torch.zeros((S, B), dtype=torch.float64, device=self.device)
+            nf = torch.zeros((B,), dtype=torch.int32, device=self.device)
+        rc = self.lib.lmpc_fleet_ss_query_batch(self._h, C.c_int32(B), _ptr(q), _ptr(ss_x), _ptr(ss_j), _ptr(nf))
+        self._check(rc, "lmpc_fleet_ss_query_batch")
+        return ss_x, ss_j, nf
+
+    def fleet_ss_load(self, laps, total_length: float, car: int = -1):
+        """lmpc_fleet_ss_load: laps = list of (x [n,6], u [n,2], k [n], t [n]) host arrays, oldest first, pushed into the ring of
+        car `car` (-1: of every car)."""
+        import numpy as np
+
+        n_pts = np.array([np.asarray(l[0]).shape[0] for l in laps], dtype=np.int32)
+        if len(laps):
+            cat = [np.ascontiguousarray(np.concatenate([np.asarray(l[i], dtype=np.float64).reshape(n, -1) for l, n in zip(laps, n_pts)], 0))
+                   for i in range(4)]
+        else:
+            cat = [np.zeros((0, w)) for w in (6, 2, 1, 1)]
+        rc = self.lib.lmpc_fleet_ss_load(self._h, C.c_int32(int(car)), C.c_int32(len(laps)), n_pts.ctypes.data_as(C.c_void_p),
+                                         *[a.ctypes.data_as(C.c_void_p) for a in cat], C.c_double(float(total_length)))
+        self._check(rc, "lmpc_fleet_ss_load")
+
+    def fleet_ss_get_laps(self, car: int):
+        """lmpc_fleet_ss_get_laps: the closed laps of one car, oldest first, as a list of (x [n,6], u [n,2], k [n], t [n]) host arrays."""
+        import numpy as np
+
+        n_laps = C.c_int32(0)
+        n_pts = np.zeros(max(int(self.config["max_lap_stored"]), 1), dtype=np.int32)
+        rc = self.lib.lmpc_fleet_ss_get_laps(self._h, C.c_int32(int(car)), C.byref(n_laps), n_pts.ctypes.data_as(C.c_void_p), None, None, None, None)
+        self._check(rc, "lmpc_fleet_ss_get_laps")
+        n_pts = n_pts[:n_laps.value]
+        n = int(n_pts.sum())
+        x, u, k, t = np.zeros((n, 6)), np.zeros((n, 2)), np.zeros(n), np.zeros(n)
+        if n:
+            n_pts2 = np.zeros(max(int(self.config["max_lap_stored"]), 1), dtype=np.int32)
+            rc = self.lib.lmpc_fleet_ss_get_laps(self._h, C.c_int32(int(car)), C.byref(n_laps), n_pts2.ctypes.data_as(C.c_void_p),
+                                                 *[a.ctypes.data_as(C.c_void_p) for a in (x, u, k, t)])
+            self._check(rc, "lmpc_fleet_ss_get_laps")
+        cuts = np.cumsum(n_pts)[:-1]
+        return [tuple(parts) for parts in zip(*(np.split(a, cuts) for a in (x, u, k, t)))] if len(n_pts) else []
+
+    def fleet_ss_stats(self, B: int, out=None):
+        """lmpc_fleet_ss_stats: {"laps_in_ring", "lap_count", "n_dropped"} int32 [B] and "last_lap_time" float64 [B], device tensors;
+        `out` (such a dict) reuses buffers.  Asynchronous."""
+        torch = self._torch
+        self.use_current_stream()
+        if out is None:
+            out = {key: torch.zeros((B,), dtype=torch.int32, device=self.device) for key in ("laps_in_ring", "lap_count", "n_dropped")}
+            out["last_lap_time"] = torch.zeros((B,), dtype=torch.float64, device=self.device)
+        rc = self.lib.lmpc_fleet_ss_stats(self._h, C.c_int32(B), _ptr(out.get("laps_in_ring")), _ptr(out.get("lap_count")),
+                                          _ptr(out.get("n_dropped")), _ptr(out.get("last_lap_time")))
+        self._check(rc, "lmpc_fleet_ss_stats")
+        return out

@@ -245,3 +245,131 @@ def run_lmpc(tracker, learner, track: dict, x0, u0, warm_laps: int = 2, learn_la
         t += dt
     return {"lap_times": lap_times, "lap_kind": lap_kind, "worst_excess": worst_excess, "n_fail": n_fail, "steps": k + 1,
             "laps_in_set": len(man.laps), "x": x, "warm_hit_rate": (n_hit / n_warm) if n_warm else None}
+
+
+def run_lmpc_fleet(tracker, learner, track: dict, x0, u0, warm_laps: int = 2, learn_laps: int = 4, dt: float = 0.025,
+                   n_sub: int = 2, warm_speed_scale: float = 0.7, max_steps: int = 20000, max_pts_per_lap: int = 1024,
+                   record_trace: bool = False):
+    """run_lmpc with every car learning from ITS OWN laps: the fleet safe set on `learner` (lmpc_fleet_ss_*: one recorder and one
+    ring of max_lap_stored laps per car, on the device) replaces the host recorder of car 0 and the shared store.  Per period, in
+    run_lmpc's order: record (x, u_prev, curvature at s, t) for all cars, query every learning car's own ring, solve, plant step,
+    shift.  Car b switches from the tracking to the learning controller when its own ring holds `warm_laps` laps; while the fleet is
+    mixed both controllers solve the batch and results and shifted inputs are selected per car (the cars not learning yet pass
+    through the learning kernel on the zero-filled set the query writes for an empty ring, and their status from it is ignored);
+    when all cars are in one phase only that controller runs.  Stops when every car has `learn_laps` learning laps, or at max_steps.
+
+    No state is copied to the host: lap times and kinds are kept on the device from lmpc_fleet_ss_stats (a lap's kind is the phase
+    its car drove it in; the lap at whose close a car switches is still "tracking").  The host reads one small int32 tensor per
+    period -- laps_in_ring [B] and, beside it, the per-car "has its learning laps" flag -- to decide which controllers to launch.
+
+    Returns "lap_times" / "lap_kind": per car the list of its closed laps in order (at most warm_laps + learn_laps + 8 are kept),
+    device tensors "worst_excess", "n_fail" (failures of the controller the car was driving with), "n_dropped", "laps_in_ring", and
+    "steps", "x"; record_trace=True adds "trace", the (x, u, k, t) handed to the recorder each period."""
+    import numpy as np
+    import torch
+
+    trk = tracker.device_track(track)
+    L = float(track["L"])
+    B = x0.shape[1]
+    dev = x0.device
+    learner.fleet_ss_create(B, max_pts_per_lap)
+    x, u_prev = x0.clone(), u0.clone()
+    half_b = float(tracker.vehicle["b"]) / 2.0
+    worst_excess = torch.zeros(B, dtype=torch.float64, device=dev)
+    n_fail = torch.zeros(B, dtype=torch.int64, device=dev)
+    inp = tracker.prepare(trk, x, dt, speed_scale=warm_speed_scale)
+    out_t, out_l = tracker.alloc_outputs(B), learner.alloc_outputs(B)
+    S = int(learner.config["num_ss_pts"])
+    out_l["convex_combi_optm"] = torch.zeros((S, B), dtype=torch.float64, device=dev)
+    ss_buf = (torch.zeros((6, S, B), dtype=torch.float64, device=dev), torch.zeros((S, B), dtype=torch.float64, device=dev),
+              torch.zeros((B,), dtype=torch.int32, device=dev))
+    curv = trk["curvature"]
+    M = int(curv.numel())
+    x_lo = torch.as_tensor(learner.config["x_min"], dtype=torch.float64, device=dev)[:, None]
+    x_hi = torch.as_tensor(learner.config["x_max"], dtype=torch.float64, device=dev)[:, None]
+    keys = ("X_ref", "U_ref", "T_ref", "bound_left", "bound_right", "curvatures", "vel_ref")
+    # device bookkeeping of the laps: slot i of car b is its i-th closed lap
+    n_rec = warm_laps + learn_laps + 8
+    lap_time = torch.zeros((n_rec, B), dtype=torch.float64, device=dev)
+    lap_learn = torch.zeros((n_rec, B), dtype=torch.bool, device=dev)
+    n_learn = torch.zeros(B, dtype=torch.int64, device=dev)
+    learning_d = torch.zeros(B, dtype=torch.bool, device=dev)
+    small = torch.zeros((2, B), dtype=torch.int32, device=dev)   # what the host reads: laps_in_ring, done
+    stats = {"laps_in_ring": small[0], "lap_count": torch.zeros(B, dtype=torch.int32, device=dev),
+             "n_dropped": torch.zeros(B, dtype=torch.int32, device=dev), "last_lap_time": torch.zeros(B, dtype=torch.float64, device=dev)}
+    count_prev = torch.zeros(B, dtype=torch.int32, device=dev)
+    learning = np.zeros(B, dtype=bool)   # host mirror of learning_d
+    trace, t, k = [], 0.0, -1
+    for k in range(max_steps):
+        # x_ic by the phase the car was in BEFORE this period's sample (run_lmpc sets it before its recorder step): learning cars get
+        # the measured state projected onto the state box
+        if learning.all():
+            x_ic = torch.minimum(torch.maximum(x, x_lo), x_hi)
+        elif learning.any():
+            x_ic = torch.where(learning_d[None, :], torch.minimum(torch.maximum(x, x_lo), x_hi), x)
+        else:
+            x_ic = x
+        inp["x_ic"], inp["u_ic"] = x_ic, u_prev
+        # every car feeds its recorder: state, applied input, curvature at its abscissa (periodic linear interpolation), time
+        pos = torch.remainder(x[0], L) * (M / L)
+        i0 = torch.clamp(pos.floor().long(), 0, M - 1)
+        fr = pos - i0
+        kap = curv[i0] * (1.0 - fr) + curv[(i0 + 1) % M] * fr
+        if record_trace:
+            trace.append((x.clone(), u_prev.clone(), kap.clone(), t))
+        learner.fleet_ss_record(x, u_prev, kap, t, L)
+        learner.fleet_ss_stats(B, out=stats)
+        closed = (stats["lap_count"] != count_prev) & (count_prev >= 1)   # (the first crossing closes the discarded partial lap)
+        slot = torch.clamp(count_prev.long() - 1, 0, n_rec - 1)[None, :]
+        keep = (closed & (count_prev <= n_rec))[None, :]
+        lap_time.scatter_(0, slot, torch.where(keep, stats["last_lap_time"][None, :], lap_time.gather(0, slot)))
+        lap_learn.scatter_(0, slot, torch.where(keep, learning_d[None, :], lap_learn.gather(0, slot)))
+        n_learn += (closed & learning_d).to(torch.int64)
+        count_prev.copy_(stats["lap_count"])
+        learning_d |= small[0] >= warm_laps   # after the lap's kind was noted
+        small[1].copy_((n_learn >= learn_laps).to(torch.int32))
+        host = small.cpu().numpy()            # the period's one read
+        learning |= host[0] >= warm_laps
+        if host[1].all():
+            break
+        some, every = bool(learning.any()), bool(learning.all())
+        if some:
+            # query = last knot of the abscissa-aligned reference (racing_mpc.cpp:219-223,249-254)
+            s_last, s0 = inp["X_ref"][0, -1], x[0]
+            kk = (s0 - s_last).abs() + L / 2
+            q = torch.stack([s_last + (kk - torch.fmod(kk, L)) * torch.sign(s0 - s_last), inp["X_ref"][1, -1]]).contiguous()
+            ss_x, ss_j, _ = learner.fleet_ss_query(q, out=ss_buf)
+            learner.solve(inp, out_l, ss_x=ss_x, ss_j=ss_j)
+        if not every:
+            tracker.solve(inp, out_t)
+        if every:
+            out = out_l
+        elif not some:
+            out = out_t
+        else:
+            out = {"X_optm": torch.where(learning_d, out_l["X_optm"], out_t["X_optm"]),
+                   "U_optm": torch.where(learning_d, out_l["U_optm"], out_t["U_optm"]),
+                   "status": torch.where(learning_d, out_l["status"], out_t["status"])}
+        ok = out["status"] == 0
+        n_fail += (~ok).to(torch.int64)
+        u_apply = torch.where(ok[None, :], out["U_optm"][:, 0, :], inp["U_ref"][:, 0, :]).contiguous()
+        (learner if every else tracker).plant_step(trk, x, u_apply, dt / n_sub, n_sub)
+        exc = torch.maximum(x[1] + half_b - inp["bound_left"][0], inp["bound_right"][0] - (x[1] - half_b))
+        worst_excess = torch.maximum(worst_excess, exc)
+        u_prev = u_apply
+        if every:
+            inp = learner.shift(trk, inp, out, dt, speed_scale=1.0)
+        elif not some:
+            inp = tracker.shift(trk, inp, out, dt, speed_scale=warm_speed_scale)
+        else:
+            nl, nt = learner.shift(trk, inp, out, dt, speed_scale=1.0), tracker.shift(trk, inp, out, dt, speed_scale=warm_speed_scale)
+            inp = {key: torch.where(learning_d, nl[key], nt[key]) for key in keys}
+            inp["L"] = L
+        t += dt
+    learner.fleet_ss_stats(B, out=stats)
+    n_closed = np.minimum(np.maximum(count_prev.cpu().numpy() - 1, 0), n_rec)
+    lt, lk = lap_time.cpu().numpy(), lap_learn.cpu().numpy()
+    return {"lap_times": [[float(v) for v in lt[:n_closed[b], b]] for b in range(B)],
+            "lap_kind": [["lmpc" if v else "tracking" for v in lk[:n_closed[b], b]] for b in range(B)],
+            "worst_excess": worst_excess, "n_fail": n_fail, "n_dropped": stats["n_dropped"].clone(),
+            "laps_in_ring": stats["laps_in_ring"].clone(), "steps": k + 1, "x": x, "trace": trace}

@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "lmpc_device.h"
+#include "lmpc_fleet_ss.h"
 
 template <bool WS_LAYOUT, typename io, int W>
 __global__ void lmpc_linearize_kernel(lmpc_params, int, const io*, const io*, const io*, const io*, io*, io*, io*);
@@ -90,6 +91,13 @@ struct lmpc_handle {
   int reg_npad = 0;           // their number, padded to a multiple of four with unreachable rows
   bool reg_exact = false;     // features large against the bandwidth: the kernel recomputes each weight from sum (z - q)^2
   lmpc_regression_spec reg_spec{};
+  // fleet safe set (lmpc_fleet_ss_create): one recorder and one ring of laps per car, csrc/lmpc_fleet_ss.h
+  lmpc_fleet_store fleet{};
+  int* fleet_meta = nullptr;     // the store's per-car int arrays, one allocation (zeroed by lmpc_fleet_ss_reset)
+  double* fleet_metad = nullptr;  // and its per-car double arrays
+  size_t fleet_meta_n = 0, fleet_metad_n = 0;
+  int64_t fleet_bytes = 0;
+  double fleet_L = 0.0;  // total_length of the last record / load call: what the query unrolls the laps by
   // staging for the single-problem host entry points (lmpc_solve_host, lmpc_ss_query_host): device buffers and PINNED
   // host mirrors, all sized and allocated by lmpc_create -- the per-step path of one controller allocates nothing
   double* stage_dev = nullptr;
@@ -538,6 +546,7 @@ void lmpc_destroy(lmpc_handle* h) {
   if (h->reg_u) (void)hipFree(h->reg_u);
   if (h->reg_y) (void)hipFree(h->reg_y);
   if (h->reg_tab) (void)hipFree(h->reg_tab);
+  (void)lmpc_fleet_ss_destroy(h);
   if (h->stage_dev) (void)hipFree(h->stage_dev);
   if (h->stage_int) (void)hipFree(h->stage_int);
   if (h->sqp_ws) (void)hipFree(h->sqp_ws);
@@ -1500,6 +1509,253 @@ int lmpc_regress_batch(lmpc_handle* h, int32_t batch, const double* X_ref, const
   if (batch == 0) return LMPC_OK;
   HIP_TRY(h, hipSetDevice(h->device));
   return launch_regress<false>(h, batch, X_ref, U_ref, A, Bm, g);
+}
+
+
+// ---- fleet safe set: one recorder and one ring of laps per car (csrc/lmpc_fleet_ss.h, csrc/lmpc_fleet_ss_kernel.hip) ----
+int lmpc_fleet_ss_destroy(lmpc_handle* h) {
+  if (!h) return LMPC_ERR_ARGUMENT;
+  if (!h->fleet.B) return LMPC_OK;
+  (void)hipSetDevice(h->device);
+  (void)hipStreamSynchronize(h->stream);
+  if (h->fleet.key) (void)hipFree(h->fleet.key);
+  if (h->fleet.xr) (void)hipFree(h->fleet.xr);
+  if (h->fleet.aux) (void)hipFree(h->fleet.aux);
+  if (h->fleet_meta) (void)hipFree(h->fleet_meta);
+  if (h->fleet_metad) (void)hipFree(h->fleet_metad);
+  h->fleet = lmpc_fleet_store{};
+  h->fleet_meta = nullptr;
+  h->fleet_metad = nullptr;
+  h->fleet_meta_n = h->fleet_metad_n = 0;
+  h->fleet_bytes = 0;
+  h->fleet_L = 0.0;
+  return LMPC_OK;
+}
+
+int lmpc_fleet_ss_reset(lmpc_handle* h) {
+  if (!h) return LMPC_ERR_ARGUMENT;
+  if (!h->fleet.B) return fail(h, LMPC_ERR_ARGUMENT, "lmpc_fleet_ss_reset: no fleet store (lmpc_fleet_ss_create)");
+  HIP_TRY(h, hipSetDevice(h->device));
+  HIP_TRY(h, hipMemsetAsync(h->fleet_meta, 0, h->fleet_meta_n * sizeof(int), h->stream));
+  HIP_TRY(h, hipMemsetAsync(h->fleet_metad, 0, h->fleet_metad_n * sizeof(double), h->stream));
+  return LMPC_OK;
+}
+
+int lmpc_fleet_ss_create(lmpc_handle* h, int32_t batch, int32_t max_pts_per_lap) {
+  if (!h) return LMPC_ERR_ARGUMENT;
+  if (batch < 1 || max_pts_per_lap < 1) return fail(h, LMPC_ERR_ARGUMENT, "lmpc_fleet_ss_create: batch and max_pts_per_lap must be positive");
+  if (h->cfg.max_lap_stored < 1)
+    return fail(h, LMPC_ERR_ARGUMENT, "lmpc_fleet_ss_create: lmpc_config.max_lap_stored must be positive (a fleet ring is bounded)");
+  // 80 bytes per sample; the sample count is held below 2^36 (5.5 TB) so that no size below can overflow
+  const unsigned long long slots = (unsigned long long)batch * ((unsigned long long)h->cfg.max_lap_stored + 1ull);
+  if (slots > (1ull << 36) / (unsigned long long)max_pts_per_lap)
+    return fail(h, LMPC_ERR_ARGUMENT, "lmpc_fleet_ss_create: batch x (max_lap_stored + 1) x max_pts_per_lap is too large");
+  const size_t rows = (size_t)slots * (size_t)max_pts_per_lap;
+  const int rc0 = lmpc_fleet_ss_destroy(h);
+  if (rc0 != LMPC_OK) return rc0;
+  HIP_TRY(h, hipSetDevice(h->device));
+  lmpc_fleet_store st{};
+  st.B = batch;
+  st.R = h->cfg.max_lap_stored;
+  st.C = max_pts_per_lap;
+  const size_t Bz = (size_t)batch, meta_n = (size_t)slots + 7 * Bz, metad_n = Bz * (1 + LMPC_FLEET_DUR);
+  int* meta = nullptr;
+  double* metad = nullptr;
+  hipError_t e = hipMalloc(&st.key, rows * sizeof(double2));
+  if (e == hipSuccess) e = hipMalloc(&st.xr, rows * 4 * sizeof(double));
+  if (e == hipSuccess) e = hipMalloc(&st.aux, rows * 4 * sizeof(double));
+  if (e == hipSuccess) e = hipMalloc(&meta, meta_n * sizeof(int));
+  if (e == hipSuccess) e = hipMalloc(&metad, metad_n * sizeof(double));
+  if (e == hipSuccess) e = hipMemsetAsync(meta, 0, meta_n * sizeof(int), h->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(metad, 0, metad_n * sizeof(double), h->stream);
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    for (void* q : {(void*)st.key, (void*)st.xr, (void*)st.aux, (void*)meta, (void*)metad})
+      if (q) (void)hipFree(q);
+    return fail(h, LMPC_ERR_RUNTIME, std::string("lmpc_fleet_ss_create: ") + hipGetErrorString(e));
+  }
+  st.npts = meta;
+  st.head = meta + slots;
+  st.cnt = st.head + Bz;
+  st.open_n = st.cnt + Bz;
+  st.flags = st.open_n + Bz;
+  st.lap_count = st.flags + Bz;
+  st.n_dropped = st.lap_count + Bz;
+  st.dur_n = st.n_dropped + Bz;
+  st.s_prev = metad;
+  st.dur = metad + Bz;
+  h->fleet = st;
+  h->fleet_meta = meta;
+  h->fleet_metad = metad;
+  h->fleet_meta_n = meta_n;
+  h->fleet_metad_n = metad_n;
+  h->fleet_bytes = (int64_t)(rows * 80 + meta_n * sizeof(int) + metad_n * sizeof(double));
+  h->fleet_L = 0.0;
+  return LMPC_OK;
+}
+
+int lmpc_fleet_ss_bytes(const lmpc_handle* h, int64_t* bytes) {
+  if (!h || !bytes) return LMPC_ERR_ARGUMENT;
+  *bytes = h->fleet_bytes;
+  return LMPC_OK;
+}
+
+namespace {
+int fleet_check(lmpc_handle* h, int32_t batch, const char* who) {
+  if (!h->fleet.B) return fail(h, LMPC_ERR_ARGUMENT, std::string(who) + ": no fleet store (lmpc_fleet_ss_create)");
+  if (batch != h->fleet.B)
+    return fail(h, LMPC_ERR_ARGUMENT, std::string(who) + ": batch " + std::to_string(batch) + " is not the store's " + std::to_string(h->fleet.B));
+  return LMPC_OK;
+}
+}  // namespace
+
+int lmpc_fleet_ss_record_batch(lmpc_handle* h, int32_t batch, const double* x, const double* u, const double* k, double t,
+                               double total_length, const int32_t* active) {
+  if (!h) return LMPC_ERR_ARGUMENT;
+  if (!x || !u || !k || !(total_length > 0.0)) return fail(h, LMPC_ERR_ARGUMENT, "lmpc_fleet_ss_record_batch: null pointer or bad total_length");
+  const int rc = fleet_check(h, batch, "lmpc_fleet_ss_record_batch");
+  if (rc != LMPC_OK) return rc;
+  HIP_TRY(h, hipSetDevice(h->device));
+  h->fleet_L = total_length;
+  hipLaunchKernelGGL(lmpc_fleet_ss_record_kernel, dim3((batch + 255) / 256), dim3(256), 0, h->stream, h->fleet, x, u, k, t, total_length,
+                     active);
+  HIP_TRY(h, hipGetLastError());
+  return LMPC_OK;
+}
+
+int lmpc_fleet_ss_query_batch(lmpc_handle* h, int32_t batch, const double* query, double* ss_x, double* ss_j, int32_t* n_found) {
+  if (!h) return LMPC_ERR_ARGUMENT;
+  if (!query || !ss_x || !ss_j || !n_found) return fail(h, LMPC_ERR_ARGUMENT, "lmpc_fleet_ss_query_batch: null pointer");
+  const int rc = fleet_check(h, batch, "lmpc_fleet_ss_query_batch");
+  if (rc != LMPC_OK) return rc;
+  if (h->cfg.num_ss_pts < 1 || h->cfg.num_ss_pts_per_lap < 1)
+    return fail(h, LMPC_ERR_ARGUMENT, "num_ss_pts / num_ss_pts_per_lap not configured");
+  if (h->cfg.num_ss_pts_per_lap > 64) return fail(h, LMPC_ERR_ARGUMENT, "lmpc_fleet_ss_query_batch: num_ss_pts_per_lap > 64");
+  HIP_TRY(h, hipSetDevice(h->device));
+  hipLaunchKernelGGL(lmpc_fleet_ss_query_kernel, dim3(8 * ((batch + 7) / 8)), dim3(64), 0, h->stream, h->fleet, h->cfg.num_ss_pts,
+                     h->cfg.num_ss_pts_per_lap, h->fleet_L, query, ss_x, ss_j, n_found);
+  HIP_TRY(h, hipGetLastError());
+  return LMPC_OK;
+}
+
+int lmpc_fleet_ss_stats(lmpc_handle* h, int32_t batch, int32_t* laps_in_ring, int32_t* lap_count, int32_t* n_dropped,
+                        double* last_lap_time) {
+  if (!h) return LMPC_ERR_ARGUMENT;
+  const int rc = fleet_check(h, batch, "lmpc_fleet_ss_stats");
+  if (rc != LMPC_OK) return rc;
+  HIP_TRY(h, hipSetDevice(h->device));
+  hipLaunchKernelGGL(lmpc_fleet_ss_stats_kernel, dim3((batch + 255) / 256), dim3(256), 0, h->stream, h->fleet, laps_in_ring, lap_count,
+                     n_dropped, last_lap_time);
+  HIP_TRY(h, hipGetLastError());
+  return LMPC_OK;
+}
+
+int lmpc_fleet_ss_load(lmpc_handle* h, int32_t car, int32_t n_laps, const int32_t* n_pts, const double* x, const double* u,
+                       const double* k, const double* t, double total_length) {
+  if (!h) return LMPC_ERR_ARGUMENT;
+  if (!h->fleet.B) return fail(h, LMPC_ERR_ARGUMENT, "lmpc_fleet_ss_load: no fleet store (lmpc_fleet_ss_create)");
+  if (car < -1 || car >= h->fleet.B || n_laps < 0 || (n_laps > 0 && (!n_pts || !x || !u || !k || !t)) || !(total_length > 0.0))
+    return fail(h, LMPC_ERR_ARGUMENT, "lmpc_fleet_ss_load: bad argument");
+  for (int l = 0; l < n_laps; ++l) {
+    if (n_pts[l] < 1) return fail(h, LMPC_ERR_ARGUMENT, "lmpc_fleet_ss_load: empty lap");
+    if (n_pts[l] > h->fleet.C)
+      return fail(h, LMPC_ERR_ARGUMENT, "lmpc_fleet_ss_load: lap " + std::to_string(l) + " has " + std::to_string(n_pts[l]) +
+                                            " samples, the store's capacity is " + std::to_string(h->fleet.C));
+  }
+  h->fleet_L = total_length;
+  if (n_laps == 0) return LMPC_OK;
+  // the ring keeps the last max_lap_stored laps: the earlier ones of a longer list would be pushed out again (their count stays)
+  const int first = n_laps > h->fleet.R ? n_laps - h->fleet.R : 0;
+  std::vector<int> ln, lo;
+  size_t skip = 0, kept = 0;
+  for (int l = 0; l < n_laps; ++l) {
+    if (l < first) {
+      skip += (size_t)n_pts[l];
+      continue;
+    }
+    lo.push_back((int)kept);
+    ln.push_back(n_pts[l]);
+    kept += (size_t)n_pts[l];
+  }
+  HIP_TRY(h, hipSetDevice(h->device));
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  const int nl = (int)ln.size();
+  double* dev = nullptr;
+  int* devi = nullptr;
+  hipError_t e = hipMalloc(&dev, kept * 10 * sizeof(double));
+  if (e == hipSuccess) e = hipMalloc(&devi, (size_t)2 * nl * sizeof(int));
+  double *dx = dev, *du = dev + kept * 6, *dk = dev + kept * 8, *dt = dev + kept * 9;
+  if (e == hipSuccess) e = hipMemcpy(dx, x + skip * 6, kept * 6 * sizeof(double), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(du, u + skip * 2, kept * 2 * sizeof(double), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(dk, k + skip, kept * sizeof(double), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(dt, t + skip, kept * sizeof(double), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(devi, ln.data(), (size_t)nl * sizeof(int), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(devi + nl, lo.data(), (size_t)nl * sizeof(int), hipMemcpyHostToDevice);
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(lmpc_fleet_ss_load_kernel, dim3(car < 0 ? h->fleet.B : 1), dim3(256), 0, h->stream, h->fleet, (int)car, nl, devi,
+                       devi + nl, dx, du, dk, dt);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+  if (e == hipSuccess && first > 0) {  // SafeSetRecorder::load counts every lap it adds (safe_set.cpp:270)
+    // (the laps that did not fit the ring were added and pushed out again upstream: they count)
+    std::vector<int> lc((size_t)h->fleet.B);
+    e = hipMemcpy(lc.data(), h->fleet.lap_count, lc.size() * sizeof(int), hipMemcpyDeviceToHost);
+    for (int b = 0; b < h->fleet.B; ++b)
+      if (car < 0 || b == car) lc[(size_t)b] += first;
+    if (e == hipSuccess) e = hipMemcpy(h->fleet.lap_count, lc.data(), lc.size() * sizeof(int), hipMemcpyHostToDevice);
+  }
+  if (dev) (void)hipFree(dev);
+  if (devi) (void)hipFree(devi);
+  if (e != hipSuccess) return fail(h, LMPC_ERR_RUNTIME, std::string("lmpc_fleet_ss_load: ") + hipGetErrorString(e));
+  return LMPC_OK;
+}
+
+int lmpc_fleet_ss_get_laps(lmpc_handle* h, int32_t car, int32_t* n_laps, int32_t* n_pts, double* x, double* u, double* k, double* t) {
+  if (!h) return LMPC_ERR_ARGUMENT;
+  if (!h->fleet.B) return fail(h, LMPC_ERR_ARGUMENT, "lmpc_fleet_ss_get_laps: no fleet store (lmpc_fleet_ss_create)");
+  if (car < 0 || car >= h->fleet.B || !n_laps) return fail(h, LMPC_ERR_ARGUMENT, "lmpc_fleet_ss_get_laps: bad car or null n_laps");
+  if ((x || u || k || t) && !n_pts) return fail(h, LMPC_ERR_ARGUMENT, "lmpc_fleet_ss_get_laps: the sample arrays need n_pts");
+  const lmpc_fleet_store& st = h->fleet;
+  HIP_TRY(h, hipSetDevice(h->device));
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  const int R1 = st.R + 1;
+  int head = 0, cnt = 0;
+  std::vector<int> np((size_t)R1);
+  HIP_TRY(h, hipMemcpy(&head, st.head + car, sizeof(int), hipMemcpyDeviceToHost));
+  HIP_TRY(h, hipMemcpy(&cnt, st.cnt + car, sizeof(int), hipMemcpyDeviceToHost));
+  HIP_TRY(h, hipMemcpy(np.data(), st.npts + (size_t)car * R1, (size_t)R1 * sizeof(int), hipMemcpyDeviceToHost));
+  if (head < 0 || head >= R1 || cnt < 0 || cnt > st.R) return fail(h, LMPC_ERR_RUNTIME, "lmpc_fleet_ss_get_laps: corrupt ring state");
+  *n_laps = cnt;
+  std::vector<double> key, xr, ax;
+  size_t o = 0;
+  for (int a = 0; a < cnt; ++a) {  // oldest first
+    const int sl = ((head - cnt + a) % R1 + R1) % R1;
+    const int n = np[(size_t)sl] < st.C ? np[(size_t)sl] : st.C;
+    if (n_pts) n_pts[a] = n;
+    if (!(x || u || k || t) || n < 1) continue;
+    const size_t row = ((size_t)car * R1 + sl) * st.C;
+    key.resize((size_t)n * 2);
+    xr.resize((size_t)n * 4);
+    ax.resize((size_t)n * 4);
+    HIP_TRY(h, hipMemcpy(key.data(), st.key + row, (size_t)n * 16, hipMemcpyDeviceToHost));
+    HIP_TRY(h, hipMemcpy(xr.data(), st.xr + row * 4, (size_t)n * 32, hipMemcpyDeviceToHost));
+    HIP_TRY(h, hipMemcpy(ax.data(), st.aux + row * 4, (size_t)n * 32, hipMemcpyDeviceToHost));
+    for (int i = 0; i < n; ++i, ++o) {
+      if (x) {
+        x[o * 6] = key[(size_t)i * 2];
+        x[o * 6 + 1] = key[(size_t)i * 2 + 1];
+        for (int c = 0; c < 4; ++c) x[o * 6 + 2 + c] = xr[(size_t)i * 4 + c];
+      }
+      if (u) {
+        u[o * 2] = ax[(size_t)i * 4];
+        u[o * 2 + 1] = ax[(size_t)i * 4 + 1];
+      }
+      if (k) k[o] = ax[(size_t)i * 4 + 2];
+      if (t) t[o] = ax[(size_t)i * 4 + 3];
+    }
+  }
+  return LMPC_OK;
 }
 
 }  // extern "C"
