@@ -4,8 +4,8 @@ the debug-hook build).
 
 The library picks a kernel from (N, num_ss_pts, precision): `real` in {double, float}, KQ = slots per lane in {2, 4, 7, 11, 14}
 (N <= 11 / 23 / 40 / 64 / 81), KS = safe-set points per lane in {0, 2, 3} (none / <= 128 / <= 192 points), `io` in {double,
-float}; lean or fat LDS records, polish inlined or called, DPP or LDS sweeps follow from those (csrc/lmpc_capi.hip `kq_for`,
-`ks_for`, `pick_*_fn`; lmpc_query_launch_for reports what an entry point would launch).  Rounds 2 - 4 each met an instantiation
+float}; lean or fat LDS records, polish inlined or called, DPP or LDS sweeps follow from those (csrc/lmpc_capi.hip `kernel_table`
+and `choose_kernel`; lmpc_query_launch_for reports what an entry point would launch).  Rounds 2 - 4 each met an instantiation
 that miscomputed under a source change that should not matter ("the register-starved instantiations"): a
 compiler-sensitive corner that only an every-problem check of EVERY instantiation notices.  So: every N from 3 to 81 -- not a
 hand-picked list: slots wrap round the lanes differently at every N -- x {BARC tracking, IAC tracking, learning with 96 points
