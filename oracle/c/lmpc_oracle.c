@@ -437,7 +437,7 @@ static inline double slot_val(double (*z)[8], double (*v)[2], int i, int sl) {
 #define STALL_STEP 1e-6 /* scaled size of the last primal step above which a stalled, unpolished iterate is not vouched for (ipm_solve's exit) */
 #endif
 #define MA_MAX 6 /* four until round 5: a five-lap safe set has optima that blend one point per lap, and the fifth point then went
-                  * through 1 / theta -> 1e12 (cond(F_B) with it): answers 1e-2 off, reported OPTIMAL (csrc/lmpc_solve_kernel.hip) */
+                  * through 1 / theta -> 1e12 (cond(F_B) with it): answers 1e-2 off, reported OPTIMAL (csrc/lmpc_terminal.hip.h, MA_MAX) */
 #define TAU_REL 1e-5 /* tau = TAU_REL * max_j u_j'E u_j: cond(F_B) <= ~1e5 */
 typedef struct {
   double Fi[36];       /* F^-1 over all points */

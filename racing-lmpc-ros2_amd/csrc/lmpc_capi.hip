@@ -219,9 +219,7 @@ int ks_for(int S) { return S <= 0 ? 0 : (S <= 128 ? 2 : (S <= 192 ? 3 : -1)); }
 
 // which cold fp64 tracking solves take the two-wave kernels: forced by lmpc_set_waves_per_problem, else by measurement (LMPC_W2_AUTO_KQ:
 // the smallest one-wave slot count from which two waves are the default)
-#ifndef LMPC_W2_AUTO_KQ
 #define LMPC_W2_AUTO_KQ 11  // N >= 41 (with the fused factorisation in both): N = 80 9.70 -> 8.06 ms per 4096, N = 65 6.59 -> 5.32, N = 41 .. 64 -1 .. 4 %; N <= 40 +5 %: one wave (profiles/r06_fuse_ab.txt)
-#endif
 
 // what is asked of a handle: the cold solve of an entry point (SOLVE_F64: as lmpc_solve_batch launches it, one or two waves;
 // SOLVE_F64_ONE_WAVE: whatever the wave setting), the fp64 second pass of a mixed solve, the warm start
@@ -1178,7 +1176,7 @@ int lmpc_loop_advance_batch(lmpc_handle* h, int32_t batch, const lmpc_track* tra
   static_assert(sizeof(long long) == sizeof(int64_t) && sizeof(unsigned long long) == sizeof(uint64_t), "counter types");
   lmpc_params PL = h->P;
   PL.warm_flag = (h->warm_flag.get() && h->warm_flag_n == batch) ? h->warm_flag.get() : nullptr;  // the last solve of this batch was a warm one
-  hipLaunchKernelGGL(lmpc_loop_advance_kernel, dim3((batch + 63) / 64), dim3(64 * LMPC_LOOP_WAVES), 0, h->stream, PL, batch, *track, status, iters, X_optm,
+  hipLaunchKernelGGL(lmpc_loop_advance_kernel, dim3((batch + 63) / 64), dim3(64 * lmpc_loop_waves), 0, h->stream, PL, batch, *track, status, iters, X_optm,
                      U_optm, x, u_prev, dt, dt_sim, n_sub, speed_scale, speed_limit, restart_failed ? 1 : 0, X_ref, U_ref, T_ref, bound_left,
                      bound_right, curvatures, vel_ref, distance, worst_excess, reinterpret_cast<long long*>(n_fail),
                      reinterpret_cast<unsigned long long*>(n_accepted));

@@ -62,7 +62,7 @@ struct lmpc_params {
 #define LMPC_KNOT_STRIDE 36
 #define LMPC_TAIL_DOUBLES 320
 // learning: the terminal region behind the records -- always fp64 cells, whatever the records' type: the terminal-block
-// scratch (lmpc_solve_kernel.hip TL_*) and the (centred) safe-set points [6][64 KS], KS = 2 up to 128 points, 3 up to 192
+// scratch (lmpc_terminal.hip.h TL_*) and the (centred) safe-set points [6][64 KS], KS = 2 up to 128 points, 3 up to 192
 #define LMPC_TERM_CELLS 272
 #define LMPC_SS_STRIDE(S) ((S) + 1)  // safe-set points kept behind the terminal cells, 6 cells each: S of them + one zero point
 #define LMPC_LIN_RECORD 54  // per stage in the linearisation workspace: ABt[8][6] | g[6]
@@ -71,9 +71,7 @@ struct lmpc_params {
 // through two chunk buffers of LMPC_LEAN_CHUNK workspace records
 #define LMPC_LEAN_STAGE_STRIDE 24
 #define LMPC_LEAN_CHUNK 8
-#ifndef LMPC_LEAN_MIN_KQ
 #define LMPC_LEAN_MIN_KQ 11
-#endif
 // (the kernels' slot classes: 2 / 4 / 7 / 11 / 14 slots per lane for N <= 11 / 23 / 40 / 64 / 81; lean from LMPC_LEAN_MIN_KQ slots on)
 static inline int lmpc_slot_class(int N) { return N <= 11 ? 2 : (N <= 23 ? 4 : (N <= 40 ? 7 : (N <= 64 ? 11 : 14))); }
 static inline int lmpc_is_lean(int N, int real_bytes) { return real_bytes == 8 && lmpc_slot_class(N) >= LMPC_LEAN_MIN_KQ; }

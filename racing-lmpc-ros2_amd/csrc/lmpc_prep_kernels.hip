@@ -269,15 +269,13 @@ __global__ __launch_bounds__(256) void lmpc_prepare_kernel(lmpc_params P, int B,
 // preparation at its new state (:210-235, 261-292).  The same arithmetic as lmpc_plant_kernel, lmpc_shift_kernel and
 // lmpc_prepare_kernel in that order (tests/test_gpu_loop.py: bit for bit, but for the last knot's one-step rollout, where the inlined
 // model is contracted differently here and there: 1 - 2 ulp) without the ~40 small launches between them.
-// A workgroup is 64 cars (the lanes) x LMPC_LOOP_WAVES waves.  Wave 0 applies the input, steps the plant and keeps the books;
+// A workgroup is 64 cars (the lanes) x lmpc_loop_waves waves.  Wave 0 applies the input, steps the plant and keeps the books;
 // the shift of a car whose solve succeeded has no chain in it except the last knot's rollout, so the waves share its knots
 // (wave w: knots w, w + W, ...; reads from the solution only, writes the references: no hazard, no barrier).  A car whose solve
 // failed is wave 0's alone, knot after knot: the cold restart is a rollout, and the shift of the OLD plan is done in place (a
 // thread reads knot i + 1 before it writes knot i + 1) -- which is why the reference arrays carry no __restrict__.
-#ifndef LMPC_LOOP_WAVES  // (4 / 8 / 16 measured on the closed loop, profiles/r05_tail_ab.txt: 6.49 / 6.53 / 6.36 M car-steps/s at 4096 cars warm)
-#define LMPC_LOOP_WAVES 8
-#endif
-__global__ __launch_bounds__(64 * LMPC_LOOP_WAVES) void lmpc_loop_advance_kernel(
+constexpr int lmpc_loop_waves = 8;  // (measured on the closed loop at 4 / 8 / 16, profiles/r05_tail_ab.txt: 6.49 / 6.53 / 6.36 M car-steps/s at 4096 cars warm)
+__global__ __launch_bounds__(64 * lmpc_loop_waves) void lmpc_loop_advance_kernel(
     lmpc_params P, int B, lmpc_track trk, const int* __restrict__ status, const int* __restrict__ iters, const double* __restrict__ X_sol,
     const double* __restrict__ U_sol, double* __restrict__ x_io, double* __restrict__ u_prev, double dt, double dt_sim, int nsub,
     double speed_scale, double speed_limit, int restart_failed, double* X_ref, double* U_ref, double* T_ref, double* bl, double* br,
@@ -388,7 +386,7 @@ __global__ __launch_bounds__(64 * LMPC_LOOP_WAVES) void lmpc_loop_advance_kernel
   }
   // the solution, shifted: knot i of the new reference is knot i + 1 of the solution; the last one is rolled out from the
   // new knot N - 2 with the repeated last input (racing_mpc_node.cpp:247-249)
-  for (int i = w; i < N; i += LMPC_LOOP_WAVES) {
+  for (int i = w; i < N; i += lmpc_loop_waves) {
     if (i < NS) {
 #pragma unroll
       for (int k = 0; k < 6; ++k) x[k] = X_sol[(size_t)(k * N + i + 1) * B + b];
@@ -493,7 +491,7 @@ __global__ __launch_bounds__(64) void lmpc_shift_lambda_kernel(int B, int S, int
                                                                const int* __restrict__ idx, int advance, double* __restrict__ lam_ref) {
   const int b = blockIdx.x * 64 + threadIdx.x;
   if (b >= B) return;
-  constexpr int MAXSUP = 8, MAXFREE = 6;  // (the terminal block keeps at most six weights explicit: MA_MAX of lmpc_solve_kernel.hip)
+  constexpr int MAXSUP = 8, MAXFREE = 6;  // (the terminal block keeps at most six weights explicit: MA_MAX of lmpc_terminal.hip.h)
   int sup_code[MAXSUP], n = 0;
   double sup_lam[MAXSUP];
   for (int i = 0; i < S; ++i) {

@@ -29,6 +29,10 @@
 // Algorithm (twin of oracle/c/lmpc_oracle.c, which documents the derivation): Mehrotra
 // predictor-corrector interior point; Newton systems by Riccati recursion on (z, v = dU); the
 // shared boundary slack sigma (one scalar coupling all knots) by a Schur complement.
+//
+// This file: the Riccati sweeps of both layouts, the active-set polish, lmpc_solve_problem, the kernels and the lists of what each
+// translation unit instantiates.  What they are written in -- layout and policies, wave primitives, limits, the safe-set terminal
+// block -- is in the four headers included below (DESIGN.md section 4 has the file map); lmpc_solve_w2.hip.h holds the two-wave kernel.
 #include <hip/hip_runtime.h>
 
 #include <type_traits>
@@ -36,802 +40,10 @@
 
 #include "lmpc_device.h"
 
-// waves per SIMD asked of the compiler for the single-precision N <= 23 kernel (its 10 KB records allow 16 per CU):
-// measured 1.04 / 0.93 / 0.97 ms per 8192-batch at 2 / 3 / 4 -- the issue ceiling (LDS pipe, VALU) is ~12 % away
-#ifndef OCCF
-#define OCCF 3
-#endif
-#define NSLOT 11
-// resident waves per SIMD the register allocation is sized for: the fp64 tracking kernels up to N = 23 and every fp32
-// kernel up to N = 40 run two (three for fp32, N <= 23); the fp64 LMPC and long-horizon kernels need the full file
-constexpr int lmpc_waves_per_simd(int real_bytes, int kq, int ks) {
-  return real_bytes == 4 ? ((kq <= 4 && ks == 0) ? OCCF : (kq <= 7 ? 2 : 1)) : ((ks == 0 && kq <= 4) ? 2 : 1);
-}
-
-// Optional per-phase cycle accounting (make prof -> -DLMPC_PHASE_TIMING): one s_memtime read per
-// phase boundary, per-wave totals written over kkt_out as [16][B] doubles (caller allocates 20 rows).
-#ifdef LMPC_PHASE_TIMING
-struct Prof {
-  long long acc[16];
-  long long t, w0;
-};
-#define PT_DECL Prof pf; { for (int k = 0; k < 16; ++k) pf.acc[k] = 0; pf.t = __builtin_readcyclecounter(); pf.w0 = wall_clock64(); }
-#define PT_MARK(k) { const long long pt_n = __builtin_readcyclecounter(); pf.acc[k] += pt_n - pf.t; pf.t = pt_n; }
-#else
-struct Prof {};
-#define PT_DECL Prof pf;
-#define PT_MARK(k)
-#endif
-#define SL_U 6
-#define SL_V 8
-#define SL_EY 10
-
-// ---- LDS layout (doubles) ---------------------------------------------------------------------
-// stage record i (stride 78): M[8][8]: column c of the stage model with the feedback gain appended,
-//                               M[c][k] = [A B][k][c] (k < 6), M[c][6 + j] = K_j[c].  Row c starts at
-//                               ST_ROW(c) = 8 c + 2 (c >> 1): the two-cell skew after every second row puts
-//                               the eight rows on eight different 4-bank groups, so the per-lane row reads
-//                               (b128, lane = row) are conflict-free; column reads (lane = column) stay
-//                               contiguous.  The six skew cells and the tail of the record hold
-//                               Hinv (h00,h01) @16 | (h11, dt) @34 | kff rhs0 [2] @52 | kff rhs1 [2] @70 | g[6] @72
-// knot record i (stride 36):  z[8] v[2] @0 | rhs0: Th / q / d [10] @10 | rhs1: q / e [10] @20
-//                             | csig @30 | eyT / eyD @31 | boundary row bounds (hi, lo) @32 | qlin_vx @34
-// tail: P[8][10] @0 | W[8][10] @80 | Y[8][10] @160 | pvec[2 buf][2 rhs][8] @240 | consts @272 (48)
-#define ST_ROW(c) (8 * (c) + 2 * ((c) >> 1))
-#define ST_HI 16     // h00, h01
-#define ST_HI11 34   // h11
-#define ST_DT 35
-#define ST_KFF(s) ((s) ? 70 : 52)
-#define ST_G 72
-#define KN_R0 10
-#define KN_R1 20
-#define KN_CSIG 30
-#define KN_EY 31
-#define KN_BHL 32
-#define KN_QLIN 34
-#define TL_P 0
-#define TL_W 80
-#define TL_Y 160
-#define TL_PV 240
-#define TL_CT 272
-#define CT_QD 0
-#define CT_QT 6
-#define CT_QU 12
-#define CT_SV 16
-#define CT_HL 20    // box bounds of the ten primal components, (hi, lo) interleaved
-#define CT_ZERO 40  // a 0.0 entry: coefficient slot for "no term"
-#define CT_E 41     // 2 * convex_hull_slack (LMPC)
-// LMPC extension of the tail (only allocated when learning): terminal-block quantities (see term_factor_u)
-// (offsets in `treal` cells from the start of the terminal region, which follows the real-typed records and tail)
-#define TL_PT 0      // PT[6][6]: terminal cost-to-go contributed by the safe-set block
-#define TL_TG 36     // terminal gradient contribution  E eps + pT
-#define TL_EPS 42    // eps = (x_T - ss0) - (SS - ss0 1') lambda
-#define TL_FB 48     // F_B^-1 [6][6], F_B = E^-1 + U_B Th_B^-1 U_B' (the points eliminated through 1/theta)
-#define TL_WA 84     // W_A = F_B^-1 U_A, column a at +6a
-#define TL_UA 120    // u of the explicit points, point a at +6a
-#define TL_LC 156    // C_A^-1 [6][6] (full, symmetric), C_A = Theta_A + U_A'F_B^-1 U_A; C_A itself while it is being formed
-#define TL_X1 192    // C_A^-1 (1_A - W_A'a_B)
-#define TL_G 198     // g = E U M^-1 1
-#define TL_AB 204    // a_B = U_B Th_B^-1 1
-#define TL_RA 210    // right-hand side of the explicit points (written by their owner lanes)
-#define TL_THA 216   // theta of the explicit points
-#define TL_XA 222    // their step d lambda_A (read back by the owner lanes)
-#define TL_S11 228   // s11 = 1'M^-1 1
-#define TL_E 230     // E = 2 convex_hull_slack (exact, whatever `real` is)
-#define TL_Z 236     // Z = C_A^-1 W_A' [6][6] (a product of term_factor_u)
-#define TL_UL 272    // the (centred) safe-set points, point-major [S][6]
-// Explicit points at most (the smallest theta below tau).  Four until round 5 ("supports of 1-3 points are what occurs"): with a
-// FIVE-lap safe set the optimum blends one point per lap, a support of five, on ~0.1 % of the bench distribution at N = 27 .. 29
-// and on most problems at N <= 5 (tests/dispatch_sweep.py found them).  The fifth point then went through 1 / theta with theta ->
-// 1e-12: cond(F_B) 1e12, Newton steps with a stationarity residual of O(1), and an answer 1e-2 from the optimum reported OPTIMAL --
-// by the kernel and its twin alike, so kernel-against-twin tests could not see it; the dense oracle did.  Six is what the terminal
-// block can hold (C_A = Theta_A + U_A'F_B^-1 U_A has rank <= 6 as Theta_A -> 0) and what its LDS cells were laid out for.
-#define MA_MAX 6
-#define TAU_REL 1e-5   // tau = TAU_REL * max_j u_j'E u_j: cond(F_B) <= ~1e5 whatever the iteration does
-#define STALL_MU 1e-9  // complementarity below which a step that does not lower it ends the solve
-#define STALL_STEP 1e-6  // ... and the scaled size of that step above which the stalled iterate, unless the polish verifies it, is MAX_ITER
-#define NBHD_GAMMA 1e-2  // once mu has risen: no complementarity product below this fraction of their mean after a step (1e-3
-                        // does not stop the cycle the rule is there for; applied to every problem 3e-2 costs 13 % more iterations)
-#define NBHD_TRIALS 3   // cuts of the step length by 0.6 at most (two are what the cycling problem needs; bounded so that a point already
-                        // outside the neighbourhood cannot freeze the iteration)
-#define F_UP 1
-#define F_LO 2
-#define F_SIG 4
-#define F_QLIN 8
-#define F_MOVE 16
-#define F_EY 32
-#define F_SCH 64
-// Row r of the 8x8 work matrices P, W, Y starts at MROWS(r) = 8 r + 2 (r >> 1) -- the stage records' skew (ST_ROW): the eight rows
-// sit on eight different 4-bank groups (conflict-free b128 row reads, as with the stride of 10 doubles used until round 5), AND the
-// rows of a 16-lane store group (r = 2g, 2g + 1) are 16 banks apart, so the element stores of W, Y, P -- ds_write_b64: contiguous
-// 16-lane groups, 32 banks -- are conflict-free too; with the stride of 10 rows 2g and 2g + 1 overlapped in four banks: every one of
-// the four stores per factor stage took 8 LDS cycles instead of 4 (40 % of the headline kernel's SQ_LDS_BANK_CONFLICT, round 6).
-#define MROWS(r) (8 * (r) + 2 * ((r) >> 1))
-
-// The workgroup is a single wavefront and the LDS executes one wave's DS instructions in issue order, so cross-lane
-// exchange through LDS needs no s_barrier and no wait for the write to retire: only the compiler must not move memory
-// operations across the exchange point.  __builtin_amdgcn_wave_barrier alone does not say that -- it is declared as not
-// touching memory, so around a store that only SOME lanes execute (`if (lane < 6) T[..] = ..`) the IR-level passes may
-// still schedule the other lanes' later loads of those cells, on the not-taken path, ahead of the taken path's stores:
-// the readers then see the previous content (seen once on the terminal block of the learning problem: results changed
-// from process to process).  Release / acquire fences at WAVEFRONT scope around the barrier pin the order; at that scope
-// they emit no cache action and no wait.
-__device__ __forceinline__ void wave_fence() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-__device__ __forceinline__ void wave_sync() { wave_fence(); }
-
-// A value that is the same in every lane, moved to scalar registers (v_readfirstlane): the solver's
-// wave-wide scalars (mu, step lengths, sigma, ...) then cost no vector registers while they are carried
-// across the Riccati sweeps, and feed the VALU as scalar operands.
-__device__ __forceinline__ double uni(double x) {
-  return __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(x)), __builtin_amdgcn_readfirstlane(__double2loint(x)));
-}
-__device__ __forceinline__ float uni(float x) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(x))); }
-
-// Lane k's value of a wave-distributed number as a wave-uniform scalar (v_readlane_b32; the result lives in SGPRs
-// and feeds the FMAs as a scalar operand).
-__device__ __forceinline__ double lane_bcast(double v, int k) {
-  const int lo = __builtin_amdgcn_readlane(__double2loint(v), k);
-  const int hi = __builtin_amdgcn_readlane(__double2hiint(v), k);
-  return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ float lane_bcast(float v, int k) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), k)); }
-
-// ds_swizzle bit mode: source lane = (lane & 0x18) | K, i.e. lane K of each group of 8 (PATTERN = 0x18 | K << 5)
-template <int PATTERN>
-__device__ __forceinline__ double group_bcast(double v) {
-  return __hiloint2double(__builtin_amdgcn_ds_swizzle(__double2hiint(v), PATTERN), __builtin_amdgcn_ds_swizzle(__double2loint(v), PATTERN));
-}
-template <int PATTERN>
-__device__ __forceinline__ float group_bcast(float v) { return __int_as_float(__builtin_amdgcn_ds_swizzle(__float_as_int(v), PATTERN)); }
-
-// Wave reductions on the VALU (DPP), not through the LDS crossbar (ds_bpermute): the LDS pipeline is this kernel's
-// tightest resource and a 6-step bpermute chain costs ~460 cycles of latency against ~130 here.  Four row_ror steps
-// leave every lane of a 16-lane row with the row's total, row_bcast15 / row_bcast31 fold the rows into lane 63.
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ double dpp_move(double x, double identity) {
-  const int lo = __builtin_amdgcn_update_dpp(__double2loint(identity), __double2loint(x), CTRL, ROW_MASK, 0xf, false);
-  const int hi = __builtin_amdgcn_update_dpp(__double2hiint(identity), __double2hiint(x), CTRL, ROW_MASK, 0xf, false);
-  return __hiloint2double(hi, lo);
-}
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ float dpp_move(float x, float identity) {
-  return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(identity), __float_as_int(x), CTRL, ROW_MASK, 0xf, false));
-}
-#define DPP_ROW_ROR(n) (0x120 + (n))
-#define DPP_ROW_BCAST15 0x142
-#define DPP_ROW_BCAST31 0x143
-struct op_sum {
-  template <typename real> static __device__ __forceinline__ real id() { return real(0); }
-  template <typename real> static __device__ __forceinline__ real f(real a, real b) { return a + b; }
-};
-struct op_max {
-  template <typename real> static __device__ __forceinline__ real id() { return -real(INFINITY); }
-  template <typename real> static __device__ __forceinline__ real f(real a, real b) { return fmax(a, b); }
-};
-struct op_min {
-  template <typename real> static __device__ __forceinline__ real id() { return real(INFINITY); }
-  template <typename real> static __device__ __forceinline__ real f(real a, real b) { return fmin(a, b); }
-};
-// NV independent reductions in lock-step (their steps interleave); results as wave-uniform scalars
-template <class OP, int NV, typename real>
-__device__ __forceinline__ void wave_reduce_n(real (&v)[NV]) {
-  const real id = OP::template id<real>();
-#pragma unroll
-  for (int k = 0; k < NV; ++k) v[k] = OP::f(v[k], dpp_move<DPP_ROW_ROR(8), 0xf>(v[k], id));
-#pragma unroll
-  for (int k = 0; k < NV; ++k) v[k] = OP::f(v[k], dpp_move<DPP_ROW_ROR(4), 0xf>(v[k], id));
-#pragma unroll
-  for (int k = 0; k < NV; ++k) v[k] = OP::f(v[k], dpp_move<DPP_ROW_ROR(2), 0xf>(v[k], id));
-#pragma unroll
-  for (int k = 0; k < NV; ++k) v[k] = OP::f(v[k], dpp_move<DPP_ROW_ROR(1), 0xf>(v[k], id));
-#pragma unroll
-  for (int k = 0; k < NV; ++k) v[k] = OP::f(v[k], dpp_move<DPP_ROW_BCAST15, 0xa>(v[k], id));
-#pragma unroll
-  for (int k = 0; k < NV; ++k) v[k] = OP::f(v[k], dpp_move<DPP_ROW_BCAST31, 0xc>(v[k], id));
-#pragma unroll
-  for (int k = 0; k < NV; ++k) v[k] = lane_bcast(v[k], 63);
-}
-template <typename real>
-__device__ __forceinline__ real wave_sum(real x) {
-  real v[1] = {x};
-  wave_reduce_n<op_sum, 1>(v);
-  return v[0];
-}
-template <typename real>
-__device__ __forceinline__ real wave_max(real x) {
-  real v[1] = {x};
-  wave_reduce_n<op_max, 1>(v);
-  return v[0];
-}
-template <typename real>
-__device__ __forceinline__ real wave_min(real x) {
-  real v[1] = {x};
-  wave_reduce_n<op_min, 1>(v);
-  return v[0];
-}
-template <int NV, typename real>
-__device__ __forceinline__ void wave_sum_n(real (&v)[NV]) {
-  wave_reduce_n<op_sum, NV>(v);
-}
-
-// Exchange with the partner lane that differs in bit BIT of the lane number (and, for bits 2 and 3, in the bits below:
-// the row mirrors are the involutions DPP offers there) -- every pairing used by wave_sum_split below.
-template <int BIT>
-__device__ __forceinline__ double pair_exchange(double x) {
-  if constexpr (BIT == 5) return __shfl_xor(x, 32, 64);
-  if constexpr (BIT == 4)  // ds_swizzle, bit mode: and 0x1f, or 0, xor 0x10
-    return __hiloint2double(__builtin_amdgcn_ds_swizzle(__double2hiint(x), 0x401F), __builtin_amdgcn_ds_swizzle(__double2loint(x), 0x401F));
-  if constexpr (BIT == 3) return dpp_move<0x140, 0xf>(x, 0.0);  // row_mirror
-  if constexpr (BIT == 2) return dpp_move<0x141, 0xf>(x, 0.0);  // row_half_mirror
-  if constexpr (BIT == 1) return dpp_move<0x4E, 0xf>(x, 0.0);   // quad_perm [2,3,0,1]
-  return dpp_move<0xB1, 0xf>(x, 0.0);                            // quad_perm [1,0,3,2]
-}
-template <int BIT>
-__device__ __forceinline__ float pair_exchange(float x) { return (float)pair_exchange<BIT>((double)x); }
-
-// Many sums at once, for NV up to 32 (the safe-set block reduces 35 per iteration): instead of NV full reductions, each
-// step pairs the lanes across one bit of the lane number and SPLITS the values between the partners -- the lane with
-// the bit clear keeps the lower half (adding its partner's contributions), the other the upper half -- so the work
-// halves with every step: P/2 + P/4 + ... exchanges for P values instead of 6 P.  After log2 P steps lane l holds the
-// partial total of value l >> (6 - log2 P) over its group; plain pairwise sums over the remaining bits finish it.
-template <int NV, typename real>
-__device__ __forceinline__ void wave_sum_split(real (&v)[NV], int lane) {
-  constexpr int P = NV <= 2 ? 2 : NV <= 4 ? 4 : NV <= 8 ? 8 : NV <= 16 ? 16 : 32;
-  constexpr int LOGP = P == 2 ? 1 : P == 4 ? 2 : P == 8 ? 3 : P == 16 ? 4 : 5;
-  static_assert(NV <= 32, "wave_sum_split handles up to 32 values");
-  real a[P];
-#pragma unroll
-  for (int k = 0; k < P; ++k) a[k] = k < NV ? v[k] : real(0);
-  auto split = [&](auto bit_c, auto half_c) {
-    constexpr int BIT = decltype(bit_c)::value, H = decltype(half_c)::value;
-    const bool up = (lane >> BIT) & 1;
-#pragma unroll
-    for (int k = 0; k < H; ++k) {
-      const real keep = up ? a[k + H] : a[k];
-      const real send = up ? a[k] : a[k + H];
-      a[k] = keep + pair_exchange<BIT>(send);
-    }
-  };
-  auto fold = [&](auto bit_c) {
-    constexpr int BIT = decltype(bit_c)::value;
-    a[0] = a[0] + pair_exchange<BIT>(a[0]);
-  };
-  using std::integral_constant;
-  // bits 5, 4, 3, 2, 1 carry the splits while more than one value is left; the rest are plain sums
-  if constexpr (LOGP >= 1) split(integral_constant<int, 5>{}, integral_constant<int, P / 2>{}); else fold(integral_constant<int, 5>{});
-  if constexpr (LOGP >= 2) split(integral_constant<int, 4>{}, integral_constant<int, P / 4>{}); else fold(integral_constant<int, 4>{});
-  if constexpr (LOGP >= 3) split(integral_constant<int, 3>{}, integral_constant<int, (P / 8 > 0 ? P / 8 : 1)>{}); else fold(integral_constant<int, 3>{});
-  if constexpr (LOGP >= 4) split(integral_constant<int, 2>{}, integral_constant<int, (P / 16 > 0 ? P / 16 : 1)>{}); else fold(integral_constant<int, 2>{});
-  if constexpr (LOGP >= 5) split(integral_constant<int, 1>{}, integral_constant<int, 1>{}); else fold(integral_constant<int, 1>{});
-  fold(integral_constant<int, 0>{});
-#pragma unroll
-  for (int k = 0; k < NV; ++k) v[k] = lane_bcast(a[0], k << (6 - LOGP));
-}
-
-// 1/x: hardware v_rcp seed + one Newton step (full accuracy for normal x); replaces the ~12-instruction IEEE
-// division sequence in the per-row arithmetic.
-__device__ __forceinline__ double frcp(double x) {
-  double r = __builtin_amdgcn_rcp(x);
-  return __builtin_fma(__builtin_fma(-x, r, 1.0), r, r);
-}
-__device__ __forceinline__ float frcp(float x) {
-  float r = __builtin_amdgcn_rcpf(x);
-  return __builtin_fmaf(__builtin_fmaf(-x, r, 1.0f), r, r);
-}
-
-// 1/sqrt(x): hardware v_rsq seed + Newton steps y <- y + y (1 - x y^2)/2 (two in double: the seed carries ~26 bits);
-// the IEEE sqrt + division pair it replaces is ~70 dependent instructions, ten times per terminal factorisation.
-__device__ __forceinline__ double frsqrt(double x) {
-  double y = __builtin_amdgcn_rsq(x);
-  y = __builtin_fma(0.5 * y, __builtin_fma(-x * y, y, 1.0), y);
-  return __builtin_fma(0.5 * y, __builtin_fma(-x * y, y, 1.0), y);
-}
-__device__ __forceinline__ float frsqrt(float x) {
-  const float y = __builtin_amdgcn_rsqf(x);
-  return __builtin_fmaf(0.5f * y, __builtin_fmaf(-x * y, y, 1.0f), y);
-}
-
-__device__ __forceinline__ double rfma(double a, double b, double c) { return __builtin_fma(a, b, c); }
-__device__ __forceinline__ float rfma(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
-
-// Per-precision constants of the iteration.  fp32: the complementarity floor of a single-precision Riccati
-// recursion is ~1e-6 (weights lam/t ~ 1e5 already cancel four digits in P), rows are feasible to ~1e-4.
-template <typename real> struct ipm_limits;
-template <> struct ipm_limits<double> {
-  static __device__ __forceinline__ double tol(double cfg) { return cfg; }
-  static constexpr double rd_ok = 1e-9, rd_infeasible = 1e-6, tiny = 1e-300;
-  static constexpr double rd_distress = 1e-6;  // a rise of mu counts as distress only in the (nearly) feasible end game
-};
-template <> struct ipm_limits<float> {
-  static __device__ __forceinline__ float tol(double cfg) { return fmaxf((float)cfg, 2e-6f); }
-  static constexpr float rd_ok = 1e-4f, rd_infeasible = 1e-2f, tiny = 1e-30f;
-  static constexpr float rd_distress = 1e-4f;
-};
-// Active-set polish (what OSQP's polish = true is to the reference, racing_mpc.cpp:90-95; derivation and measurements in
-// oracle/c/lmpc_oracle.c, which runs the same rounds): rows with lam > t are HELD -- weight theta on them, none on the
-// others, one stabilised factorisation -- then `steps` multiplier steps on that factor (gradient y + theta * residual on
-// the held rows, full Newton step, y <- y + theta * (residual + the row's own increment)), a KKT test (held rows met to
-// `feas` with y >= -dual, the others satisfied to `feas`, the last step below step_tol in the reference's scaled units),
-// and up to `rounds` repairs of the held set.  Double precision
-// tries it once as soon as mu <= mu_early with rows feasible to rd_early -- about two iterations before the interior
-// point's own tolerance, and the stabilised factorisations of those iterations are the ones it saves -- and again at
-// convergence if refused; single precision polishes at its convergence (mu ~ 2e-6), where it turns "within sqrt(mu) of the
-// optimum" into "the optimum to the accuracy of an fp32 solve".
-// The acceptance test of the single-precision polish (-D overrides: the tail measurements behind profiles/r04_f32_acceptance.md).
-// Until round 4: rows to 1e-5, multipliers to -1e-3.  At the batch sizes one GPU runs, that let three answers of 65536 learning
-// problems through that the fp32 KKT test verified and the fp64 kernel contradicts: 2.4e-3 away with the regression on (a held
-// row's multiplier between -1e-3 and -3e-4), 1.2e-3 and 1.0e-3 without it (a multiplier at -7e-5; a row violated by 3.8e-6).
-// With rows to 3e-6 and multipliers to -3e-5 the worst of four 32768-batches is 9.0e-4 (one problem; every other below 2.5e-5)
-// and the worst IAC problem 8.5e-5; the fp64 pass gets 4 more problems of 32768 and the solve takes the same time.
-#ifndef LMPC_F32_POL_FEAS
-#define LMPC_F32_POL_FEAS 3e-6f
-#endif
-#ifndef LMPC_F32_POL_DUAL
-#define LMPC_F32_POL_DUAL 3e-5f
-#endif
-#ifndef LMPC_F32_POL_STEP_TOL
-#define LMPC_F32_POL_STEP_TOL 1e-4f
-#endif
-#ifndef LMPC_F32_POL_STEPS
-#define LMPC_F32_POL_STEPS 3
-#endif
-template <typename real> struct polish_limits;
-template <> struct polish_limits<double> {
-  static constexpr bool early = true;
-  // Round 5: up to FOUR multiplier steps (the loop stops after the second when that one moved the iterate by <= step_ok), a last
-  // step of at most 1e-6 (1e-5 until then) and four rounds (three).  A held set that a repair has extended -- the new rows start
-  // from a zero multiplier -- or two boundary rows coupled through sigma converge like 0.1 per step, not at once: the second
-  // step was still 1.5e-5 .. 1.7e-4, the attempt was refused, and what stood was the interior point's own answer, 9e-6 (tracking,
-  // N = 80) and 2e-5 (learning, N = 60) from the dense optimum; an attempt accepted at 1e-5 with that rate is itself 1e-6 off.
-  // Measured on the serial twin against the dense optimum over the bench distributions (scratch/r5/cmp_cache.py): worst 2e-7
-  // at every horizon, mean iterations -0.3 %, the slowest problem of the N = 20 batch 18 -> 14 iterations.
-  // Round 6: up to SIX steps.  The fused factorisation (riccati_factor<.., FUSE>) changes the last bits of every sweep, and one problem of
-  // tests/dispatch_sweep.py's 323 584 (BARC tracking, N = 51) fell on the other side of the limit: its exit attempt's steps go 2.1e-5,
-  // 5.9e-6, 1.9e-6, 2.2e-7 on the twin (accepted) and ended just above step_tol in the kernel -- refused, and the interior point's own
-  // iterate (mu 5e-12, a degenerate problem: 3.4e-6 from the twin in dU) stood with status OPTIMAL.  A consistent set whose steps are
-  // still CONVERGING is not a reason to give the optimum up: two more steps cost two sweeps on the few problems that need them (the
-  // loop leaves after any step <= step_ok) and nothing on the others.
-  // mu_early stays 1e-8.  1e-7 was measured in round 6 (scratch/r6/twin_mu_early.py on the twin, then on the GPU): mean iterations
-  // 8.92 -> 8.63 (BARC N = 20), 9.41 -> 9.17 (N = 40), 12.5 -> 12.2 (learning), every answer still 1e-9 from the dense optimum, the
-  // pipelined rate +1.3 % -- and the KERNEL slower: 0.813 -> 0.861 ms (N = 20), 2.35 -> 2.48 (N = 40), 8.11 -> 8.65 (N = 80) per 4096:
-  // more early attempts are refused, those problems pay the attempt and a second one, and a launch lasts as long as its slowest waves.
-  static constexpr double theta = 1e8, feas = 1e-9, dual = 1e-7, mu_early = 1e-8, rd_early = 1e-6, step_ok = 1e-7, step_tol = 1e-6;
-  // dual_l: the same test on the SIMPLEX rows' multipliers, a decade tighter (round 6).  The learning problem is LP-like along blends of
-  // nearly exchangeable safe-set points: a wrong vertex whose pinned weights have multipliers of -2e-8 .. -1e-7 passed at -1e-7 and sat
-  // 1.4e-3 from the dense optimum in X at an objective gap below 1e-9 (the twin, one problem of the 3.9 M of the large dispatch sweeps:
-  // N = 71, 160 points; at -1e-8 it is repaired to the optimum).  No problem of the learning fixtures has a multiplier in between: same
-  // iterations, same answers (scratch/r6/twin_mu_early.py with TWIN_MACRO=POLISH_DUAL_L).
-  static constexpr double dual_l = 1e-8;
-  static constexpr int rounds = 4, steps = 6;
-};
-template <> struct polish_limits<float> {
-  // theta: 1e7 needs the stabilised factor and the fp64 2x2 pivot; with 1e5 chains of held input rows (u_i = u_{i-1} + t v_i,
-  // stiffness R_d / t^2 per link) converge like 0.7 per step.  Up to three steps: the third removes what the rounding of the
-  // first two has left, and is only taken when the second still moved the iterate by more than step_ok (scaled units).
-  static constexpr bool early = false;  // (an early attempt at mu ~ 1e-4 was measured on the serial twin: the iterations it saves are fewer than the rounds it adds)
-  static constexpr float theta = 1e7f, feas = LMPC_F32_POL_FEAS, dual = LMPC_F32_POL_DUAL, mu_early = 0.0f, rd_early = 0.0f, step_ok = 3e-6f,
-                         step_tol = LMPC_F32_POL_STEP_TOL;
-  static constexpr float dual_l = LMPC_F32_POL_DUAL;  // (the simplex rows' multipliers: the rows' own limit in single precision)
-  static constexpr int rounds = 4, steps = LMPC_F32_POL_STEPS;
-};
-// 1 / scale of the quantity a slot constrains: the reference's scale vectors (racing_mpc.cpp:36-37, hard-coded there for every
-// vehicle) -- used only to measure a polish step
-__device__ __forceinline__ float slot_inv_scale(int sl) {
-  return sl == 0 ? 5e-4f : (sl == 1 || sl == 10) ? 0.1f : sl == 2 ? 10.0f : sl == 3 ? 0.0125f : (sl == 4 || sl == 5) ? 0.5f : (sl == 6 || sl == 8) ? 0.1f : (1.0f / 0.3f);
-}
-#define POLISH_THETA_L 1e8  // the simplex rows (always fp64)
-#define POLISH_STRONG 1e3   // a row with lam >= POLISH_STRONG t is one the interior point holds firmly
-#define POLISH_EXIT 256         // flag in PolishArgs::max_rounds: the attempt at the interior point's exit
-#ifndef POLISH_EXIT_GAMMA
-#define POLISH_EXIT_GAMMA 1e-2
-#endif
-// ... holds a row from lam > 1e-2 t on (early and warm attempts: lam > t)
-#define WARM_ROUNDS 2       // repairs a warm start may spend before the cold start takes over
-static_assert(polish_limits<double>::rounds == LMPC_WARM_ROUNDS_MAX, "lmpc_set_warm_rounds' upper limit is the polish's");
-#define WARM_ACT 1e-9       // a box row of the plan counts as active within this slack (a polished plan sits on its bounds to ~1e-16)
-#define WARM_ACT_EY 1e-3    // boundary rows: their bounds move with the shift (the track's half-width over one knot's travel)
-template <typename real> struct vec2;
-template <> struct vec2<double> { typedef double2 type; };
-template <> struct vec2<float> { typedef float2 type; };
-
-// Inverse of a symmetric positive definite 6x6 (row-major, full storage) by Cholesky; every index is
-// a compile-time constant after unrolling, so the factor lives in registers.  Executed redundantly by
-// all lanes on wave-uniform data.
-template <typename real>
-__device__ __forceinline__ void spd_inv6(const real (&F)[36], real (&Fi)[36]) {
-  real Lc[36];
-#pragma unroll
-  for (int j = 0; j < 6; ++j) {
-    real d = F[j * 6 + j];
-#pragma unroll
-    for (int k = 0; k < j; ++k) d -= Lc[j * 6 + k] * Lc[j * 6 + k];
-    d = sqrt(d);
-    const real id = 1.0 / d;
-    Lc[j * 6 + j] = id;  // store the reciprocal of the pivot
-#pragma unroll
-    for (int i = j + 1; i < 6; ++i) {
-      real t = F[i * 6 + j];
-#pragma unroll
-      for (int k = 0; k < j; ++k) t -= Lc[i * 6 + k] * Lc[j * 6 + k];
-      Lc[i * 6 + j] = t * id;
-    }
-  }
-#pragma unroll
-  for (int c = 0; c < 6; ++c) {
-    real y[6], x[6];
-#pragma unroll
-    for (int i = 0; i < 6; ++i) {
-      real t = (i == c) ? 1.0 : 0.0;
-#pragma unroll
-      for (int k = 0; k < i; ++k) t -= Lc[i * 6 + k] * y[k];
-      y[i] = t * Lc[i * 6 + i];
-    }
-#pragma unroll
-    for (int i = 5; i >= 0; --i) {
-      real t = y[i];
-#pragma unroll
-      for (int k = i + 1; k < 6; ++k) t -= Lc[k * 6 + i] * x[k];
-      x[i] = t * Lc[i * 6 + i];
-    }
-#pragma unroll
-    for (int i = 0; i < 6; ++i) Fi[i * 6 + c] = x[i];
-  }
-}
-
-// LMPC simplex row j: gradient of the (eps-eliminated) terminal cost wrt lambda_j including the row's
-// barrier coefficient, bl_j = ss_j - cf_j - u_j'E eps; also returns 1/theta_j.
-// (ee = E eps of this iteration, wave-uniform)
-template <typename real>
-__device__ __forceinline__ real simplex_bl(real lm, real t, real l, real pprod, real ssj, const real (&u)[6],
-                                             real smu, real pm, const real (&ee)[6], real& itf) {
-  const real it_ = frcp(t);
-  const real th = l * it_;
-  itf = frcp(th);
-  const real cf = th * (-lm + t) + (smu - pm * pprod) * it_;
-  real ue = 0.0;
-#pragma unroll
-  for (int k = 0; k < 6; ++k) ue += u[k] * ee[k];
-  return ssj - cf - ue;
-}
-
-// The same row in a polish round: barrier coefficient y + theta (-lambda_j) if the row lambda_j >= 0 is held (weight theta),
-// none if lambda_j is free (it is then one of the explicit unknowns: 1/theta is not used).
-template <typename real>
-__device__ __forceinline__ real simplex_bl_polish(real lm, real y, bool held, real ssj, const real (&u)[6], const real (&ee)[6],
-                                                    real& itf) {
-  itf = held ? real(1.0 / POLISH_THETA_L) : real(0);
-  const real cf = held ? y - real(POLISH_THETA_L) * lm : real(0);
-  real ue = 0.0;
-#pragma unroll
-  for (int k = 0; k < 6; ++k) ue += u[k] * ee[k];
-  return ssj - cf - ue;
-}
-
-// ---- terminal block: two-level elimination of the simplex weights (oracle/c/lmpc_oracle.c documents the derivation) ----
-// Points with theta >= tau (B) are eliminated through 1/theta and enter as wave sums (T_B, a_B, s_B); the few points
-// whose lambda stays positive have theta -> 0 and are kept as explicit unknowns (A, at most MA_MAX): nothing is ever
-// divided by a small theta, and cond(F_B) stays below ~1/TAU_REL.  Everything here is wave-uniform arithmetic on values
-// every lane holds; results go to the LDS tail (lane 0 writes), the per-right-hand-side solves read them back as
-// broadcast reads.  Unused explicit slots (a >= m) hold u = 0, theta = 1, so they drop out without a branch.
-// x <- C_A^-1 x.  Lane `la` (< MA_MAX) brings component la of x in `v` and holds row la of C_A^-1 in `ci`; every lane gets all
-// of the result.  (Until round 5 every lane carried the whole Cholesky factor and ran both substitutions itself: with six
-// explicit points that is 21 live values and two dependent chains of 21 operations per right-hand side.)
-template <typename real>
-__device__ __forceinline__ void cinv_apply(const real (&ci)[MA_MAX], real v, real (&x)[MA_MAX]) {
-  real s = 0.0;
-#pragma unroll
-  for (int b = 0; b < MA_MAX; ++b) s += ci[b] * lane_bcast(v, b);
-#pragma unroll
-  for (int a = 0; a < MA_MAX; ++a) x[a] = lane_bcast(s, a);
-}
-
-// F = E^-1 + T_B (full 6x6), a_B, s_B, m explicit points (their u, theta already in T[TL_UA], T[TL_THA]).
-// Writes F_B^-1, W_A, C_A^-1, x1, g, a_B, s11 and PT = F^-1 + g g'/s11 to the LDS tail.
-// The two Cholesky factors are wave-uniform arithmetic in registers (every lane holds the sums they start from); the
-// products in between run one OUTPUT per lane -- a column of F_B^-1 or C_A^-1, an element of W_A, C_A, Z, PT -- on operands
-// fetched from LDS in one batch per stage, results to LDS (each cell has one writer), a fence, next stage.  An earlier form
-// computed everything in every lane with lane 0 storing: ~300 dependent LDS round trips per call, 26 k cycles per
-// iteration at one wave per SIMD.
-template <typename real>
-__device__ __forceinline__ void term_factor_u(real* T, int lane, const real (&F)[36], const real (&aB)[6], real sB, int m) {
-  {  // F_B^-1 by Cholesky: lane c < 6 solves for column c
-    real Lf[36];
-#pragma unroll
-    for (int j = 0; j < 6; ++j) {
-      real d = F[j * 6 + j];
-#pragma unroll
-      for (int k = 0; k < j; ++k) d -= Lf[j * 6 + k] * Lf[j * 6 + k];
-      const real id = frsqrt(d);
-      Lf[j * 6 + j] = id;  // reciprocal pivot
-#pragma unroll
-      for (int i = j + 1; i < 6; ++i) {
-        real t = F[i * 6 + j];
-#pragma unroll
-        for (int k = 0; k < j; ++k) t -= Lf[i * 6 + k] * Lf[j * 6 + k];
-        Lf[i * 6 + j] = t * id;
-      }
-    }
-    const int c = lane < 6 ? lane : 0;
-    real y[6], x[6];
-#pragma unroll
-    for (int i = 0; i < 6; ++i) {
-      real t = (i == c) ? real(1) : real(0);
-#pragma unroll
-      for (int k = 0; k < i; ++k) t -= Lf[i * 6 + k] * y[k];
-      y[i] = t * Lf[i * 6 + i];
-    }
-#pragma unroll
-    for (int i = 5; i >= 0; --i) {
-      real t = y[i];
-#pragma unroll
-      for (int k = i + 1; k < 6; ++k) t -= Lf[k * 6 + i] * x[k];
-      x[i] = t * Lf[i * 6 + i];
-    }
-    if (lane < 6) {
-#pragma unroll
-      for (int i = 0; i < 6; ++i) T[TL_FB + i * 6 + lane] = x[i];
-    }
-    if (lane == 0) {
-#pragma unroll
-      for (int k = 0; k < 6; ++k) T[TL_AB + k] = aB[k];
-    }
-  }
-  wave_fence();
-  {  // W[a][r] = sum_c F_B^-1[r][c] u_a[c]: lane 6a + r
-    const int l = lane < 6 * MA_MAX ? lane : 0, a = (l * 43) >> 8, r = l - 6 * a;
-    real fb[6], ua[6];
-#pragma unroll
-    for (int c = 0; c < 6; ++c) {
-      fb[c] = T[TL_FB + r * 6 + c];
-      ua[c] = T[TL_UA + a * 6 + c];
-    }
-    real v = 0.0;
-#pragma unroll
-    for (int c = 0; c < 6; ++c) v += fb[c] * ua[c];
-    if (lane < 6 * MA_MAX) T[TL_WA + lane] = v;
-  }
-  wave_fence();
-  {  // C_A = Theta_A + U_A'W_A, staged through the cells of its inverse: lane 6a + b
-    static_assert(MA_MAX == 6, "lane mapping of C_A, stride of its cells");
-    const int l = lane < 36 ? lane : 0, a = (l * 43) >> 8, bq = l - 6 * a;
-    real ua[6], wb[6];
-#pragma unroll
-    for (int r = 0; r < 6; ++r) {
-      ua[r] = T[TL_UA + a * 6 + r];
-      wb[r] = T[TL_WA + bq * 6 + r];
-    }
-    real v = (a == bq) ? T[TL_THA + a] : real(0);
-#pragma unroll
-    for (int r = 0; r < 6; ++r) v += ua[r] * wb[r];
-    if (lane < 36) T[TL_LC + a * 6 + bq] = v;
-  }
-  wave_fence();
-  {  // C_A^-1 by Cholesky, like F_B^-1: the factor in registers (wave-uniform), lane c < MA_MAX solves for column c.  A jitter for
-     // identical points (the padding repeats the last point of the set: C_A is then singular as theta -> 0).  An unused slot
-     // (a >= m) has u = 0, theta = 1: its row and column of C_A are those of the identity, and so are its inverse's.
-    real Lc[36];
-    real jit = 0.0;
-#pragma unroll
-    for (int a = 0; a < MA_MAX; ++a) {
-#pragma unroll
-      for (int bq = 0; bq <= a; ++bq) Lc[a * 6 + bq] = T[TL_LC + a * 6 + bq];
-      jit += Lc[a * 6 + a];
-    }
-    jit *= real(sizeof(real) == 4 ? 1e-6 : 1e-13);
-#pragma unroll
-    for (int a = 0; a < MA_MAX; ++a) {
-#pragma unroll
-      for (int bq = 0; bq <= a; ++bq) {
-        real v = Lc[a * 6 + bq] + (a == bq ? jit : real(0));
-#pragma unroll
-        for (int k = 0; k < bq; ++k) v -= Lc[a * 6 + k] * Lc[bq * 6 + k];
-        Lc[a * 6 + bq] = (a == bq) ? frsqrt(v) : v * Lc[bq * 6 + bq];
-      }
-    }
-    const int c = lane < MA_MAX ? lane : 0;
-    real y[MA_MAX], x[MA_MAX];
-#pragma unroll
-    for (int i = 0; i < MA_MAX; ++i) {
-      real t = (i == c) ? real(1) : real(0);
-#pragma unroll
-      for (int k = 0; k < i; ++k) t -= Lc[i * 6 + k] * y[k];
-      y[i] = t * Lc[i * 6 + i];
-    }
-#pragma unroll
-    for (int i = MA_MAX - 1; i >= 0; --i) {
-      real t = y[i];
-#pragma unroll
-      for (int k = i + 1; k < MA_MAX; ++k) t -= Lc[k * 6 + i] * x[k];
-      x[i] = t * Lc[i * 6 + i];
-    }
-    wave_fence();  // (every lane has read C_A before its cells take the inverse)
-    if (lane < MA_MAX) {
-#pragma unroll
-      for (int i = 0; i < MA_MAX; ++i) T[TL_LC + i * 6 + lane] = x[i];
-    }
-  }
-  wave_fence();
-  // x1 = C_A^-1 (1_A - W_A'a_B), z1 = a_B + U_A x1, g = F_B^-1 z1, s11 = 1_A'x1 + s_B - a_B'g: a row per lane, the
-  // vectors from one product to the next through v_readlane
-  real s11 = sB;
-  {
-    const int la = lane < MA_MAX ? lane : 0, lr = lane < 6 ? lane : 0;
-    real wa[6], fb[6], ua[MA_MAX], ci[MA_MAX];
-#pragma unroll
-    for (int r = 0; r < 6; ++r) {
-      wa[r] = T[TL_WA + la * 6 + r];
-      fb[r] = T[TL_FB + lr * 6 + r];
-    }
-#pragma unroll
-    for (int a = 0; a < MA_MAX; ++a) {
-      ua[a] = T[TL_UA + a * 6 + lr];
-      ci[a] = T[TL_LC + la * 6 + a];
-    }
-    real x1[MA_MAX], g[6];
-    {
-      real v = la < m ? real(1) : real(0);
-#pragma unroll
-      for (int r = 0; r < 6; ++r) v -= wa[r] * aB[r];
-      cinv_apply(ci, v, x1);
-    }
-    real z1u[6];
-    {
-      real z = aB[0];
-#pragma unroll
-      for (int k = 1; k < 6; ++k) z = (lr == k) ? aB[k] : z;
-#pragma unroll
-      for (int a = 0; a < MA_MAX; ++a) {
-        z += ua[a] * x1[a];
-        s11 += a < m ? x1[a] : real(0);
-      }
-#pragma unroll
-      for (int c = 0; c < 6; ++c) z1u[c] = lane_bcast(z, c);
-    }
-    {
-      real v = 0.0;
-#pragma unroll
-      for (int c = 0; c < 6; ++c) v += fb[c] * z1u[c];
-#pragma unroll
-      for (int r = 0; r < 6; ++r) {
-        g[r] = lane_bcast(v, r);
-        s11 -= aB[r] * g[r];
-      }
-    }
-    if (lane == 0) {
-#pragma unroll
-      for (int k = 0; k < 6; ++k) T[TL_G + k] = g[k];
-#pragma unroll
-      for (int a = 0; a < MA_MAX; ++a) T[TL_X1 + a] = x1[a];
-      T[TL_S11] = s11;
-    }
-  }
-  {  // Z = C_A^-1 W_A': lane 6a + c
-    const int l = lane < 36 ? lane : 0, a = (l * 43) >> 8, c = l - 6 * a;
-    real v = 0.0;
-#pragma unroll
-    for (int bq = 0; bq < MA_MAX; ++bq) v += T[TL_LC + a * 6 + bq] * T[TL_WA + bq * 6 + c];
-    if (lane < 36) T[TL_Z + a * 6 + c] = v;
-  }
-  wave_fence();
-  {  // PT = F_B^-1 - W_A C_A^-1 W_A' + g g'/s11: lane 6r + c
-    const real is11 = frcp(s11);
-    const int l = lane < 36 ? lane : 0, r = (l * 43) >> 8, c = l - 6 * r;
-    real v = T[TL_FB + r * 6 + c] + T[TL_G + r] * T[TL_G + c] * is11;
-#pragma unroll
-    for (int a = 0; a < MA_MAX; ++a) v -= T[TL_WA + a * 6 + r] * T[TL_Z + a * 6 + c];
-    if (lane < 36) T[TL_PT + lane] = v;
-  }
-  wave_fence();
-}
-
-// One right-hand side: beta = U_B Th_B^-1 r_B, sig = 1'Th_B^-1 r_B (wave sums over B), r_A in T[TL_RA], simplex
-// residual r1.  Returns h = E U dlambda and nu; writes the explicit points' step to T[TL_XA] (lane 0).
-// The operands (rows of W_A, U_A, F_B^-1, C_A^-1, a_B, g) do not depend on the right-hand side: every lane
-// fetches the row it works on in ONE batch of LDS reads, the four short products run one output per lane, and what the
-// next product needs of the previous one travels through v_readlane (scalar registers), not through LDS -- at one wave
-// per SIMD every dependent LDS round trip is ~100 idle cycles, and the all-lanes-compute-everything form of this
-// routine had ~100 of them.
-template <typename real>
-__device__ __forceinline__ void term_solve_u(real* T, int lane, int m, const real (&beta)[6], real sig, real r1, real (&h)[6],
-                                             real& nu) {
-  const int la = lane < MA_MAX ? lane : 0, lr = lane < 6 ? lane : 0;
-  real wa[6], fb[6], ua[MA_MAX], ci[MA_MAX], ab[6], gg[6], x1[MA_MAX];
-#pragma unroll
-  for (int r = 0; r < 6; ++r) {
-    wa[r] = T[TL_WA + la * 6 + r];
-    fb[r] = T[TL_FB + lr * 6 + r];
-    ab[r] = T[TL_AB + r];
-    gg[r] = T[TL_G + r];
-  }
-  const real ra = T[TL_RA + la], s11 = T[TL_S11];
-#pragma unroll
-  for (int a = 0; a < MA_MAX; ++a) {
-    ua[a] = T[TL_UA + a * 6 + lr];
-    x1[a] = T[TL_X1 + a];
-    ci[a] = T[TL_LC + la * 6 + a];
-  }
-  real xa[MA_MAX];
-  {
-    real v = ra;
-#pragma unroll
-    for (int r = 0; r < 6; ++r) v -= wa[r] * beta[r];
-    cinv_apply(ci, v, xa);
-  }
-  real num = sig - r1;
-  real zu[6];
-  {
-    real z = beta[0];
-#pragma unroll
-    for (int k = 1; k < 6; ++k) z = (lr == k) ? beta[k] : z;
-#pragma unroll
-    for (int a = 0; a < MA_MAX; ++a) {
-      z += ua[a] * xa[a];
-      num += a < m ? xa[a] : real(0);
-    }
-#pragma unroll
-    for (int c = 0; c < 6; ++c) zu[c] = lane_bcast(z, c);
-  }
-  {
-    real v = 0.0;
-#pragma unroll
-    for (int c = 0; c < 6; ++c) v += fb[c] * zu[c];
-#pragma unroll
-    for (int r = 0; r < 6; ++r) {
-      h[r] = lane_bcast(v, r);
-      num -= ab[r] * h[r];
-    }
-  }
-  nu = num * frcp(s11);
-#pragma unroll
-  for (int r = 0; r < 6; ++r) h[r] = h[r] - nu * gg[r];
-  if (lane == 0) {
-#pragma unroll
-    for (int a = 0; a < MA_MAX; ++a) T[TL_XA + a] = xa[a] - nu * x1[a];
-  }
-  wave_fence();
-}
-
-// Register-resident state of the LMPC simplex rows lambda_j >= 0 (KS safe-set points per lane); empty for
-// the tracking kernel so that it costs it nothing.
-template <typename real, int KS>
-struct SimplexRows {
-  bool on[KS];
-  int aidx[KS];  // slot of the point among the explicit ones of this iteration, -1: eliminated through 1/theta
-  real lm[KS], t[KS], l[KS], p[KS], j[KS], dl[KS];
-  real sv[KS];  // lambda at the start of a polish (restored when it is refused)
-  const real* ul;  // the (centred) points in LDS, point-major: component k of point j at ul[6 j + k], S points -- read-only
-                   // after the load, 36 registers (KS = 3) the iteration's row state needs more.  A point is 48 bytes = three
-                   // 16-byte reads; 16 consecutive lanes at a 48-byte stride cover all 64 banks once, so the reads are
-                   // conflict-free.  A lane slot past S reads the zero point stored behind the last one (uz[q] = its index).
-  int uz[KS];      // 6 * (index of the point this lane's slot q reads)
-  __device__ __forceinline__ void load_u(int q, int lane, real (&u)[6]) const {
-    const real* p = ul + uz[q];
-#pragma unroll
-    for (int k = 0; k < 6; ++k) u[k] = p[k];
-  }
-  real ss0[6];
-  real r1;   // 1 - 1'lambda
-  real tau;  // theta below which a point is kept explicit
-  int m;     // explicit points of this iteration
-};
-template <typename real>
-struct SimplexRows<real, 0> {};
-
-template <typename real>
-struct Lds {
-  real* base;
-  int N;
-  int stride;  // of a stage record: LMPC_STAGE_STRIDE, or LMPC_LEAN_STAGE_STRIDE in the lean layout (below)
-  bool fresh;  // FRESH_LANE in the sweeps of this instantiation (a compile-time constant where the sweeps are inlined)
-  bool chain_prio;  // CHAIN_PRIO around the serial stage chains (likewise)
-  __device__ __forceinline__ real* st(int i) const { return base + i * stride; }
-  __device__ __forceinline__ real* kn(int i) const { return base + (N - 1) * stride + i * LMPC_KNOT_STRIDE; }
-  __device__ __forceinline__ real* tail() const { return base + (N - 1) * stride + N * LMPC_KNOT_STRIDE; }
-};
+#include "lmpc_solve_layout.hip.h"   // LDS layout, Lds / SimplexRows, per-instantiation policies
+#include "lmpc_wave.hip.h"           // fences, broadcasts, reductions, scheduling pins
+#include "lmpc_limits.hip.h"         // ipm_limits, polish_limits
+#include "lmpc_terminal.hip.h"       // safe-set terminal block
 
 // ---- the LEAN layout (fp64, N > 40) -----------------------------------------------------------------------------------
 // At long horizons the stage records are what limits residency: 78 doubles per stage, 48 of them the stage model [A B],
@@ -843,16 +55,14 @@ struct Lds {
 // and a chunk slot holds the workspace record as it is: ABt[8][6] (row c of it = column c of [A B]: the rows the backward
 // sweeps read are contiguous 48-byte runs on distinct banks, the columns the forward sweep reads are stride-6) | g [6].
 // N = 60: 57 KB -> 38 KB per problem, 2 -> 4 resident problems per CU (the register file allows no more); N = 80: 2 -> 3.
-#define LN_CHUNK 8
+#define LN_CHUNK LMPC_LEAN_CHUNK  // (lmpc_device.h: the host sizes the two chunk buffers with the same constants)
 #define LN_REC LMPC_LIN_RECORD
 #define LN_HI 16
 #define LN_HI11 18
 #define LN_DT 19
 #define LN_KFF(s) ((s) ? 22 : 20)
-#ifndef LMPC_LEAN_MIN_KQ  // (A/B switch: 99 builds every kernel on the fat layout; lmpc_device.h's lmpc_is_lean follows it)
-#define LMPC_LEAN_MIN_KQ 11
-#endif
-constexpr bool lmpc_lean(int real_bytes, int kq) { return real_bytes == 8 && kq >= LMPC_LEAN_MIN_KQ; }
+// Which kernels take it: lmpc_lean (lmpc_solve_layout.hip.h), the fp64 kernels from LMPC_LEAN_MIN_KQ = 11 slots per lane on.
+
 template <typename real>
 struct ModelStream {
   const real* ws;  // this problem's [N - 1][LN_REC] in the workspace (HBM / L2)
@@ -918,59 +128,6 @@ __device__ __forceinline__ real qz_entry(const real* ct, bool terminal, int r, i
   return (r < 6 || c < 6) ? ((r == c) ? dx : 0.0) : uu;
 }
 
-// Pin the issue order of LDS traffic: one wave's DS instructions return in issue order, so the read a
-// serial chain waits for must be queued ahead of the operand prefetch of the following stage.
-#define ISSUE_ORDER() __builtin_amdgcn_sched_barrier(0)
-// The serial stage chains (factorisation, sweeps) at a higher issue priority than the row phases of the wave they share a SIMD
-// with (s_setprio): the chain's next instruction is the one a solve waits for, the row phases are throughput work that fills in.
-// Two-waves-per-SIMD kernels only (alone on its SIMD a wave has nobody to yield to: +0.5 %): headline kernel -1.5 %, pipelined
-// +1.4 %, one batch at a time -1.9 %, the mixed learning kernel -1.1 %; same bits (profiles/r04_row_phases.md).
-#define LMPC_CHAIN_PRIO 3
-// (the learning problem's terminal elimination is another serial chain; raising its priority the same way was measured in round 4 and
-//  bought nothing: profiles/r04_row_phases.md)
-#define CHAIN_PRIO_ENTER() do { if (LMPC_CHAIN_PRIO && L.chain_prio) __builtin_amdgcn_s_setprio(LMPC_CHAIN_PRIO); } while (0)
-#define CHAIN_PRIO_LEAVE() do { if (LMPC_CHAIN_PRIO && L.chain_prio) __builtin_amdgcn_s_setprio(0); } while (0)
-// ... and the other way round: value x is complete before any later memory operation is issued (an
-// empty asm that consumes x and clobbers memory), used to keep a prefetch behind the last use of the
-// registers it overwrites.
-#define AFTER_VALUE(x) asm volatile("" : "+v"(x) : : "memory")
-// The lane number as a value the optimiser cannot see through: everything a sweep derives from it (row / column indices,
-// LDS addresses, 0/1 multipliers, predicates) is then computed where the sweep starts -- a dozen VALU instructions -- instead
-// of once at the top of the kernel and kept alive over the whole iteration, which at the register limit means spilled and
-// reloaded from scratch (or from VGPR lanes, for the predicates) inside the sweep's preamble, one wait per reload.  Per
-// instantiation (Lds::fresh, lmpc_fresh_lane below): what it does to the register allocation of a 3000-line kernel is not
-// monotone, and it is kept only where it was measured to pay.  (`site` numbers the sweep functions: round 4 bisected a miscompute
-// with a per-site mask, profiles/r04_d70_bisect.md.)
-#define FRESH_LANE(l, site) do { if (L.fresh) asm volatile("" : "+v"(l)); } while (0)
-
-// Lane K of every 16-lane row to the whole row (DPP row_newbcast, gfx90a+; v_mov_b64_dpp for doubles): a register-to-
-// register broadcast.  bound_ctrl:1 with full row / bank masks tells the compiler that the tied "old" operand is never
-// read, so it is not materialised (with bound_ctrl:0 every broadcast costs a v_mov of a constant first -- a fifth of the
-// sweeps' VALU instructions).  (An inline-asm form of the same instructions measured the same speed and was NOT safe: in
-// the most register-starved instantiation, KQ = 14 with KS = 3, it gave wrong and run-to-run different results that wider
-// wait states did not cure, while this builtin form is bitwise reproducible there -- the compiler has to see DPP.)
-template <int K>
-__device__ __forceinline__ double row_bcast(double v) { return __builtin_amdgcn_update_dpp(0.0, v, 0x150 + K, 0xf, 0xf, true); }
-template <int K>
-__device__ __forceinline__ float row_bcast(float v) {
-  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x150 + K, 0xf, 0xf, true));
-}
-template <typename real>
-__device__ __forceinline__ void row_bcast6(real v, real (&o)[6]) {
-  o[0] = row_bcast<0>(v); o[1] = row_bcast<1>(v); o[2] = row_bcast<2>(v);
-  o[3] = row_bcast<3>(v); o[4] = row_bcast<4>(v); o[5] = row_bcast<5>(v);
-}
-template <typename real>
-__device__ __forceinline__ void row_bcast8(real v, real (&o)[8]) {
-  o[0] = row_bcast<0>(v); o[1] = row_bcast<1>(v); o[2] = row_bcast<2>(v); o[3] = row_bcast<3>(v);
-  o[4] = row_bcast<4>(v); o[5] = row_bcast<5>(v); o[6] = row_bcast<6>(v); o[7] = row_bcast<7>(v);
-}
-template <typename real>
-__device__ __forceinline__ void row_bcast67(real v, real& a, real& b) {  // lanes 6 and 7
-  a = row_bcast<6>(v);
-  b = row_bcast<7>(v);
-}
-
 // Backward Riccati sweep for the barrier weights currently in the knots' rhs0 region
 // (Thz @ +10..17, Thv @ +18,19, boundary weight @ KN_EY).  Leaves K (columns 6,7 of M) and Hinv in
 // the stage records.
@@ -1000,7 +157,7 @@ __device__ __forceinline__ void row_bcast67(real v, real& a, real& b) {  // lane
 #define KN_TEY 35  // (the knot record's spare cell)
 template <bool HAS_PT, bool JOSEPH, bool FUSE = false, typename real, typename ptreal>
 __device__ __forceinline__ void riccati_factor(const Lds<real>& L, int lane, const ptreal* PT, const int th_off = KN_R0, const int tey_off = KN_EY) {
-  FRESH_LANE(lane, 0);
+  FRESH_LANE(lane);
   CHAIN_PRIO_ENTER();
   const int N = L.N, r = lane >> 3, c = lane & 7;
   real* T = L.tail();
@@ -1233,7 +390,7 @@ __device__ __forceinline__ void riccati_factor(const Lds<real>& L, int lane, con
 // results a stage leaves behind (kff, dz, dv) are stored off the chain.
 template <int NRHS, bool FWD_ONLY = false, typename real>  // (FWD_ONLY: the backward half ran inside the factorisation, riccati_factor<.., FUSE>)
 __device__ __forceinline__ void riccati_solve(const Lds<real>& L, int lane, Prof& pf) {
-  FRESH_LANE(lane, 2);
+  FRESH_LANE(lane);
   CHAIN_PRIO_ENTER();
   const int N = L.N;
   const int r = lane & 7, s = (lane >> 4) & (NRHS - 1);
@@ -1331,7 +488,7 @@ __device__ __forceinline__ void riccati_solve(const Lds<real>& L, int lane, Prof
 // there and the first gradient): the plan made dynamically exact about this linearisation, a few 1e-3 from where it was.
 template <bool WARM = false, typename real>
 __device__ __forceinline__ void feedback_rollout(const Lds<real>& L, int lane) {
-  FRESH_LANE(lane, 4);
+  FRESH_LANE(lane);
   const int N = L.N, r = lane & 7;
   const bool own = lane < 8;
   real* T = L.tail();
@@ -1378,7 +535,7 @@ __device__ __forceinline__ void feedback_rollout(const Lds<real>& L, int lane) {
 template <bool HAS_PT, bool JOSEPH, bool FUSE = false, typename real, typename ptreal>
 __device__ __forceinline__ void riccati_factor_lean(const Lds<real>& L, ModelStream<real>& M, int lane, const ptreal* PT, const int th_off = KN_R0,
                                                     const int tey_off = KN_EY) {
-  FRESH_LANE(lane, 1);
+  FRESH_LANE(lane);
   const int N = L.N, r = lane >> 3, c = lane & 7;
   real* T = L.tail();
   real* MP = T + TL_P;
@@ -1599,7 +756,7 @@ __device__ __forceinline__ void riccati_factor_lean(const Lds<real>& L, ModelStr
 // bit for bit the same results, is scratch/r5/experiment_switches.patch); lane (s, r) = ((lane >> 4) % NRHS, lane & 7), lanes 8..15 of a row mirror 0..7.
 template <int NRHS, bool FWD_ONLY = false, typename real>
 __device__ __forceinline__ void riccati_solve_lean_dpp(const Lds<real>& L, ModelStream<real>& M, int lane, Prof& pf) {
-  FRESH_LANE(lane, 5);
+  FRESH_LANE(lane);
   const int N = L.N;
   const int r = lane & 7, s = (lane >> 4) & (NRHS - 1);
   const bool own = (lane & 8) == 0 && lane < 16 * NRHS;
@@ -1709,7 +866,7 @@ __device__ __forceinline__ void riccati_solve_lean_dpp(const Lds<real>& L, Model
 
 template <bool WARM = false, typename real>
 __device__ __forceinline__ void feedback_rollout_lean(const Lds<real>& L, ModelStream<real>& M, int lane) {
-  FRESH_LANE(lane, 6);
+  FRESH_LANE(lane);
   const int N = L.N, r = lane & 7;
   const bool own = lane < 8;
   real* T = L.tail();
@@ -1757,8 +914,8 @@ __device__ __forceinline__ void feedback_rollout_lean(const Lds<real>& L, ModelS
   }
 }
 
-// ======== the active-set polish (polish_limits above; the twin's polish() runs the same rounds) ========
-// A CALL, not part of the interior point's body (round 4; until then a lambda inlined into the solve): the polish keeps
+// ======== the active-set polish (polish_limits, lmpc_limits.hip.h; the twin's polish() runs the same rounds) ========
+// A CALL in the fp64 kernels (lmpc_polish_is_call, lmpc_solve_layout.hip.h), not part of the interior point's body (round 4; until then a lambda inlined into the solve): the polish keeps
 // ~190 B more state per lane alive than an iteration does, and inlined -- even in an outer loop of its own -- it weighed on
 // the register allocation of the iteration: 292 B of scratch per lane in the N = 20 fp64 kernel (824 B in the mixed learning
 // kernel), 88 of the 116 scratch reloads of an iteration, +10 % per iteration.  Behind a call boundary the two are allocated
@@ -1792,37 +949,6 @@ struct PolishResult {
   real sigma, mu, rdmax, last_step;
   double lm[KS > 0 ? KS : 1];  // the simplex weights of an accepted polish
 };
-__device__ __forceinline__ int uni(int x) { return __builtin_amdgcn_readfirstlane(x); }
-template <typename T>
-__device__ __forceinline__ T* uni_ptr(T* p) {
-  const unsigned long long v = reinterpret_cast<unsigned long long>(p);
-  const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)v);
-  const unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(v >> 32));
-  return reinterpret_cast<T*>(((unsigned long long)hi << 32) | lo);
-}
-
-// Where the polish is a call, and where the sweeps take a fresh lane value (FRESH_LANE above) -- measured per instantiation in
-// round 4 (profiles/r04_polish_forms.md: {inline, call} x {fresh, not}, every (KQ, KS), checksums against the round-3 build):
-//   * fp64, one wave per SIMD (KQ >= 7 or the learning problem: the instantiations that live in VGPRs + AGPRs): a CALL.  The call
-//     form computes bit for bit what the round-3 kernel computed, at every horizon and for both problems; the inlined function
-//     does not: with FRESH_LANE in the factorisation AND the vector solve the <double, 7, 0> instance (N = 24 .. 40) returns
-//     different -- wrong -- answers (72 of 8192 IAC problems "infeasible"), the same wrong answers whatever the post-RA schedule
-//     or the wait counts, and the right ones again with SGPR spills sent to memory instead of VGPR lanes, or at -O2 (DESIGN.md
-//     section 4, "the register-starved instantiations").  The call costs the callee's prologue / epilogue and the spills around
-//     the call site, ~1 KB of scratch traffic per lane and call, and buys -5 .. -16 % of the kernel time from N = 60 on and for
-//     the learning problem from N = 40 on (nothing either way at N = 40 tracking).
-//   * fp64, two waves per SIMD (tracking up to N = 23: the headline): INLINED.  Same time as the call form (0.872 against 0.868 ms
-//     per 4096 at N = 20), bit for bit the round-3 answers, and 102 MB of HBM traffic per launch against 250 MB (round 3: 174 MB):
-//     at 256 VGPRs there are no AGPR copies for a call boundary to save, and the call's own spills are the larger traffic.
-//   * fp32 (single precision and the fp32 pass of the mixed entry): INLINED -- the call form is 10 % slower on the mixed learning
-//     kernel and changes single-precision roundings enough to lose four solves of 4096 at N = 80.
-//   * FRESH_LANE everywhere.
-// (The A/B switches behind these measurements -- never / always a call, never / always fresh -- went to scratch/r5/experiment_switches.patch.)
-#ifndef LMPC_POLISH_CALL_2W  // (A/B switch: 1 puts the polish behind a call in the two-waves-per-SIMD fp64 kernels too)
-#define LMPC_POLISH_CALL_2W 1
-#endif
-constexpr bool lmpc_polish_is_call(int real_bytes, int kq, int ks) { return real_bytes == 8 && (LMPC_POLISH_CALL_2W || lmpc_waves_per_simd(real_bytes, kq, ks) < 2); }
-constexpr bool lmpc_fresh_lane(int real_bytes, int kq, int ks) { return true; }
 
 template <typename real, int KQ, int KS, typename io, bool SECOND = false>  // (SECOND: see lmpc_solve_problem)
 __device__ __forceinline__ PolishResult<real, KS> lmpc_polish(const PolishArgs<real, KQ, KS>& a) {
@@ -1834,8 +960,7 @@ __device__ __forceinline__ PolishResult<real, KS> lmpc_polish(const PolishArgs<r
   const int lane = threadIdx.x;
   const int N = uni(a.N), NS = N - 1;
   constexpr bool LEAN = lmpc_lean(sizeof(real), KQ);
-  Lds<real> L{lds, N, LEAN ? LMPC_LEAN_STAGE_STRIDE : LMPC_STAGE_STRIDE, lmpc_fresh_lane(sizeof(real), KQ, KS),
-              !SECOND && lmpc_waves_per_simd(sizeof(real), KQ, KS) >= 2};
+  Lds<real> L{lds, N, LEAN ? LMPC_LEAN_STAGE_STRIDE : LMPC_STAGE_STRIDE, !SECOND && lmpc_waves_per_simd(sizeof(real), KQ, KS) >= 2};
   real* const T = L.tail();
   treal* const TT = reinterpret_cast<treal*>(T + LMPC_TAIL_DOUBLES);
   ModelStream<real> MS{nullptr, nullptr, NS, lane, uni(a.have0), uni(a.have1)};
@@ -2389,46 +1514,6 @@ __device__ __attribute__((noinline)) PolishResult<real, KS> lmpc_polish_call(con
 // precision, <float, float> the single-precision path, <float, double> the mixed path (fp64 linearisation, regression,
 // safe-set centring and results around an fp32 interior-point iteration).
 // One problem, solved by the calling wavefront in the LDS block it is given (the body of both kernels below).
-// Row-phase policies, per instantiation by measurement (profiles/r04_row_phases.md):
-//   slots per chunk -- the long-horizon fp64 tracking kernels take their 11 / 14 slots half at a time (load, compute, store);
-//   opaque slot tables (SlotRef below) -- the long-horizon fp64 kernels and every learning kernel.
-// (fp32 at KQ >= 11 has no spills to begin with and loses 2-3 % to either; KQ <= 7 tracking loses 1-3 % to the opaque tables;
-//  the learning kernels at KQ >= 11 lose 15 % to the chunks.)
-// (bit mask of the four flag-select address sites recomputed per use in the fp64 tracking kernels with KQ <= 4: all four, -1.6..2.2 %
-//  at N = 20, bit-identical; +1 % at KQ = 7 and in fp32, which keep the hoisted form: profiles/r04_row_phases.md)
-__host__ __device__ constexpr int lmpc_row_chunk(int real_bytes, int kq, int ks) {
-  return (real_bytes == 8 && kq >= 11 && ks == 0) ? (kq + 1) / 2 : kq;
-}
-__host__ __device__ constexpr bool lmpc_opaque_slots(int real_bytes, int kq, int ks) { return (real_bytes == 8 && kq >= 11) || ks > 0; }
-__host__ __device__ constexpr int lmpc_opaque_sites(int real_bytes, int kq, int ks) { return (real_bytes == 8 && kq <= 4 && ks == 0) ? 15 : 0; }
-// the predictor's backward sweep fused into the factorisation (riccati_factor<.., FUSE>): per instantiation, by measurement
-// (MI355X, 4096 problems, kernel ms five chains -> four; profiles/r06_fuse_ab.txt):
-//   fp64 tracking  N = 20 0.859 -> 0.835, N = 24 1.639 -> 1.565, N = 40 2.461 -> 2.351, N = 60 5.368 -> 4.957, IAC N = 40 4.322 -> 4.052
-//   fp64 learning  N = 20 / 160 points 2.072 -> 2.028 (on); N = 40 5.52 -> 5.81, N = 60 14.54 -> 14.21 (off: KQ >= 7 with KS > 0 is the most register-starved family)
-//   fp32 / mixed   IAC N = 40 3.275 -> 3.203 / 6.091 -> 5.850 (on); learning N = 20 mixed 3.385 -> 3.239, but OFF: which ill-conditioned blends
-//                  of safe-set points pass the fp32 KKT test 1e-3 .. 5e-3 from the fp64 answer is decided by the last bits of the fp32
-//                  sweeps -- 3 of configs[4]'s 32768 before, 5 fused (tests/test_gpu_spec_workload.py holds the 99.99 % quantile to 1e-3);
-//                  tracking N <= 23 (KQ <= 4, three waves per SIMD): OFF -- the <float, 4, 0, double> instance of the fused build
-//                  took a memory access fault in the mixed entry (the polish's flat store of the iterate to the save area with a
-//                  clobbered address register; the fp32-array instance of the same source is fine): another of the
-//                  compiler-sensitive corners of DESIGN.md section 4, found by tests/dispatch_sweep.py on its first run.
-//   fp64 tracking N <= 23 (KQ <= 4, two waves per SIMD; the headline): ON, WITH THE POLISH BEHIND A CALL (LMPC_POLISH_CALL_2W).  Fused with the
-//                  polish inlined it gained 2.7 % and passed every test -- until an unrelated edit of the polish (a multiplier in its
-//                  classification) changed the register allocation: <double, 4, 0, double> then left the iteration after its first pass
-//                  (status MAX_ITER, 0 iterations; the loop's control variables read back correct; the same source with a printf, or with
-//                  one more integer assigned before each break, is correct: CHANGELOG.md, round 6).  Behind a call the polish's live state
-//                  (the spill source of this kernel since round 3) is out of the iteration's register allocation -- the form every
-//                  one-wave kernel has always had, all of them fused without incident: 0.819 -> 0.794 ms per 4096, every GPU test green
-//                  (the call form alone, unfused: 0.817).
-#ifndef LMPC_FUSE_MASK
-#define LMPC_FUSE_MASK 0x57
-#endif
-__host__ __device__ constexpr bool lmpc_fuse_bwd(int real_bytes, int kq, int ks) {
-  // bit 0: fp64 tracking KQ <= 4 (two waves per SIMD), 1: fp64 tracking KQ = 7, 2: fp64 tracking lean (KQ >= 11), 3: fp64 learning KQ >= 7,
-  // 4: fp32 / mixed tracking KQ >= 7, 5: fp32 / mixed tracking KQ <= 4, 6: fp64 learning KQ <= 4, 7: fp32 / mixed learning
-  return real_bytes == 8 ? (ks == 0 ? (kq <= 4 ? (LMPC_FUSE_MASK & 1) : (kq <= 7 ? (LMPC_FUSE_MASK & 2) : (LMPC_FUSE_MASK & 4))) : (kq <= 4 ? (LMPC_FUSE_MASK & 64) : (LMPC_FUSE_MASK & 8))) != 0
-                         : (ks == 0 ? (kq <= 4 ? (LMPC_FUSE_MASK & 32) : (LMPC_FUSE_MASK & 16)) : (LMPC_FUSE_MASK & 128)) != 0;
-}
 
 // SECOND: the fp64 second pass of a mixed solve -- a handful of problems a whole batch waits for, sharing the chip with the next batch's
 // first pass: its waves run at the top issue priority throughout (and do not drop it between chains).
@@ -2462,8 +1547,7 @@ __device__ __forceinline__ void lmpc_solve_problem(
   //  trusted with the polish behind a call, lmpc_fuse_bwd's comment, and the warm kernels keep theirs inline)
   constexpr bool FUSEK = lmpc_fuse_bwd(sizeof(real), KQ, KS) && !(WARMK && lmpc_waves_per_simd(sizeof(real), KQ, KS) >= 2);
   const bool fuse = FUSEK && P.has_sigma != 0;
-  Lds<real> L{lds, N, LEAN ? LMPC_LEAN_STAGE_STRIDE : LMPC_STAGE_STRIDE, lmpc_fresh_lane(sizeof(real), KQ, KS),
-              !SECOND && lmpc_waves_per_simd(sizeof(real), KQ, KS) >= 2};
+  Lds<real> L{lds, N, LEAN ? LMPC_LEAN_STAGE_STRIDE : LMPC_STAGE_STRIDE, !SECOND && lmpc_waves_per_simd(sizeof(real), KQ, KS) >= 2};
   if constexpr (SECOND && LMPC_CHAIN_PRIO) __builtin_amdgcn_s_setprio(3);
   real* T = L.tail();
   real* ct = T + TL_CT;
@@ -3885,10 +2969,11 @@ __global__ __launch_bounds__(64, lmpc_waves_per_simd(8, KQ, KS)) void lmpc_solve
   __global__ void lmpc_solve_kernel_w2<KQ>(lmpc_params, int, const double*, const double*, const double*, const double*, \
                                            const double*, const double*, const double*, double*, double*, double*, int*, int*, double*);
 
-#define LMPC_INSTANTIATE(REAL, KQ, KS, IO)                                                                              \
-  template __global__ void lmpc_solve_kernel<REAL, KQ, KS, IO>(lmpc_params, int, const IO*, const IO*, const IO*,        \
-                                                                const IO*, const IO*, const IO*, const IO*, const IO*,    \
-                                                                const IO*, IO*, IO*, IO*, IO*, int*, int*, IO*);
+#define LMPC_SOLVE_SIGNATURE(REAL, KQ, KS, IO)                                                                           \
+  __global__ void lmpc_solve_kernel<REAL, KQ, KS, IO>(lmpc_params, int, const IO*, const IO*, const IO*, const IO*, const IO*, \
+                                                       const IO*, const IO*, const IO*, const IO*, IO*, IO*, IO*, IO*, int*, int*, IO*);
+#define LMPC_INSTANTIATE(REAL, KQ, KS, IO) template LMPC_SOLVE_SIGNATURE(REAL, KQ, KS, IO)
+#define LMPC_INSTANTIATED_ELSEWHERE(REAL, KQ, KS, IO) extern template LMPC_SOLVE_SIGNATURE(REAL, KQ, KS, IO)
 #ifdef LMPC_SINGLE_INSTANCE  // (ISA inspection: hipcc -S -DLMPC_SINGLE_INSTANCE="double, 4, 3, double")
 #define LMPC_INSTANTIATE_X(...) LMPC_INSTANTIATE(__VA_ARGS__)
 LMPC_INSTANTIATE_X(LMPC_SINGLE_INSTANCE)
@@ -3948,10 +3033,8 @@ LMPC_INSTANTIATE(float, 14, 0, double)
 // which is compiled with -mllvm -amdgpu-sched-strategy=iterative-minreg -- the most spill-bound kernel of the library is the one
 // place where the minimum-register scheduler pays (131 against 184 spilled VGPRs, 9.93 against 10.65 ms per 32768, same bits;
 // every other kernel is 3-20 % slower with it: profiles/r04_sched_strategies.md).  Here: declarations only.
-extern template __global__ void lmpc_solve_kernel<float, 4, 2, double>(lmpc_params, int, const double*, const double*, const double*, const double*,
-    const double*, const double*, const double*, const double*, const double*, double*, double*, double*, double*, int*, int*, double*);
-extern template __global__ void lmpc_solve_kernel<float, 4, 3, double>(lmpc_params, int, const double*, const double*, const double*, const double*,
-    const double*, const double*, const double*, const double*, const double*, double*, double*, double*, double*, int*, int*, double*);
+LMPC_INSTANTIATED_ELSEWHERE(float, 4, 2, double)
+LMPC_INSTANTIATED_ELSEWHERE(float, 4, 3, double)
 // the fp64 second pass behind each of the mixed kernels above
 #define LMPC_INSTANTIATE_CLEANUP(KQ, KS)                                                                                  \
   template __global__ void lmpc_cleanup_kernel<double, KQ, KS, double>(lmpc_params, int, const int*, const int*,          \

@@ -1,6 +1,8 @@
 // lmpc_solve_w2.hip.h -- TWO wavefronts per problem on one LDS record: the fp64 tracking kernels for N >= 24 (round 6).
-// (Included by lmpc_solve_kernel.hip: every device function of that file -- Riccati factorisation and sweeps, the lean model stream,
-//  the reductions -- is used as it is.  A translation unit of its own, lmpc_lib_w2.hip: it rebuilds in twenty seconds.)
+// (Included by lmpc_solve_kernel.hip behind everything it uses as it is: that file's Riccati factorisation and sweeps, its lean
+//  model stream and the polish's argument structs; the reductions and pins of lmpc_wave.hip.h, the layout and policies of
+//  lmpc_solve_layout.hip.h, the limits of lmpc_limits.hip.h.  A translation unit of its own, lmpc_lib_w2.hip: its object compiles
+//  in twenty seconds.)
 //
 // Why.  With one wave per problem the slots of the inequality rows are dealt to 64 lanes: 7 per lane at N = 40, 11 at N = 60, 14 at
 // N = 80.  A slot is 6 doubles of row state (slacks and multipliers of both sides, the predictor's products) + three table integers
@@ -24,10 +26,10 @@
 //   ... without the opaque slot tables                   6.23   10.64                      676 / 1276 / 1364
 //   ... the chain role by hardware placement (HW_ID) instead of wave 0: no difference (6.48 / 11.10)
 //   one wave, fused factorisation         1.56    2.35   5.00    9.70   4.05    11.41      424 / 1008 / 1792
-//   two waves, fused (LMPC_W2_FUSE, shipped) 1.65  2.47   4.85    8.06   4.15     9.54      316 /  644 /  820
+//   two waves, fused (shipped)            1.65    2.47   4.85    8.06   4.15     9.54      316 /  644 /  820
 // (fused: the predictor's backward sweep inside the factorisation, riccati_factor<.., FUSE> -- four dependent chains per iteration
 //  instead of five.)  The library takes these kernels from N = 41 on -- every lean-layout horizon: -1 .. 4 % up to N = 64, -19 % at N = 65
-//  (6.59 -> 5.32 ms: where the one-wave kernel goes from 11 to 14 slots per lane), -17 % at N = 80 -- lmpc_capi.hip: LMPC_W2_AUTO_KQ;
+//  (6.59 -> 5.32 ms: where the one-wave kernel goes from 11 to 14 slots per lane), -17 % at N = 80 -- lmpc_capi.hip: LMPC_W2_AUTO_KQ = 11;
 // lmpc_set_waves_per_problem forces either.  Answers: the one-wave kernel's to 1e-11, same statuses, same iteration counts on every
 // problem of the six batches.
 // Why not more: the chain wave still carries its row state across a Riccati stage that wants ~200 registers of its own, and the
@@ -41,22 +43,11 @@
 #define LMPC_SOLVE_W2_HIP_H_
 
 #define W2_THREADS 128
-#ifndef LMPC_W2_FUSE  // 1 (shipped): four dependent chains per iteration instead of five (N = 80: 9.55 -> ms, profiles/r06_fuse_ab.txt)
-#define LMPC_W2_FUSE 1
-#endif
-// slots per lane with 128 lanes: KQ is the one-wave kernel's (7: N <= 40, 11: N <= 64, 14: N <= 81)
-#ifndef LMPC_W2_SPLIT  // 1 (shipped): the slots dealt evenly, 4 / 6 / 7 per lane; 0: unevenly (the chain wave 3 / 4 / 4, the other 4 / 7 / 10)
-#define LMPC_W2_SPLIT 1
-#endif
-#ifndef LMPC_W2_ROLE  // 0 (shipped): the chain phases on wave 0 of every workgroup; 1: on the wave the hardware placed on the SIMD whose parity is its wave slot's
-#define LMPC_W2_ROLE 0
-#endif
-constexpr int lmpc_w2_slots0(int kq) { return LMPC_W2_SPLIT ? (kq <= 7 ? 4 : (kq <= 11 ? 6 : 7)) : (kq <= 7 ? 3 : 4); }  // the chain wave
-constexpr int lmpc_w2_slots1(int kq) {  // the other wave: 64 (KL0 + KL1) >= 11 N at the class's largest N
-  return LMPC_W2_SPLIT ? (kq <= 7 ? 4 : (kq <= 11 ? 6 : 7)) : (kq <= 7 ? 4 : (kq <= 11 ? 7 : 10));
-}
-static_assert(64 * (lmpc_w2_slots0(7) + lmpc_w2_slots1(7)) >= 11 * 40 && 64 * (lmpc_w2_slots0(11) + lmpc_w2_slots1(11)) >= 11 * 64 &&
-              64 * (lmpc_w2_slots0(14) + lmpc_w2_slots1(14)) >= 11 * 81, "every slot has an owner");
+// slots per lane with 128 lanes, dealt evenly to both waves: KQ is the one-wave kernel's (7: N <= 40, 11: N <= 64, 14: N <= 81);
+// 128 KL >= 11 N at the class's largest N.  (Measured: dealt unevenly -- the chain wave 3 / 4 / 4, the other 4 / 7 / 10 -- the
+// table above.)
+constexpr int lmpc_w2_slots(int kq) { return kq <= 7 ? 4 : (kq <= 11 ? 6 : 7); }
+static_assert(128 * lmpc_w2_slots(7) >= 11 * 40 && 128 * lmpc_w2_slots(11) >= 11 * 64 && 128 * lmpc_w2_slots(14) >= 11 * 81, "every slot has an owner");
 
 struct Wg2 {
   double* red;  // LDS: [2 parities][2 waves][8 values] -- cells of the factorisation's Y matrix, idle outside the chain phases
@@ -107,7 +98,7 @@ __device__ __attribute__((noinline)) PolishResult<double, 0> lmpc_polish_w2(cons
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const int N = uni(a.N), NS = N - 1;
   constexpr bool LEAN = lmpc_lean(8, KQ);
-  Lds<real> L{lds, N, LEAN ? LMPC_LEAN_STAGE_STRIDE : LMPC_STAGE_STRIDE, true, true};
+  Lds<real> L{lds, N, LEAN ? LMPC_LEAN_STAGE_STRIDE : LMPC_STAGE_STRIDE, true};
   real* const T = L.tail();
   Wg2 g{T + TL_Y, wv, 0};
   ModelStream<real> MS{nullptr, nullptr, NS, lane, uni(a.have0), uni(a.have1)};
@@ -388,7 +379,7 @@ __device__ __forceinline__ void lmpc_solve_problem_w2(const lmpc_params& P, cons
   const int N = P.N, NS = N - 1;
   const real inf = real(INFINITY), marg = real(P.marg), qsig = real(P.qsig), tol = lim::tol(P.tol);
   constexpr bool LEAN = lmpc_lean(8, KQ);
-  Lds<real> L{lds, N, LEAN ? LMPC_LEAN_STAGE_STRIDE : LMPC_STAGE_STRIDE, true, true};
+  Lds<real> L{lds, N, LEAN ? LMPC_LEAN_STAGE_STRIDE : LMPC_STAGE_STRIDE, true};
   real* T = L.tail();
   real* ct = T + TL_CT;
   real* KN0 = L.kn(0);
@@ -448,7 +439,7 @@ __device__ __forceinline__ void lmpc_solve_problem_w2(const lmpc_params& P, cons
 
   // ---------------- slot ownership: slot j = SLOT0 + lane + 64 q ----------------
   const bool has_sigma = P.has_sigma != 0;
-  const bool fuse = LMPC_W2_FUSE && has_sigma;  // the predictor's backward sweep inside the factorisation (riccati_factor<.., FUSE>)
+  const bool fuse = has_sigma;  // the predictor's backward sweep inside the factorisation (riccati_factor<.., FUSE>)
   const int KNB = NS * L.stride;
   const int JB = KNB + N * LMPC_KNOT_STRIDE + TL_W;
   const int CTB = KNB + N * LMPC_KNOT_STRIDE + TL_CT;
@@ -1004,29 +995,13 @@ __global__ __launch_bounds__(W2_THREADS, 2) void lmpc_solve_kernel_w2(lmpc_param
     b = (int)blockIdx.x < n ? P.launch_order[blockIdx.x] : B;
   }
   if (b >= B) return;
-  constexpr int KL0 = lmpc_w2_slots0(KQ), KL1 = lmpc_w2_slots1(KQ);
-  // Which of the two waves runs the chain phases: wave 0.  (LMPC_W2_ROLE = 1, an experiment kept for the record: if the hardware
-  // dealt a workgroup's waves to neighbouring SIMDs and filled a CU pair by pair, the chain waves of two problems would share SIMD 0
-  // and two more SIMD 2; giving the role to the wave whose SIMD parity equals its wave slot's parity would spread them.  Measured: no
-  // difference -- the chain phases' cycle counts are the one-wave kernel's either way.)
-  int chain_wave = 0;
-  if (LMPC_W2_ROLE) {
-    unsigned hw;
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
-    const int claim = ((((hw >> 4) & 3) ^ (hw & 15)) & 1) == 0;
-    int* const vote = reinterpret_cast<int*>(lds_raw);  // (the first cells of the records: not loaded yet)
-    if ((threadIdx.x & 63) == 0) vote[threadIdx.x >> 6] = claim;
-    __syncthreads();
-    const int v0 = vote[0], v1 = vote[1];
-    __syncthreads();
-    chain_wave = __builtin_amdgcn_readfirstlane((v0 != v1) ? (v0 ? 0 : 1) : 0);
-  }
-  if ((int)(threadIdx.x >> 6) == chain_wave)
-    lmpc_solve_problem_w2<KQ, KL0, 0, true>(P, B, b, lds_raw, ws_lin, x_ic, u_ic, T_ref, bl, br, vref, X_out, U_out, dU_out, status_out, iters_out,
-                                            kkt_out);
+  constexpr int KL = lmpc_w2_slots(KQ);
+  if ((threadIdx.x >> 6) == 0)  // wave 0 runs the chain phases (by hardware placement instead: no difference, the table above)
+    lmpc_solve_problem_w2<KQ, KL, 0, true>(P, B, b, lds_raw, ws_lin, x_ic, u_ic, T_ref, bl, br, vref, X_out, U_out, dU_out, status_out, iters_out,
+                                           kkt_out);
   else
-    lmpc_solve_problem_w2<KQ, KL1, 64 * KL0, false>(P, B, b, lds_raw, ws_lin, x_ic, u_ic, T_ref, bl, br, vref, X_out, U_out, dU_out, status_out,
-                                                    iters_out, kkt_out);
+    lmpc_solve_problem_w2<KQ, KL, 64 * KL, false>(P, B, b, lds_raw, ws_lin, x_ic, u_ic, T_ref, bl, br, vref, X_out, U_out, dU_out, status_out,
+                                                  iters_out, kkt_out);
 }
 
 #endif

@@ -4,7 +4,7 @@ The YAML files of the reference run the tracking controller at N = 40 / 60 / 80 
 iac_car_tracking_mpc.param.yaml) and the learning controller at N = 40 / 60 (barc_lmpc.param.yaml, iac_car_lmpc.param.yaml);
 until round 5 the GPU suite held those horizons to the twin on 24 - 48 problems only, and the builder's own full-size record
 (profiles/r04_fullsize_parity.txt) showed what that hid: 1.1e-6 at N = 80 and 1.7e-5 at learning N = 60, problems whose polish was
-refused one multiplier step short of convergence (fixed in round 5: csrc/lmpc_solve_kernel.hip `polish_limits<double>`).  Here:
+refused one multiplier step short of convergence (fixed in round 5: csrc/lmpc_limits.hip.h `polish_limits<double>`).  Here:
 batches of 4096 (IAC: the 8192 of configs[3]'s per-GPU share), the bench's own distributions, same assertions as
 test_gpu_path.py::test_full_batch_properties -- statuses equal, X / U / dU of every problem within 1e-6 (scaled), iteration counts
 equal on >= 90 %.  The twin is held to the dense optimum by tests/test_dense_fixtures.py (CPU) and scratch/r5/acc_dense.py."""
