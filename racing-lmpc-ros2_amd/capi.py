@@ -14,6 +14,7 @@ _HERE = Path(__file__).resolve().parent
 _LIB = None
 
 SOLVE_OPTIMAL, SOLVE_MAX_ITER, SOLVE_INFEASIBLE = 0, 1, 2
+TRACK_OK, TRACK_NOT_CONVERGED, TRACK_BAD_INPUT = 0, 1, 2   # per-pose status of Solver.global_to_frenet
 
 _ABI_SYMBOLS = ("lmpc_create", "lmpc_destroy", "lmpc_last_error", "lmpc_set_stream", "lmpc_synchronize",
                 "lmpc_linearize_batch", "lmpc_solve_batch", "lmpc_set_safe_set", "lmpc_ss_query_batch",
@@ -25,7 +26,9 @@ _ABI_SYMBOLS = ("lmpc_create", "lmpc_destroy", "lmpc_last_error", "lmpc_set_stre
                 "lmpc_last_solve_precision", "lmpc_solve_batch_warm_ss", "lmpc_solve_host_warm_ss", "lmpc_shift_lambda_batch",
                 "lmpc_get_warm_accepted", "lmpc_set_waves_per_problem",
                 "lmpc_fleet_ss_create", "lmpc_fleet_ss_destroy", "lmpc_fleet_ss_reset", "lmpc_fleet_ss_bytes", "lmpc_fleet_ss_record_batch",
-                "lmpc_fleet_ss_query_batch", "lmpc_fleet_ss_load", "lmpc_fleet_ss_get_laps", "lmpc_fleet_ss_stats")
+                "lmpc_fleet_ss_query_batch", "lmpc_fleet_ss_load", "lmpc_fleet_ss_get_laps", "lmpc_fleet_ss_stats",
+                "lmpc_spline_track_create", "lmpc_spline_track_destroy", "lmpc_spline_track_tabulate", "lmpc_track_sample_batch",
+                "lmpc_global_to_frenet_batch", "lmpc_frenet_to_global_batch")
 
 
 class LmpcError(RuntimeError):
@@ -114,6 +117,25 @@ def _ptr(t):
     if t is None:
         return C.c_void_p(0)
     return C.c_void_p(t.data_ptr())
+
+
+class SplineTrack:
+    """A track's splines on the device (lmpc_spline_track), made by Solver.spline_track; freed by close() or with the object."""
+
+    def __init__(self, solver, ptr, L: float, h_bar: float, n_wp: int):
+        self._solver, self._p = solver, ptr
+        self.L, self.h_bar, self.n_wp = L, h_bar, n_wp
+
+    def close(self):
+        if getattr(self, "_p", None) and getattr(self._solver, "_h", None):
+            self._solver.lib.lmpc_spline_track_destroy(self._solver._h, self._p)
+        self._p = C.c_void_p(0)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class Solver:
@@ -671,4 +693,77 @@ class Solver:
         rc = self.lib.lmpc_fleet_ss_stats(self._h, C.c_int32(B), _ptr(out.get("laps_in_ring")), _ptr(out.get("lap_count")),
                                           _ptr(out.get("n_dropped")), _ptr(out.get("last_lap_time")))
         self._check(rc, "lmpc_fleet_ss_stats")
+        return out
+
+    # ---- spline track: the interpolants on the device, global <-> Frenet (racing_trajectory.cpp:25-236; include/lmpc_hip.h) ----
+    def spline_track(self, tr) -> SplineTrack:
+        """lmpc_spline_track_create from a RacingTrajectory (or the dict its to_spline_track() returns): uploads once."""
+        import numpy as np
+        self.use_current_stream()
+        d = tr if isinstance(tr, dict) else tr.to_spline_track()
+        arr = {k: np.ascontiguousarray(d[k], dtype=np.float64) for k in ("breaks", "coef", "wp_x", "wp_y", "wp_s")}
+        P, n_wp = arr["breaks"].size - 1, arr["wp_s"].size
+        if arr["coef"].shape != (5, P, 4) or arr["wp_x"].size != n_wp or arr["wp_y"].size != n_wp:
+            raise ValueError("spline_track: coef must be [5][P][4] for P + 1 breaks, and wp_x, wp_y, wp_s of one length")
+        dp = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))  # noqa: E731
+        p = C.c_void_p(0)
+        rc = self.lib.lmpc_spline_track_create(self._h, C.c_double(float(d["L"])), C.c_int32(P), dp(arr["breaks"]), dp(arr["coef"]),
+                                               C.c_int32(n_wp), dp(arr["wp_x"]), dp(arr["wp_y"]), dp(arr["wp_s"]), C.byref(p))
+        self._check(rc, "lmpc_spline_track_create")
+        return SplineTrack(self, p, float(d["L"]), float(np.median(np.diff(arr["wp_s"]))), n_wp)
+
+    def track_sample(self, track: SplineTrack, s, out=None):
+        """lmpc_track_sample_batch: the interpolants at the abscissae s [n] (any value: wrapped) -> float64 [7][n] =
+        x, y, yaw, curvature (as written upstream), left, right, vel."""
+        self.use_current_stream()
+        s = self._t(s).reshape(-1)
+        if out is None:
+            out = self._torch.empty((7, s.numel()), dtype=self._torch.float64, device=self.device)
+        self._check(self.lib.lmpc_track_sample_batch(self._h, track._p, C.c_int32(s.numel()), _ptr(s), _ptr(out)), "lmpc_track_sample_batch")
+        return out
+
+    def tabulate_track(self, track: SplineTrack, M: int = 1024) -> dict:
+        """lmpc_spline_track_tabulate: the uniform tables of an lmpc_track (what RacingTrajectory.to_track_table samples on the host),
+        filled on the device; the returned dict goes wherever a `track` is expected."""
+        torch = self._torch
+        self.use_current_stream()
+        out = {k: torch.empty((M,), dtype=torch.float64, device=self.device) for k in ("curvature", "bound_left", "bound_right", "vel")}
+        rc = self.lib.lmpc_spline_track_tabulate(self._h, track._p, C.c_int32(M), *[_ptr(out[k]) for k in ("curvature", "bound_left", "bound_right", "vel")])
+        self._check(rc, "lmpc_spline_track_tabulate")
+        out["L"], out["M"] = track.L, int(M)
+        return out
+
+    def global_to_frenet(self, track: SplineTrack, pose, s0=None, seeded=None, out=None):
+        """lmpc_global_to_frenet_batch: pose [3][B] = (x, y, yaw) -> (frenet [3][B] = (s, t, xi), status int32 [B]: TRACK_*).  s0 [B]
+        starts the search of the poses with seeded[b] != 0 (int32 [B]; None: all of them), the others start at the nearest
+        waypoint.  `out` = (frenet, status) reuses buffers.  Asynchronous."""
+        torch = self._torch
+        self.use_current_stream()
+        pose = self._t(pose)
+        B = pose.shape[1]
+        if s0 is not None:
+            s0 = self._t(s0)
+        if seeded is not None:
+            if s0 is None:
+                raise ValueError("global_to_frenet: `seeded` needs s0")
+            seeded = torch.as_tensor(seeded, dtype=torch.int32, device=self.device).contiguous()
+        frenet, status = out if out is not None else (torch.empty((3, B), dtype=torch.float64, device=self.device),
+                                                      torch.empty((B,), dtype=torch.int32, device=self.device))
+        rc = self.lib.lmpc_global_to_frenet_batch(self._h, track._p, C.c_int32(B), _ptr(pose), _ptr(s0), _ptr(seeded), _ptr(frenet), _ptr(status))
+        self._check(rc, "lmpc_global_to_frenet_batch")
+        return frenet, status
+
+    def frenet_to_global(self, track: SplineTrack, X, out=None):
+        """lmpc_frenet_to_global_batch: rows 0 - 2 of X [6][n][B] (a plan) or [6][B] (car states; any leading size >= 3) ->
+        pose [3][n][B] / [3][B] = (x, y, yaw).  Asynchronous."""
+        torch = self._torch
+        self.use_current_stream()
+        X = self._t(X)
+        if X.dim() not in (2, 3) or X.shape[0] < 3:
+            raise ValueError("frenet_to_global: X is [>= 3][n][B] or [>= 3][B]")
+        shape = (3,) + tuple(X.shape[1:])
+        n, B = (1, X.shape[1]) if X.dim() == 2 else (X.shape[1], X.shape[2])
+        if out is None:
+            out = torch.empty(shape, dtype=torch.float64, device=self.device)
+        self._check(self.lib.lmpc_frenet_to_global_batch(self._h, track._p, C.c_int32(B), C.c_int32(n), _ptr(X), _ptr(out)), "lmpc_frenet_to_global_batch")
         return out

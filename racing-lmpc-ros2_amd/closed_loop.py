@@ -119,6 +119,41 @@ def run(solver, track: dict, x0, u0, steps: int, dt: float = 0.025, n_sub: int =
             "warm_hit_rate": (float(hits) / (B * max(steps, 1))) if warm else None}
 
 
+def run_global(solver, track: dict, spline, x0, u0, steps: int, dt: float = 0.025, n_sub: int = 2, speed_scale: float = 0.9,
+               restart_failed: bool = True, warm: bool = False):
+    """`run` (fused) with the state crossing the GLOBAL frame every period, as it does between the reference's simulator node and its
+    controller node: after lmpc_loop_advance_batch the cars' (s, e_y, e_psi) go to poses (x, y, yaw) with lmpc_frenet_to_global_batch
+    (racing_simulator_node.cpp:273-278), the poses are projected back with lmpc_global_to_frenet_batch started from the abscissa they
+    came from (racing_mpc_node.cpp:181-185, initialize_with_previous), and the result replaces x[0:3] -- two more launches per period,
+    no host round trip.  `spline`: Solver.spline_track of the track whose tables `track` holds.  Returns run's statistics and
+    "track_status": int32 [B], the largest projection status a car has seen (0: every projection converged)."""
+    import torch
+
+    trk = solver.device_track(track)
+    x, u_prev = x0.clone(), u0.clone()
+    B = x.shape[1]
+    inp = solver.prepare(trk, x, dt, speed_scale=speed_scale)
+    out = solver.alloc_outputs(B)
+    kw = dict(dtype=torch.float64, device=x.device)
+    dist, worst_excess = torch.zeros(B, **kw), torch.zeros(B, **kw)
+    n_fail = torch.zeros(B, dtype=torch.int64, device=x.device)
+    hits = torch.zeros((), dtype=torch.int64, device=x.device)
+    pose, frenet = torch.empty((3, B), **kw), torch.empty((3, B), **kw)
+    status = torch.empty(B, dtype=torch.int32, device=x.device)
+    track_status = torch.zeros(B, dtype=torch.int32, device=x.device)
+    for _ in range(steps):
+        inp["x_ic"], inp["u_ic"] = x, u_prev
+        solver.solve(inp, out, warm=True if warm else None)
+        solver.loop_advance(trk, inp, out, x, u_prev, dt, dt / n_sub, n_sub, speed_scale=speed_scale, restart_failed=restart_failed,
+                            distance=dist, worst_excess=worst_excess, n_fail=n_fail, n_accepted=hits if warm else None)
+        solver.frenet_to_global(spline, x, out=pose)
+        solver.global_to_frenet(spline, pose, s0=x[0], out=(frenet, status))
+        x[0:3].copy_(frenet)
+        torch.maximum(track_status, status, out=track_status)
+    return {"x": x, "distance": dist, "worst_excess": worst_excess, "n_fail": n_fail, "track_status": track_status,
+            "warm_hit_rate": (float(hits) / (B * max(steps, 1))) if warm else None}
+
+
 def record_laps(solver, track: dict, speed_scales=(0.80, 0.85, 0.90, 0.95, 1.0), dt: float = 0.03, n_sub: int = 3):
     """The laps SURVEY.md 8d config 3 stores in the safe set: "running config 1's tracking loop for 5 laps with seed-indexed speed
     scales {0.80, 0.85, 0.90, 0.95, 1.0}", one sample per 0.03 s (the recorder's period upstream, racing_mpc_node.cpp:66).  One

@@ -10,6 +10,7 @@
 // is launched: `launch_params` / `launch_solve`; what a solve is asked: `solve_args`); the exported functions.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -135,6 +136,14 @@ struct __attribute__((visibility("hidden"))) lmpc_handle {  // (its members are 
     for (auto& e : ev)
       if (e) (void)hipEventDestroy(e);
   }
+};
+
+// A spline track (lmpc_spline_track_create): the device copy of RacingTrajectory's piecewise cubics and waypoints; `view` is what the
+// kernels of lmpc_track_kernel.hip take.
+struct __attribute__((visibility("hidden"))) lmpc_spline_track {
+  lmpc_spline_view view{};
+  int device = 0;
+  dev_buf<double> breaks, coef, wp_xy, wp_s;
 };
 
 namespace {
@@ -1643,6 +1652,141 @@ int lmpc_fleet_ss_get_laps(lmpc_handle* h, int32_t car, int32_t* n_laps, int32_t
       if (t) t[o] = ax[(size_t)i * 4 + 3];
     }
   }
+  return LMPC_OK;
+}
+
+// ---- spline track: the interpolants on the device, global <-> Frenet (lmpc_track_kernel.hip) ----
+
+int lmpc_spline_track_create(lmpc_handle* h, double L, int32_t P, const double* breaks, const double* coef, int32_t n_wp,
+                             const double* wp_x, const double* wp_y, const double* wp_s, lmpc_spline_track** track) {
+  if (!h) return LMPC_ERR_ARGUMENT;
+  if (!track) return fail(h, LMPC_ERR_ARGUMENT, "lmpc_spline_track_create: null track");
+  *track = nullptr;
+  if (!(L > 0.0) || !std::isfinite(L) || P < 1 || n_wp < 2 || !breaks || !coef || !wp_x || !wp_y || !wp_s)
+    return fail(h, LMPC_ERR_ARGUMENT, "lmpc_spline_track_create: null pointer, L <= 0, P < 1 or n_wp < 2");
+  for (int i = 0; i <= P; ++i)
+    if (!std::isfinite(breaks[i]) || (i > 0 && !(breaks[i] > breaks[i - 1])))
+      return fail(h, LMPC_ERR_ARGUMENT, "lmpc_spline_track_create: breaks must be finite and strictly increasing");
+  // the wrapped abscissa lies in [0, L]: the pieces have to cover it, or the end pieces would extrapolate over part of the lap
+  if (breaks[0] > 0.0 || breaks[P] < L) return fail(h, LMPC_ERR_ARGUMENT, "lmpc_spline_track_create: the breaks do not cover [0, L]");
+  for (size_t e = 0; e < (size_t)5 * P * 4; ++e)
+    if (!std::isfinite(coef[e])) return fail(h, LMPC_ERR_ARGUMENT, "lmpc_spline_track_create: non-finite coefficient");
+  for (int j = 0; j < n_wp; ++j)
+    if (!std::isfinite(wp_x[j]) || !std::isfinite(wp_y[j]) || !std::isfinite(wp_s[j]))
+      return fail(h, LMPC_ERR_ARGUMENT, "lmpc_spline_track_create: non-finite waypoint");
+  // one record per piece (x | y | vel | left | right), waypoints as (x, y) pairs, the median waypoint spacing
+  std::vector<double> rec((size_t)P * LMPC_TRACK_COEF), xy((size_t)n_wp * 2), gap((size_t)n_wp - 1);
+  for (int c = 0; c < 5; ++c)
+    for (int i = 0; i < P; ++i)
+      for (int k = 0; k < 4; ++k) rec[(size_t)i * LMPC_TRACK_COEF + 4 * c + k] = coef[((size_t)c * P + i) * 4 + k];
+  for (int j = 0; j < n_wp; ++j) xy[2 * (size_t)j] = wp_x[j], xy[2 * (size_t)j + 1] = wp_y[j];
+  for (int j = 0; j + 1 < n_wp; ++j) gap[j] = wp_s[j + 1] - wp_s[j];
+  std::sort(gap.begin(), gap.end());
+  const size_t ng = gap.size();
+  const double hbar = ng % 2 ? gap[ng / 2] : (gap[ng / 2 - 1] + gap[ng / 2]) / 2.0;
+  if (!(hbar > 0.0)) return fail(h, LMPC_ERR_ARGUMENT, "lmpc_spline_track_create: the waypoint abscissae must increase");
+  lmpc_spline_track* t = new (std::nothrow) lmpc_spline_track();
+  if (!t) return fail(h, LMPC_ERR_RUNTIME, "lmpc_spline_track_create: out of memory");
+  auto upload = [&]() -> int {
+    HIP_TRY(h, hipSetDevice(h->device));
+    HIP_TRY(h, t->breaks.alloc((size_t)P + 1));
+    HIP_TRY(h, t->coef.alloc(rec.size()));
+    HIP_TRY(h, t->wp_xy.alloc(xy.size()));
+    HIP_TRY(h, t->wp_s.alloc((size_t)n_wp));
+    HIP_TRY(h, hipMemcpyAsync(t->breaks.get(), breaks, ((size_t)P + 1) * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(t->coef.get(), rec.data(), rec.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(t->wp_xy.get(), xy.data(), xy.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(t->wp_s.get(), wp_s, (size_t)n_wp * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return LMPC_OK;
+  };
+  const int rc = upload();
+  if (rc != LMPC_OK) {
+    (void)hipStreamSynchronize(h->stream);  // (a copy may still read the host vectors)
+    delete t;
+    return rc;
+  }
+  t->device = h->device;
+  t->view = lmpc_spline_view{L, hbar, P, n_wp, t->breaks.get(), t->coef.get(), t->wp_xy.get(), t->wp_s.get()};
+  *track = t;
+  return LMPC_OK;
+}
+
+int lmpc_spline_track_destroy(lmpc_handle* h, lmpc_spline_track* track) {
+  if (!h) return LMPC_ERR_ARGUMENT;
+  if (!track) return LMPC_OK;
+  HIP_TRY(h, hipSetDevice(h->device));
+  HIP_TRY(h, hipStreamSynchronize(h->stream));  // a launch that reads the tables may still be queued
+  delete track;
+  return LMPC_OK;
+}
+
+}  // extern "C"
+
+namespace {
+int spline_track_check(lmpc_handle* h, const lmpc_spline_track* track, const char* who) {
+  if (!track) return fail(h, LMPC_ERR_ARGUMENT, std::string(who) + ": null track");
+  if (track->device != h->device) return fail(h, LMPC_ERR_ARGUMENT, std::string(who) + ": the track lives on another device");
+  return LMPC_OK;
+}
+
+int track_sample(lmpc_handle* h, const lmpc_spline_track* track, int32_t n, const double* s, double* x, double* y, double* yaw,
+                 double* curvature, double* left, double* right, double* vel) {
+  HIP_TRY(h, hipSetDevice(h->device));
+  hipLaunchKernelGGL(lmpc_track_sample_kernel, dim3((n + 255) / 256), dim3(256), 0, h->stream, track->view, n, s, x, y, yaw, curvature, left,
+                     right, vel);
+  HIP_TRY(h, hipGetLastError());
+  return LMPC_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int lmpc_track_sample_batch(lmpc_handle* h, const lmpc_spline_track* track, int32_t n, const double* s, double* out) {
+  if (!h) return LMPC_ERR_ARGUMENT;
+  const int rc = spline_track_check(h, track, "lmpc_track_sample_batch");
+  if (rc != LMPC_OK) return rc;
+  if (n < 0 || !s || !out) return fail(h, LMPC_ERR_ARGUMENT, "lmpc_track_sample_batch: null pointer or negative n");
+  if (n == 0) return LMPC_OK;
+  const size_t m = (size_t)n;
+  return track_sample(h, track, n, s, out, out + m, out + 2 * m, out + 3 * m, out + 4 * m, out + 5 * m, out + 6 * m);
+}
+
+int lmpc_spline_track_tabulate(lmpc_handle* h, const lmpc_spline_track* track, int32_t M, double* curvature, double* bound_left,
+                               double* bound_right, double* vel) {
+  if (!h) return LMPC_ERR_ARGUMENT;
+  const int rc = spline_track_check(h, track, "lmpc_spline_track_tabulate");
+  if (rc != LMPC_OK) return rc;
+  if (M < 2 || !curvature || !bound_left || !bound_right || !vel)  // (an lmpc_track has at least two samples)
+    return fail(h, LMPC_ERR_ARGUMENT, "lmpc_spline_track_tabulate: null pointer or M < 2");
+  return track_sample(h, track, M, nullptr, nullptr, nullptr, nullptr, curvature, bound_left, bound_right, vel);
+}
+
+int lmpc_global_to_frenet_batch(lmpc_handle* h, const lmpc_spline_track* track, int32_t B, const double* pose, const double* s0,
+                                const int32_t* seeded, double* frenet, int32_t* status) {
+  if (!h) return LMPC_ERR_ARGUMENT;
+  const int rc = spline_track_check(h, track, "lmpc_global_to_frenet_batch");
+  if (rc != LMPC_OK) return rc;
+  if (B < 0 || !pose || !frenet || !status || (seeded && !s0))
+    return fail(h, LMPC_ERR_ARGUMENT, "lmpc_global_to_frenet_batch: null pointer, negative batch, or `seeded` without s0");
+  if (B == 0) return LMPC_OK;
+  HIP_TRY(h, hipSetDevice(h->device));
+  hipLaunchKernelGGL(lmpc_track_project_kernel, dim3((B + 63) / 64), dim3(64), 0, h->stream, track->view, B, pose, s0, seeded, frenet, status);
+  HIP_TRY(h, hipGetLastError());
+  return LMPC_OK;
+}
+
+int lmpc_frenet_to_global_batch(lmpc_handle* h, const lmpc_spline_track* track, int32_t B, int32_t n, const double* X, double* pose) {
+  if (!h) return LMPC_ERR_ARGUMENT;
+  const int rc = spline_track_check(h, track, "lmpc_frenet_to_global_batch");
+  if (rc != LMPC_OK) return rc;
+  if (B < 0 || n < 1 || !X || !pose) return fail(h, LMPC_ERR_ARGUMENT, "lmpc_frenet_to_global_batch: null pointer, negative batch or n < 1");
+  if (B == 0) return LMPC_OK;
+  const long long count = (long long)n * B;
+  if (count > (1LL << 31) * 256 - 256) return fail(h, LMPC_ERR_ARGUMENT, "lmpc_frenet_to_global_batch: n x batch too large");
+  HIP_TRY(h, hipSetDevice(h->device));
+  hipLaunchKernelGGL(lmpc_track_to_global_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, h->stream, track->view, count, X, pose);
+  HIP_TRY(h, hipGetLastError());
   return LMPC_OK;
 }
 

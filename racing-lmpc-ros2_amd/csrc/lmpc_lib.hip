@@ -6,4 +6,5 @@
 #include "lmpc_fleet_ss_kernel.hip"
 #include "lmpc_reg_kernel.hip"
 #include "lmpc_sqp_kernel.hip"
+#include "lmpc_track_kernel.hip"
 #include "lmpc_capi.hip"

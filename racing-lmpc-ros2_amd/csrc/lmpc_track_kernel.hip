@@ -1,0 +1,225 @@
+// lmpc_track_kernel.hip -- the track's interpolating splines on the device: global <-> Frenet for a batch of poses.
+//
+// RacingTrajectory (racing_trajectory.cpp:25-236) fits five not-a-knot cubics -- x, y, speed, left and right boundary offset -- through
+// the waypoints over their abscissa and derives yaw = atan2(y', x') and the curvature expression as written (:108-110); every
+// interpolant is evaluated at align_abscissa(s, L/2, L) (:98).  The banded solve stays on the host, once per track
+// (RacingTrajectory::to_spline_track); what arrives here is the piecewise polynomials a + b h + c h^2 + d h^3 over the P + 1 breaks of
+// the extended waypoint abscissae, repacked by lmpc_spline_track_create as one 160-byte record per piece
+//     coef[piece] = x[4] | y[4] | vel[4] | left[4] | right[4]
+// so that the projection gathers a piece's x and y coefficients as one 64-byte line.  Three kernels:
+//   lmpc_track_project_kernel    global_to_frenet (:204-236; called by RacingMPCNode::on_step_timer, racing_mpc_node.cpp:181-185, and by
+//                                the simulator node, racing_simulator_node.cpp:60-65), one lane per pose
+//   lmpc_track_to_global_kernel  frenet_to_global (:122-186; frenet_to_global_function().map(N), racing_mpc_node.cpp:50,460), one
+//                                thread per (knot, problem)
+//   lmpc_track_sample_kernel     the seven interpolants at arbitrary abscissae, or at s_j = j L / M into the tables of an lmpc_track
+// Contraction is off in everything that evaluates a spline: the three kernels then compute r(s) with the same roundings (and the
+// same as the host classes), so that a pose made by one kernel projects back onto its abscissa through another.
+//
+// The tables are small (BARC: 159 pieces, 25 KB; 1400 waypoints: 225 KB) and read-only: they are gathered from global memory and
+// stay in L2.  (Staging the breaks and the x / y coefficients in LDS was not built: 72 KB at 1400 waypoints would cap a CU at
+// two workgroups for a kernel whose launch, not its loads, is what a batch of 4096 pays for -- DESIGN.md section 4.)
+#include <hip/hip_runtime.h>
+
+#include <math.h>
+
+#include "lmpc_device.h"
+
+#define LMPC_TRACK_COEF 20  // doubles per piece
+
+// what the kernels take of an lmpc_spline_track (csrc/lmpc_capi.hip owns the buffers)
+struct lmpc_spline_view {
+  double L;      // total length
+  double hbar;   // median waypoint spacing
+  int P;         // pieces; breaks [P + 1]
+  int n_wp;      // waypoints
+  const double* breaks;
+  const double* coef;   // [P][LMPC_TRACK_COEF]
+  const double* wp_xy;  // [n_wp][2]
+  const double* wp_s;   // [n_wp]
+};
+
+// align_abscissa(s, L/2, L): lmpc_utils/utils.hpp:35-41 -- the abscissa every interpolant is evaluated at (racing_trajectory.cpp:98)
+__device__ __forceinline__ double track_mod(double s, double L) {
+#pragma clang fp contract(off)
+  const double s2 = L / 2.0;
+  const double k = fabs(s2 - s) + L / 2.0;
+  const double l = k - fmod(k, L);
+  return s + l * (double)((s2 > s) - (s2 < s));
+}
+
+// The last piece whose left break is <= sm (the end pieces extrapolate): binary search over breaks [0 .. P], started from `hint`
+// (a piece index in [0, P)).  Terminates whatever sm is: the interval shrinks on either outcome of the comparison.
+__device__ __forceinline__ int track_piece(const double* __restrict__ breaks, int P, double sm, int hint) {
+  const double left = breaks[hint];
+  if (left <= sm && (hint == P - 1 || sm < breaks[hint + 1])) return hint;
+  int lo = left <= sm ? hint : 0, hi = left <= sm ? P : hint;
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (breaks[mid] <= sm) lo = mid; else hi = mid;
+  }
+  return lo;
+}
+
+struct track_poly {
+  double a, b, c, d;
+};
+__device__ __forceinline__ track_poly track_load(const double* __restrict__ coef, int piece, int which) {
+  const double2* p = reinterpret_cast<const double2*>(coef + (size_t)piece * LMPC_TRACK_COEF + 4 * which);  // 32-byte aligned
+  const double2 lo = p[0], hi = p[1];
+  return {lo.x, lo.y, hi.x, hi.y};
+}
+// NotAKnotCubic::operator() (host/racing_trajectory.cpp): value, first and second derivative, in the host's Horner forms
+__device__ __forceinline__ double poly0(const track_poly& q, double h) {
+#pragma clang fp contract(off)
+  return q.a + h * (q.b + h * (q.c + h * q.d));
+}
+__device__ __forceinline__ double poly1(const track_poly& q, double h) {
+#pragma clang fp contract(off)
+  return q.b + h * (2.0 * q.c + 3.0 * h * q.d);
+}
+__device__ __forceinline__ double poly2(const track_poly& q, double h) {
+#pragma clang fp contract(off)
+  return 2.0 * q.c + 6.0 * h * q.d;
+}
+
+// the centre line and its derivatives at abscissa s (wrapped here); `piece` in: where to start the lookup, out: the piece used
+struct track_point {
+  double x, y, dx, dy, d2x, d2y;
+};
+__device__ __forceinline__ track_point track_eval(const lmpc_spline_view& T, double s, int& piece) {
+#pragma clang fp contract(off)
+  const double sm = track_mod(s, T.L);
+  piece = track_piece(T.breaks, T.P, sm, piece);
+  const double h = sm - T.breaks[piece];
+  const track_poly qx = track_load(T.coef, piece, 0), qy = track_load(T.coef, piece, 1);
+  return {poly0(qx, h), poly0(qy, h), poly1(qx, h), poly1(qy, h), poly2(qx, h), poly2(qy, h)};
+}
+
+// utils.hpp:25-31
+__device__ __forceinline__ double track_align_yaw(double yaw_1, double yaw_2) {
+#pragma clang fp contract(off)
+  const double d = yaw_1 - yaw_2;
+  return atan2(sin(d), cos(d)) + yaw_2;
+}
+
+// RacingTrajectory::global_to_frenet for B poses, pose [3][B] = (x, y, yaw) -> frenet [3][B] = (s, t, xi), status [B].
+// Seed: s0[b] where s0 != NULL and (seeded == NULL or seeded[b] != 0) and s0[b] is finite; else the abscissa of the nearest
+// waypoint, first index on ties (the kd-tree lookup upstream, :213-216).  The waypoint loop is wave-uniform: a waypoint arrives by
+// scalar loads and every lane tests its own distance; a wave whose lanes are all seeded skips it.
+// Iteration: Newton on the first-order condition g(s) = (r(s) - p) . r'(s) of the distance the reference minimises (:144-169, CasADi
+// sqpmethod), H = |r'|^2 + (r - p) . r'': step -g / H where H > 1e-3 |r'|^2, else -sign(g) hbar; |step| <= 2 hbar; the step is halved
+// while |g| grows, at most 6 times; stop when the step taken is below 1e-13 max(1, L); 30 iterations at most
+// (LMPC_TRACK_NOT_CONVERGED).  Every evaluation wraps its abscissa, so the iterate never walks onto the +L copies of the first pieces.
+// A non-finite pose is LMPC_TRACK_BAD_INPUT with NaN outputs: its lane iterates on the first waypoint instead, so that every loop
+// below runs on finite values, and no lane reads another's data.
+__global__ __launch_bounds__(64) void lmpc_track_project_kernel(lmpc_spline_view T, int B, const double* __restrict__ pose,
+                                                                const double* __restrict__ s0, const int* __restrict__ seeded,
+                                                                double* __restrict__ frenet, int* __restrict__ status) {
+#pragma clang fp contract(off)
+  const int gb = blockIdx.x * 64 + threadIdx.x;
+  const bool live = gb < B;
+  const int b = live ? gb : B - 1;
+  double px = pose[b], py = pose[(size_t)B + b], phi = pose[2 * (size_t)B + b];
+  const bool bad = !(isfinite(px) && isfinite(py) && isfinite(phi));
+  if (bad) px = T.wp_xy[0], py = T.wp_xy[1], phi = 0.0;
+  double s = 0.0;
+  bool have_seed = false;
+  if (s0 && (!seeded || seeded[b] != 0)) {
+    s = s0[b];
+    have_seed = isfinite(s);
+  }
+  if (__any(!have_seed)) {
+    double best = INFINITY;
+    int ibest = 0;
+#pragma unroll 4
+    for (int j = 0; j < T.n_wp; ++j) {
+      const double wx = T.wp_xy[2 * (size_t)j], wy = T.wp_xy[2 * (size_t)j + 1];  // wave-uniform address: scalar loads
+      const double d = (wx - px) * (wx - px) + (wy - py) * (wy - py);
+      if (d < best) best = d, ibest = j;
+    }
+    if (!have_seed) s = T.wp_s[ibest];
+  }
+  const double hbar = T.hbar, tol = 1e-13 * fmax(1.0, T.L);
+  int piece = 0, st = LMPC_TRACK_NOT_CONVERGED;
+  s = track_mod(s, T.L);
+  track_point r = track_eval(T, s, piece);
+  double ex = r.x - px, ey = r.y - py;
+  double g = ex * r.dx + ey * r.dy;
+  for (int it = 0; it < 30; ++it) {
+    const double v2 = r.dx * r.dx + r.dy * r.dy;
+    const double H = v2 + (ex * r.d2x + ey * r.d2y);
+    double step = H > 1e-3 * v2 ? -g / H : -(double)((g > 0.0) - (g < 0.0)) * hbar;
+    step = fmin(fmax(step, -2.0 * hbar), 2.0 * hbar);
+    double a = 1.0, sn, gn;
+    track_point rn;
+    for (int k = 0;; ++k) {
+      sn = s + a * step;
+      rn = track_eval(T, sn, piece);
+      gn = (rn.x - px) * rn.dx + (rn.y - py) * rn.dy;
+      if (!(fabs(gn) > fabs(g)) || k == 6) break;
+      a *= 0.5;
+    }
+    s = sn, r = rn, g = gn;
+    ex = r.x - px, ey = r.y - py;
+    if (fabs(a * step) < tol) {
+      st = 0;
+      break;
+    }
+  }
+  // the outputs, exactly as the host class forms them (racing_trajectory.cpp:170-180)
+  const double so = track_mod(s, T.L);
+  const track_point o = track_eval(T, so, piece);
+  const double yaw = atan2(o.dy, o.dx);
+  const double sg = cos(yaw) * (py - o.y) - sin(yaw) * (px - o.x);  // lateral_sign (utils.hpp)
+  double t = hypot(px - o.x, py - o.y) * (double)((sg > 0.0) - (sg < 0.0));
+  double xi = track_align_yaw(phi, yaw) - yaw;
+  double s_out = so;
+  if (bad) s_out = t = xi = NAN, st = LMPC_TRACK_BAD_INPUT;
+  if (live) {
+    frenet[b] = s_out;
+    frenet[(size_t)B + b] = t;
+    frenet[2 * (size_t)B + b] = xi;
+    status[b] = st;
+  }
+}
+
+// RacingTrajectory::frenet_to_global for rows 0 - 2 (s, e_y, e_psi) of an SOA state array X [6][n][B] -> pose [3][n][B] = (x, y, yaw);
+// one thread per (knot, problem), `count` = n B of them.
+__global__ __launch_bounds__(256) void lmpc_track_to_global_kernel(lmpc_spline_view T, long long count, const double* __restrict__ X,
+                                                                   double* __restrict__ pose) {
+#pragma clang fp contract(off)
+  const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (e >= count) return;
+  const double s = X[e], t = X[count + e], xi = X[2 * count + e];
+  int piece = 0;
+  const track_point r = track_eval(T, s, piece);
+  const double yaw0 = atan2(r.dy, r.dx);
+  pose[e] = r.x - sin(yaw0) * t;
+  pose[count + e] = r.y + cos(yaw0) * t;
+  pose[2 * count + e] = track_align_yaw(yaw0 + xi, 0.0);
+}
+
+// The interpolants at abscissa s[j] (s != NULL) or at s_j = j L / n, the sample points of an lmpc_track with M = n (s == NULL).
+// Any output may be NULL.  curvature: x' y'' - y' x'' / sqrt((x'^2 + y'^2)^3), as written (:108-110).
+__global__ __launch_bounds__(256) void lmpc_track_sample_kernel(lmpc_spline_view T, int n, const double* __restrict__ s_in,
+                                                                double* __restrict__ x, double* __restrict__ y, double* __restrict__ yaw,
+                                                                double* __restrict__ curvature, double* __restrict__ left,
+                                                                double* __restrict__ right, double* __restrict__ vel) {
+#pragma clang fp contract(off)
+  const int j = blockIdx.x * 256 + threadIdx.x;
+  if (j >= n) return;
+  const double s = s_in ? s_in[j] : T.L * (double)j / (double)n;
+  int piece = 0;
+  const track_point r = track_eval(T, s, piece);
+  const double h = track_mod(s, T.L) - T.breaks[piece];
+  if (x) x[j] = r.x;
+  if (y) y[j] = r.y;
+  if (yaw) yaw[j] = atan2(r.dy, r.dx);
+  if (curvature) {
+    const double v2 = r.dx * r.dx + r.dy * r.dy;
+    curvature[j] = r.dx * r.d2y - r.dy * r.d2x / sqrt(v2 * v2 * v2);
+  }
+  if (vel) vel[j] = poly0(track_load(T.coef, piece, 2), h);
+  if (left) left[j] = poly0(track_load(T.coef, piece, 3), h);
+  if (right) right[j] = poly0(track_load(T.coef, piece, 4), h);
+}

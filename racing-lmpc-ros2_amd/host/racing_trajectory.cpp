@@ -1,6 +1,7 @@
 // racing_trajectory.cpp -- see racing_trajectory.hpp.
 #include "racing_trajectory.hpp"
 
+#include <algorithm>
 #include <cmath>
 #include <fstream>
 #include <sstream>
@@ -203,6 +204,26 @@ void RacingTrajectory::to_track_table(std::size_t M, std::vector<double>& curvat
     bound_right[j] = right_boundary_interpolation(s);
     vel[j] = velocity_interpolation(s);
   }
+}
+
+void RacingTrajectory::to_spline_track(SplineTrack& out) const {
+  const NotAKnotCubic* cubics[5] = {&x_, &y_, &vel_, &left_, &right_};
+  out.L = total_length_;
+  out.breaks = x_.breaks();
+  const std::size_t P = out.breaks.size() - 1, n = traj_.cols;
+  out.coef.resize(5 * P * 4);
+  for (std::size_t c = 0; c < 5; ++c)
+    for (std::size_t i = 0; i < P; ++i) cubics[c]->piece(i, &out.coef[(c * P + i) * 4]);
+  out.wp_x.resize(n); out.wp_y.resize(n); out.wp_s.resize(n);
+  for (std::size_t j = 0; j < n; ++j) {
+    out.wp_x[j] = traj_(PX, j);
+    out.wp_y[j] = traj_(PY, j);
+    out.wp_s[j] = traj_(DIST_TO_SF_BWD, j);
+  }
+  std::vector<double> gap(n - 1);
+  for (std::size_t j = 0; j + 1 < n; ++j) gap[j] = out.wp_s[j + 1] - out.wp_s[j];
+  std::sort(gap.begin(), gap.end());
+  out.h_bar = gap.size() % 2 ? gap[gap.size() / 2] : (gap[gap.size() / 2 - 1] + gap[gap.size() / 2]) / 2.0;
 }
 
 }  // namespace racing_trajectory

@@ -48,6 +48,9 @@ class NotAKnotCubic {
   NotAKnotCubic() = default;
   NotAKnotCubic(const std::vector<double>& x, const std::vector<double>& y);
   double operator()(double xq, int nu = 0) const;
+  const std::vector<double>& breaks() const { return x_; }
+  // a, b, c, d of piece i:  a + b h + c h^2 + d h^3,  h = x - breaks()[i]
+  void piece(std::size_t i, double out[4]) const { out[0] = a_[i]; out[1] = b_[i]; out[2] = c_[i]; out[3] = d_[i]; }
 
  private:
   std::vector<double> x_, a_, b_, c_, d_;
@@ -78,6 +81,14 @@ class RacingTrajectory {
   // uniform periodic tables for the device (lmpc_track): curvature, bound_left, bound_right, vel at s_j = j L / M
   void to_track_table(std::size_t M, std::vector<double>& curvature, std::vector<double>& bound_left,
                       std::vector<double>& bound_right, std::vector<double>& vel) const;
+
+  // the interpolants as piecewise polynomials for the device (lmpc_spline_track_create): the P + 1 breaks (extended waypoint
+  // abscissae), coef [5][P][4] (x, y, vel, left, right; a, b, c, d per piece), the waypoints and their median spacing
+  struct SplineTrack {
+    double L = 0.0, h_bar = 0.0;
+    std::vector<double> breaks, coef, wp_x, wp_y, wp_s;
+  };
+  void to_spline_track(SplineTrack& out) const;
 
  private:
   double mod(double s) const;

@@ -11,7 +11,8 @@ not-a-knot end conditions -- and derives yaw = atan2(y', x') and the curvature e
 (the division binds to the second product only).  Every interpolant is evaluated at align_abscissa(s, L/2, L)
 (:98), i.e. the abscissa wrapped into [0, L).
 
-The device kernels consume uniform periodic tables (`lmpc_track`); `RacingTrajectory.to_track_table` samples them.
+The solve path consumes uniform periodic tables (`lmpc_track`); `RacingTrajectory.to_track_table` samples them.  The batched
+global <-> Frenet conversions consume the splines themselves (`lmpc_spline_track`); `RacingTrajectory.to_spline_track` exports them.
 The spline here is hand-written (banded not-a-knot system -> piecewise cubics); tests compare it with scipy's
 make_interp_spline, which implements the same published algorithm (oracle/trajectory.py)."""
 from __future__ import annotations
@@ -160,6 +161,17 @@ class RacingTrajectory:
         return s_out, float(np.hypot(x - xo, y - yo) * sign), float(align_yaw(phi, yaw_o) - yaw_o)
 
     # ---- what the device kernels consume ----
+    def to_spline_track(self) -> dict:
+        """The five interpolants as piecewise polynomials (lmpc_spline_track_create, include/lmpc_hip.h): "L", "breaks" [P + 1] (the
+        extended waypoint abscissae), "coef" [5][P][4] (x, y, vel, left, right; a + b h + c h^2 + d h^3 with h = s - breaks[piece]),
+        the waypoints "wp_x", "wp_y", "wp_s" and their median spacing "h_bar"."""
+        cubics = (self._x, self._y, self._vel, self._left, self._right)
+        w = self.table
+        return {"L": self.total_length, "breaks": self._x.x.copy(),
+                "coef": np.stack([np.stack([c.a, c.b, c.c, c.d], axis=1) for c in cubics]),
+                "wp_x": w[:, PX].copy(), "wp_y": w[:, PY].copy(), "wp_s": w[:, DIST_TO_SF_BWD].copy(),
+                "h_bar": float(np.median(np.diff(w[:, DIST_TO_SF_BWD])))}
+
     def to_track_table(self, M: int = 1024) -> dict:
         """Uniform periodic tables (lmpc_track): curvature, signed boundary offsets and speed at s_j = j L / M."""
         s = np.arange(M) * self.total_length / M
