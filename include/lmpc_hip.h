@@ -229,13 +229,20 @@ int lmpc_solve_batch_warm_ss(lmpc_handle* h, int32_t batch, const double* x_ic, 
  * explicit; a support point none of whose candidates is in the new set drops out (the solver renormalises).  An active-set start
  * needs the support RIGHT: in the LMPC experiment this guess is (advance = 1; four repair rounds) for a quarter of the periods, and
  * the rest pay the refused rounds on top of their cold solve -- closed_loop.run_lmpc leaves it off by default.
+ * Both code arrays must come from lmpc_ss_query_idx_batch against the store CURRENTLY set (lmpc_set_safe_set): the codes are
+ * decoded with its lap lengths.  ss_idx_prev is one query older than ss_idx, so no generation is checked; a code that names no row
+ * of the store (-1, a row at or past the store's total, a fourth copy) is read as "no point" -- it carries no weight and receives
+ * none.  The support is read in ascending position, its first eight entries count, and weights that land on one point add in
+ * that order (fp64): the result is reproducible bit for bit.
  * No counterpart upstream: the reference hands the previous weights to OSQP by position.  All pointers DEVICE. */
 int lmpc_shift_lambda_batch(lmpc_handle* h, int32_t batch, const int32_t* ss_idx_prev, const double* lambda_prev, const int32_t* ss_idx,
                             int32_t advance, double* lambda_ref);
 
 /* accepted [batch] (DEVICE, int32): 1 where the most recent warm solve of this batch size on this handle (lmpc_solve_batch_warm,
  * lmpc_solve_batch_warm_ss) returned the active-set attempt's answer, 0 where the cold solve ran (refused attempt, or no warm kernel
- * for the configuration).  Written by the kernel itself (until round 6 callers inferred it from iters <= 4). */
+ * for the configuration).  Written by the kernel itself.  The flags belong to
+ * the LAST solve: any later cold solve through this handle (lmpc_solve_batch, _mixed, _ss_idx, _f32, lmpc_solve_full_dynamics_batch)
+ * clears them, and a `batch` other than the warm solve's -- a smaller one included: there is no prefix of the flags -- gets zeros. */
 int lmpc_get_warm_accepted(lmpc_handle* h, int32_t batch, int32_t* accepted);
 
 /* Mixed precision (BASELINE configs[4]: "mixed fp32/fp64 KKT"): same arguments, layouts and fp64 arrays as
@@ -479,8 +486,10 @@ int lmpc_plant_step_batch(lmpc_handle* h, int32_t batch, const lmpc_track* track
  *                         bound_right, curvatures, vel_ref are updated IN PLACE (they must not alias X_optm / U_optm);
  *   bookkeeping        -- optional accumulators, any of them NULL: distance [B] += abscissa travelled (unwrapped), worst_excess [B]
  *                         = max(itself, excursion of the body beyond the track edge at the new state against the bounds of knot 0),
- *                         n_fail [B] += 1 after a failed solve, *n_accepted += number of cars whose warm start was accepted (the warm kernel's own flag; 0 after a cold solve)
- *                         (status 0 and iters <= 4; needs iters).
+ *                         n_fail [B] += 1 after a failed solve, *n_accepted += number of cars with status 0 whose warm start was
+ *                         accepted (the warm kernel's own flag, lmpc_get_warm_accepted).  It counts only when the last solve on
+ *                         this handle was lmpc_solve_batch_warm / _warm_ss of the same batch size; after any other solve it adds 0
+ *                         (`iters` is no longer read; it must still be non-NULL where n_accepted is given).
  * The same arithmetic as the three entry points it replaces -- bit for bit, except that the last knot of a shifted solution (one model
  * step from the knot before it) may differ by 1 - 2 ulp, the compiler contracting the inlined model differently in the two kernels
  * (tests/test_gpu_loop.py) --; a period of a closed loop is then

@@ -932,8 +932,8 @@ int lmpc_shift_lambda_batch(lmpc_handle* h, int32_t batch, const int32_t* ss_idx
   if (!h->P.learning || h->ss_laps < 1) return fail(h, LMPC_ERR_ARGUMENT, "lmpc_shift_lambda_batch: a learning handle with a safe set stored");
   if (batch == 0) return LMPC_OK;
   HIP_TRY(h, hipSetDevice(h->device));
-  hipLaunchKernelGGL(lmpc_shift_lambda_kernel, dim3((batch + 63) / 64), dim3(64), 0, h->stream, batch, h->P.S, h->ss_laps, h->ss_npts.get(),
-                     h->ss_off.get(), ss_idx_prev, lambda_prev, ss_idx, advance, lambda_ref);
+  hipLaunchKernelGGL(lmpc_shift_lambda_kernel, dim3((batch + 63) / 64), dim3(64), 0, h->stream, batch, h->P.S, h->ss_laps, h->ss_total,
+                     h->ss_npts.get(), h->ss_off.get(), ss_idx_prev, lambda_prev, ss_idx, advance, lambda_ref);
   HIP_TRY(h, hipGetLastError());
   return LMPC_OK;
 }
@@ -973,6 +973,7 @@ int lmpc_solve_batch_f32(lmpc_handle* h, int32_t batch, const float* x_ic, const
   const launch_choice k = choose_kernel(h, SOLVE_F32);
   if (!k.fn) return fail(h, LMPC_ERR_UNSUPPORTED, "no single-precision kernel for this N");
   h->last_precision = LMPC_PRECISION_F32;
+  h->warm_flag_n = 0;  // (a cold solve, like lmpc_solve_batch's: the flags of an earlier warm solve of this batch size no longer describe the last solve)
   int rc = reserve_save(h, (size_t)batch, sizeof(float));
   if (rc == LMPC_OK)
     rc = grow(h, h->ws_f32_cap, (size_t)batch, [&]() -> int {

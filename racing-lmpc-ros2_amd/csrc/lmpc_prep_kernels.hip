@@ -473,9 +473,13 @@ __global__ __launch_bounds__(1024) void lmpc_collect_unverified_kernel(int B, co
 // previous set with weight lam > 0 and code c is looked for in the new set as the sample `advance` steps further along the same
 // lap copy (the plan's terminal state moves forward about one sample per control period: the optimum's support moves with it);
 // where that sample is not among the new neighbours, the point itself.  One thread per problem: the support is <= 6 points.
-__device__ __forceinline__ int lmpc_advance_code(int code, int adv, int n_laps, const int* __restrict__ npts, const int* __restrict__ off) {
+// `total`: rows in the store.  A code whose row lies past it names no point (it used to be read as a sample of the last lap, after
+// O(row / n) turns of the loop below); inside the store jj < n + adv, so the loop ends after at most adv / n + 1 turns.
+__device__ __forceinline__ int lmpc_advance_code(int code, int adv, int n_laps, int total, const int* __restrict__ npts,
+                                                 const int* __restrict__ off) {
   if (code < 0) return -1;
   int row = code >> 2, rep = code & 3, l = 0;
+  if (row >= total) return -1;
   for (int t = 1; t < n_laps; ++t) l = (row >= off[t]) ? t : l;
   int jj = row - off[l] + adv;
   const int n = npts[l];
@@ -486,7 +490,7 @@ __device__ __forceinline__ int lmpc_advance_code(int code, int adv, int n_laps, 
   return rep > 2 ? -1 : ((off[l] + jj) << 2) | rep;
 }
 
-__global__ __launch_bounds__(64) void lmpc_shift_lambda_kernel(int B, int S, int n_laps, const int* __restrict__ npts, const int* __restrict__ off,
+__global__ __launch_bounds__(64) void lmpc_shift_lambda_kernel(int B, int S, int n_laps, int total, const int* __restrict__ npts, const int* __restrict__ off,
                                                                const int* __restrict__ idx_prev, const double* __restrict__ lam_prev,
                                                                const int* __restrict__ idx, int advance, double* __restrict__ lam_ref) {
   const int b = blockIdx.x * 64 + threadIdx.x;
@@ -520,7 +524,7 @@ __global__ __launch_bounds__(64) void lmpc_shift_lambda_kernel(int B, int S, int
   for (int k = 0; k < n; ++k) {
     const int order[3] = {advance, 0, advance + 1};
     for (int t = 0; t < 3; ++t) {
-      const int j = find(lmpc_advance_code(sup_code[k], order[t], n_laps, npts, off));
+      const int j = find(lmpc_advance_code(sup_code[k], order[t], n_laps, total, npts, off));
       if (j < 0) continue;
       double& cell = lam_ref[(size_t)j * B + b];
       if (cell == 0.0) {
