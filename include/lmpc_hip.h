@@ -343,8 +343,11 @@ int lmpc_solve_host_warm_ss(lmpc_handle* h, const double* x_ic, const double* u_
  * for the problem; iters [B] = interior-point iterations summed over the QPs solved while the problem was still moving;
  * sqp_iters [B] = those QPs (steps taken + back-offs); sqp_move [B] = scaled |X_QP - X| of the last QP, the step it
  * proposed whatever part of it the line search took (converged iff <= step_tol); defect [B] =
- * |x_{i+1} - f_d(x_i, u_i)|_inf / scale_x of the iterate.  The first call for a batch size allocates a work area (like lmpc_reserve); synchronises the stream once per
- * QP (it has to know whether any problem is still moving). */
+ * |x_{i+1} - f_d(x_i, u_i)|_inf / scale_x of the iterate returned, after a step and after a back-off alike.  A problem that
+ * never took a step -- its first QP failed -- returns the start unchanged (dU = 0, lambda = 0) with sqp_iters = 1, that QP's
+ * status, sqp_move = +inf (never <= step_tol) and defect = 0: no defect is evaluated for it.  A learning handle needs ss_x and
+ * ss_j (LMPC_ERR_ARGUMENT otherwise, before anything is written).  The first call for a batch size allocates a work area (like
+ * lmpc_reserve); synchronises the stream once per QP (it has to know whether any problem is still moving). */
 int lmpc_solve_full_dynamics_batch(lmpc_handle* h, int32_t batch, const double* x_ic, const double* u_ic, const double* X_ref,
                                    const double* U_ref, const double* T_ref, const double* bound_left,
                                    const double* bound_right, const double* curvatures, const double* vel_ref,

@@ -12,7 +12,7 @@ available, so "the reference's result" is pinned the solver-independent way:
                         NNLS multipliers of qp.kkt_certificate, independent of any solver.
   solve_nlp_dense       an independent dense SQP (dense QPs of oracle/qp.py + the same l1-merit backtracking) from the
                         same start, to compare trajectories (the NLP is non-convex: the same start is part of "the same
-                        problem").
+                        problem").  Tracking and, given the safe set, learning.
 PARITY UNPINNED like the rest of the oracle: no reference-held outputs exist for this path.
 """
 from __future__ import annotations
@@ -54,8 +54,15 @@ def nlp_kkt_certificate(cfg: MPCConfig, veh: Vehicle, pr: dict, X, U, dU, sigma=
 
 
 def merit_cost(qp: Q.DenseQP, y: np.ndarray) -> float:
-    """The QP's cost at y with the boundary slack eliminated (sigma* = the largest boundary violation)."""
+    """The QP's cost at y with the boundary slack eliminated (sigma* = the largest boundary violation) and, for the learning
+    problem, the hull residual too: eps = x_T - SS lambda, read off the rows  x_T - eps - SS lambda = 0  (racing_mpc.cpp:496)."""
     y = y.copy()
+    if qp.S:
+        y[qp.ieps: qp.ieps + Q.NX] = 0.0
+        for k in range(Q.NX):
+            row = np.nonzero((qp.A[:, qp.ieps + k] != 0.0) & (qp.A[:, qp.ix(qp.N - 1, k)] != 0.0))[0]
+            assert row.size == 1
+            y[qp.ieps + k] = (qp.A[row[0]] @ y - qp.b[row[0]]) / -qp.A[row[0], qp.ieps + k]
     if qp.has_sigma:
         y[qp.isig] = 0.0
         rows = (qp.C[:, qp.isig] != 0.0) & ((qp.C != 0.0).sum(axis=1) == 2)
@@ -63,27 +70,33 @@ def merit_cost(qp: Q.DenseQP, y: np.ndarray) -> float:
     return qp.objective(y)
 
 
-def solve_nlp_dense(cfg: MPCConfig, veh: Vehicle, pr: dict, max_sqp: int = 40, tol: float = 1e-9):
-    """Dense SQP from (X_ref, U_ref), dU = 0: returns (X, U, dU, sigma, info)."""
+def solve_nlp_dense(cfg: MPCConfig, veh: Vehicle, pr: dict, max_sqp: int = 40, tol: float = 1e-9, ss_x=None, ss_j=None):
+    """Dense SQP from (X_ref, U_ref), dU = 0: returns (X, U, dU, sigma, info).  The learning problem takes its safe set
+    (ss_x [6][S], ss_j [S]), starts at lambda = 0, carries lambda through the step and the back-off and returns it as
+    info["lam"] (the hull residual is eliminated, eps = x_T - SS lambda: merit_cost)."""
     N = cfg.N
     X, U = np.array(pr["X_ref"], dtype=float), np.array(pr["U_ref"], dtype=float)
     dU, sigma, nu = np.zeros((2, N - 1)), 0.0, 1e-3
+    lam = np.zeros(np.asarray(ss_x).shape[1]) if cfg.learning else None
+    hull = (lambda X_, lam_: X_[:, -1] - np.asarray(ss_x, dtype=float) @ lam_) if cfg.learning else (lambda X_, lam_: None)
     info = {"status": 1, "sqp_iters": 0}
     prev, backoffs, move = None, 0, np.inf
     for it in range(max_sqp):
-        qp = Q.build_qp(cfg, veh, _at(pr, X, U))
+        qp = Q.build_qp(cfg, veh, _at(pr, X, U), ss_x, ss_j)
         y, qi = Q.solve_dense(qp)
         info["sqp_iters"] = it + 1
         if qi["status"] != 0:
             if prev is not None and backoffs < 6:   # the step outran its linearisation: half way back, linearise again
                 backoffs += 1
                 X, U, dU, sigma = 0.5 * (X + prev[0]), 0.5 * (U + prev[1]), 0.5 * (dU + prev[2]), 0.5 * (sigma + prev[3])
+                if cfg.learning:
+                    lam = 0.5 * (lam + prev[4])
                 continue
             info["status"] = 2
             break
         backoffs = 0
         o = qp.split(y)
-        y0 = Q.pack(qp, X, U, dU, sigma=sigma)
+        y0 = Q.pack(qp, X, U, dU, sigma=sigma, lam=lam, eps=hull(X, lam))
         a = 1.0
         if it > 0:
             c0 = np.abs(defect(veh, pr, X, U)).sum()
@@ -98,11 +111,15 @@ def solve_nlp_dense(cfg: MPCConfig, veh: Vehicle, pr: dict, max_sqp: int = 40, t
                     break
                 a *= 0.5
         move = np.abs((o["X_optm"] - X) / SCALE_X[:, None]).max()   # the step proposed, whatever part of it is taken
-        prev = (X, U, dU, sigma)
+        prev = (X, U, dU, sigma, lam)
         X, U, dU = X + a * (o["X_optm"] - X), U + a * (o["U_optm"] - U), dU + a * (o["dU_optm"] - dU)
+        if cfg.learning:
+            lam = lam + a * (o["convex_combi_optm"] - lam)
         sigma = sigma + a * (o.get("sigma", 0.0) - sigma)
         if move <= tol:
             info["status"] = 0
             break
     info["move"] = move
+    if cfg.learning:
+        info["lam"] = lam
     return X, U, dU, sigma, info

@@ -508,7 +508,7 @@ class Solver:
         learning = bool(self.config["learning"])
         if learning:
             out["convex_combi_optm"] = torch.zeros((int(self.config["num_ss_pts"]), B), dtype=torch.float64, **kw)
-            ss_x, ss_j = self._t(ss_x), self._t(ss_j)
+            ss_x, ss_j = (None if t is None else self._t(t) for t in (ss_x, ss_j))   # (None: the library refuses the call)
         rc = self.lib.lmpc_solve_full_dynamics_batch(
             self._h, C.c_int32(B), *[_ptr(a[k]) for k in ("x_ic", "u_ic", "X_ref", "U_ref", "T_ref", "bound_left",
                                                            "bound_right", "curvatures", "vel_ref")],
@@ -518,6 +518,30 @@ class Solver:
             _ptr(out["sqp_iters"]), _ptr(out["sqp_move"]), _ptr(out["defect"]))
         self._check(rc, "lmpc_solve_full_dynamics_batch")
         out["_inputs_keepalive"] = a
+        return out
+
+    def solve_full_dynamics_host(self, inp: dict, b: int = 0, max_sqp: int = 10, tol: float = 1e-9, ss_x=None, ss_j=None) -> dict:
+        """lmpc_solve_full_dynamics_host on problem `b` of batched numpy inputs ([field][knot][batch], ss_x [6][S][batch]): ONE
+        problem through HOST arrays in the reference's column-major layout, as the facade calls it.  Returns numpy results in the
+        batch = 1 device layout (X_optm [6][N][1], ...), so that they compare with a row of solve_full_dynamics."""
+        import numpy as np
+
+        N, S = self.N, int(self.config["num_ss_pts"]) if bool(self.config["learning"]) else 0
+        col = lambda a: np.ascontiguousarray(np.asarray(a, dtype=np.float64)[..., b].T)      # [field][knot] -> knot-major
+        a = [col(inp[k]) for k in ("x_ic", "u_ic", "X_ref", "U_ref", "T_ref", "bound_left", "bound_right", "curvatures", "vel_ref")]
+        sx, sj = (None if t is None else col(t) for t in (ss_x, ss_j))
+        X, U, dU, lam = np.zeros((N, 6)), np.zeros((N - 1, 2)), np.zeros((N - 1, 2)), np.zeros(max(S, 1))
+        ints, dbl = np.zeros(3, dtype=np.int32), np.zeros(2)
+        p = lambda t, off=0: C.c_void_p(None if t is None else t.ctypes.data + off * t.itemsize)
+        rc = self.lib.lmpc_solve_full_dynamics_host(
+            self._h, *[p(t) for t in a], C.c_double(float(inp.get("L", 0.0))), p(sx), p(sj), C.c_int32(int(max_sqp)), C.c_double(float(tol)),
+            p(X), p(U), p(dU), p(lam if S else None), p(ints), p(ints, 1), p(ints, 2), p(dbl), p(dbl, 1))
+        self._check(rc, "lmpc_solve_full_dynamics_host")
+        out = {"X_optm": X.T[:, :, None].copy(), "U_optm": U.T[:, :, None].copy(), "dU_optm": dU.T[:, :, None].copy(),
+               "status": ints[0:1].copy(), "iters": ints[1:2].copy(), "sqp_iters": ints[2:3].copy(), "sqp_move": dbl[0:1].copy(),
+               "defect": dbl[1:2].copy()}
+        if S:
+            out["convex_combi_optm"] = lam[:, None].copy()
         return out
 
     # ---- safe set (safe_set.cpp:116-180) ----

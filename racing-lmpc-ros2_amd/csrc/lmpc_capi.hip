@@ -1004,6 +1004,8 @@ int lmpc_solve_full_dynamics_batch(lmpc_handle* h, int32_t batch, const double* 
     return fail(h, LMPC_ERR_ARGUMENT, "lmpc_solve_full_dynamics_batch: null pointer or negative batch");
   if (max_sqp < 1) return fail(h, LMPC_ERR_ARGUMENT, "lmpc_solve_full_dynamics_batch: max_sqp < 1");
   if (h->P.learning && !convex_combi_optm) return fail(h, LMPC_ERR_ARGUMENT, "learning=1 needs convex_combi_optm");
+  // (solve_batch refuses this too, but only after the outputs below have been overwritten with the start)
+  if (h->P.learning && (!ss_x || !ss_j)) return fail(h, LMPC_ERR_ARGUMENT, "lmpc_solve_full_dynamics_batch: learning=1 needs ss_x and ss_j");
   if (batch == 0) return LMPC_OK;
   HIP_TRY(h, hipSetDevice(h->device));
   const size_t B = (size_t)batch, N = (size_t)h->P.N, NS = N - 1, S = (size_t)h->P.S;

@@ -20,7 +20,8 @@
 //   back-off when the QP about the new iterate is infeasible (its linearised dynamics cannot meet the hard boxes: the step
 //            went too far for the linearisation that proposed it) the iterate is moved half way back to the previous one
 //            and linearised again, up to LMPC_SQP_BACKOFF times in a row -- the role of IPOPT's restoration phase upstream.
-//            Only after that does the problem stop with the QP's status.
+//            Only after that does the problem stop with the QP's status.  The defect reported follows the iterate: it is
+//            evaluated again at the midpoint.
 //   move     the convergence measure is the size of the QP's own step |w_QP - w| (scaled), not of the shortened step
 //            taken: a collapsed line search cannot pass for convergence.
 #include <hip/hip_runtime.h>
@@ -48,7 +49,7 @@ struct lmpc_sqp_arrays {
   int* status;     // status of the last QP taken into the iterate (out)
   int* sqp_iters;  // QPs solved for this problem: steps taken + back-offs (in/out)
   double* move;    // largest scaled |X_QP - X| of the last QP (out): the step proposed, whatever part of it was taken
-  double* defect;  // |c|_inf of the iterate after the step (out)
+  double* defect;  // |c|_inf of the iterate after the step or the back-off (out)
   int* n_active;   // device counter of problems still active after this step (atomic)
 };
 
@@ -60,6 +61,7 @@ struct sqp_point {  // w(a) = cur + a (q - cur), read on the fly
   double a;
   __device__ double blend(const double* cur, const double* q, size_t e) const {
     const double c = cur[e * B + b];
+    if (a == 0.0) return c;  // the iterate itself: the arrays of a QP that failed are not read
     return c + a * (q[e * B + b] - c);
   }
 };
@@ -131,6 +133,9 @@ __global__ __launch_bounds__(64) void lmpc_sqp_linesearch_kernel(lmpc_params P, 
         A.dU[(size_t)e * B + b] = 0.5 * (A.dU[(size_t)e * B + b] + A.dUp[(size_t)e * B + b]);
       }
       for (int j = 0; j < S; ++j) A.lam[(size_t)j * B + b] = 0.5 * (A.lam[(size_t)j * B + b] + A.lamp[(size_t)j * B + b]);
+      double Jm, cm, cim;  // the defect reported is the returned iterate's: the midpoint's now
+      sqp_eval(P, A, B, b, 0.0, Jm, cm, cim);
+      A.defect[b] = cim;
       atomicAdd(A.n_active, 1);
       return;
     }
