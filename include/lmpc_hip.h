@@ -406,7 +406,8 @@ typedef struct lmpc_regression_spec {
 
 /* HOST pointers, laps concatenated as in lmpc_set_safe_set: x [n][6], u [n][2], k [n] (curvature), t [n] (time
  * stamps) -- the lap_.x/u/k/t of SSTrajectory.  n_laps = 0 or spec = NULL switches the regression off.  While it is
- * on, lmpc_solve_batch applies it between its linearisation and its QP kernel. */
+ * on, lmpc_solve_batch applies it between its linearisation and its QP kernel.  With laps it is refused (LMPC_ERR_ARGUMENT)
+ * while lmpc_fleet_ss_set_regression is in effect. */
 int lmpc_set_regression_laps(lmpc_handle* h, int32_t n_laps, const int32_t* n_pts, const double* x, const double* u,
                              const double* k, const double* t, const lmpc_regression_spec* spec);
 
@@ -583,7 +584,8 @@ int lmpc_last_kernel_ms(lmpc_handle* h, float* linearize_ms, float* solve_ms);
  * by one (lap_count and the duration are kept as for any lap).  Nothing is ever written outside a car's slots.
  * Every call names the store's own batch (LMPC_ERR_ARGUMENT otherwise, and without a store).  The store serves the array form of the
  * safe set only: the by-reference codes (lmpc_ss_query_idx_batch, lmpc_solve_batch_ss_idx, lmpc_solve_batch_warm_ss with ss_idx,
- * lmpc_shift_lambda_batch) name rows of the shared store and have no fleet form; lmpc_set_regression_laps stays one store per handle. */
+ * lmpc_shift_lambda_batch) name rows of the shared store and have no fleet form.  The error-dynamics regression has one:
+ * lmpc_fleet_ss_set_regression / lmpc_fleet_ss_regress_batch below (lmpc_set_regression_laps stays one store per handle). */
 int lmpc_fleet_ss_create(lmpc_handle* h, int32_t batch, int32_t max_pts_per_lap);
 int lmpc_fleet_ss_destroy(lmpc_handle* h);
 int lmpc_fleet_ss_reset(lmpc_handle* h);
@@ -621,6 +623,36 @@ int lmpc_fleet_ss_get_laps(lmpc_handle* h, int32_t car, int32_t* n_laps, int32_t
  * minus t of the lap's first sample, 0 before the first.  Asynchronous on the handle's stream. */
 int lmpc_fleet_ss_stats(lmpc_handle* h, int32_t batch, int32_t* laps_in_ring, int32_t* lap_count, int32_t* n_dropped,
                         double* last_lap_time);
+
+/* Per-car error-dynamics regression: SafeSetManager::query(RegQuery) (safe_set.cpp:182-245) as B controllers call it, each on the
+ * laps of its OWN SafeSetManager -- lmpc_set_regression_laps / lmpc_regress_batch above with query (b, i) run against the closed laps
+ * in car b's ring at the time of each call.  Same spec, same arithmetic, same two sign conventions (the comment at
+ * lmpc_regression_spec); the weights are always formed from sum (z - q)^2.  Only closed laps in the ring count: not the open lap
+ * being recorded, not a lap dropped for its length, not a lap the ring has evicted.
+ * lmpc_fleet_ss_set_regression uploads NO data.  It validates the spec exactly as lmpc_set_regression_laps does ((features, rows)
+ * other than (5, 3) and (8, 6): LMPC_ERR_UNSUPPORTED; an index out of range or dist_max <= 0: LMPC_ERR_ARGUMENT), needs a fleet store
+ * (LMPC_ERR_ARGUMENT without one) and allocates, per car, a packed table of max_lap_stored x (max_pts_per_lap - 1) samples rounded
+ * up to four, 8 (features + rows + 1) bytes each -- 72 for (5, 3), 120 for (8, 6); 4096 cars x 5 x 1023 x 72: 1.5 GB;
+ * lmpc_fleet_ss_bytes includes it -- and nothing later allocates.  The tables are filled on the device, in front of each use, for
+ * the cars whose ring has changed since their last fill (a lap closed or was loaded: lap_count moved on); the caller does nothing
+ * for that and no call reads the device.  Calling it again with another spec re-validates and refills (it synchronises the
+ * handle's stream only when the table's size changes).  spec = NULL switches it off and frees the table, as do lmpc_fleet_ss_create
+ * (which replaces the store) and lmpc_fleet_ss_destroy.  It is refused (LMPC_ERR_ARGUMENT) while lmpc_set_regression_laps is in
+ * effect, and lmpc_set_regression_laps with laps is refused while this is: a handle corrects its model from one source.
+ * While it is on: every fp64 / mixed batched solve (lmpc_solve_batch, _mixed, _warm, _warm_ss, _ss_idx, the QPs of
+ * lmpc_solve_full_dynamics_batch) applies it between its linearisation and its QP kernel, where lmpc_set_regression_laps applies
+ * the shared one, and must name the store's batch -- another batch is LMPC_ERR_ARGUMENT before anything is written; the
+ * single-problem host entries (lmpc_solve_host*, lmpc_solve_full_dynamics_host) are a batch of one and follow the same rule;
+ * lmpc_solve_batch_f32 returns LMPC_ERR_UNSUPPORTED. */
+int lmpc_fleet_ss_set_regression(lmpc_handle* h, const lmpc_regression_spec* spec);
+
+/* lmpc_regress_batch with query (b, i) run against car b's own ring: adds RegResult{A, B, C} onto A [6][6][N-1][B],
+ * Bm [6][2][N-1][B], g [6][N-1][B] (the arrays of lmpc_linearize_batch; DEVICE pointers), linearisation points X_ref [6][N][B],
+ * U_ref [2][N-1][B].  batch must be the store's.  A car without a closed lap, and a query with no sample inside the bandwidth,
+ * leave their entries bit-identical (safe_set.cpp:207-210).  Two launches, asynchronous on the handle's stream, no host round trip
+ * and no allocation (legal inside a captured control period). */
+int lmpc_fleet_ss_regress_batch(lmpc_handle* h, int32_t batch, const double* X_ref, const double* U_ref, double* A, double* Bm,
+                                double* g);
 
 /* Spline track: RacingTrajectory's interpolants on the device (racing_trajectory.cpp:25-120) and the two conversions built on them.
  * The five interpolating not-a-knot cubics -- x, y, speed, left and right boundary offset over the abscissa of the waypoints, closed by

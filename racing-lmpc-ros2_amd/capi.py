@@ -27,6 +27,7 @@ _ABI_SYMBOLS = ("lmpc_create", "lmpc_destroy", "lmpc_last_error", "lmpc_set_stre
                 "lmpc_get_warm_accepted", "lmpc_set_waves_per_problem",
                 "lmpc_fleet_ss_create", "lmpc_fleet_ss_destroy", "lmpc_fleet_ss_reset", "lmpc_fleet_ss_bytes", "lmpc_fleet_ss_record_batch",
                 "lmpc_fleet_ss_query_batch", "lmpc_fleet_ss_load", "lmpc_fleet_ss_get_laps", "lmpc_fleet_ss_stats",
+                "lmpc_fleet_ss_set_regression", "lmpc_fleet_ss_regress_batch",
                 "lmpc_spline_track_create", "lmpc_spline_track_destroy", "lmpc_spline_track_tabulate", "lmpc_track_sample_batch",
                 "lmpc_global_to_frenet_batch", "lmpc_frenet_to_global_batch")
 
@@ -718,6 +719,33 @@ class Solver:
                                           _ptr(out.get("n_dropped")), _ptr(out.get("last_lap_time")))
         self._check(rc, "lmpc_fleet_ss_stats")
         return out
+
+    # ---- per-car error-dynamics regression on the fleet safe set (safe_set.cpp:182-245, one SafeSetManager per car) ----
+    def fleet_ss_set_regression(self, in_state=(3, 4, 5), in_ctrl=(0, 1), out_rows=(3, 4, 5), dist_max: float = 1.0,
+                                as_written: bool = False, off: bool = False):
+        """lmpc_fleet_ss_set_regression: from now on every fp64 / mixed solve of this solver (and fleet_ss_regress) corrects problem
+        b's model by the regression on car b's OWN closed laps in the fleet store, as they are at each call; nothing is uploaded.
+        in_state=None or off=True switches it off.  as_written: the reference's literal signs (set_regression_laps)."""
+        self.use_current_stream()
+        if off or in_state is None:
+            self._check(self.lib.lmpc_fleet_ss_set_regression(self._h, None), "lmpc_fleet_ss_set_regression")
+            return
+        spec = CRegressionSpec()
+        spec.n_out, spec.n_in_state, spec.n_in_ctrl, spec.dist_max = len(out_rows), len(in_state), len(in_ctrl), float(dist_max)
+        spec.out[:len(out_rows)] = list(out_rows)
+        spec.in_state[:len(in_state)] = list(in_state)
+        spec.in_ctrl[:len(in_ctrl)] = list(in_ctrl)
+        spec.as_written = 1 if as_written else 0
+        self._check(self.lib.lmpc_fleet_ss_set_regression(self._h, C.byref(spec)), "lmpc_fleet_ss_set_regression")
+
+    def fleet_ss_regress(self, inp: dict, A, Bm, g):
+        """lmpc_fleet_ss_regress_batch: regress() with problem b run against car b's own ring -- adds RegResult onto A [6,6,N-1,B],
+        Bm [6,2,N-1,B], g [6,N-1,B] (device tensors, in place).  Asynchronous."""
+        self.use_current_stream()
+        X, U = self._t(inp["X_ref"]), self._t(inp["U_ref"])
+        rc = self.lib.lmpc_fleet_ss_regress_batch(self._h, C.c_int32(X.shape[2]), _ptr(X), _ptr(U), _ptr(A), _ptr(Bm), _ptr(g))
+        self._check(rc, "lmpc_fleet_ss_regress_batch")
+        return A, Bm, g
 
     # ---- spline track: the interpolants on the device, global <-> Frenet (racing_trajectory.cpp:25-236; include/lmpc_hip.h) ----
     def spline_track(self, tr) -> SplineTrack:

@@ -284,7 +284,7 @@ def run_lmpc(tracker, learner, track: dict, x0, u0, warm_laps: int = 2, learn_la
 
 def run_lmpc_fleet(tracker, learner, track: dict, x0, u0, warm_laps: int = 2, learn_laps: int = 4, dt: float = 0.025,
                    n_sub: int = 2, warm_speed_scale: float = 0.7, max_steps: int = 20000, max_pts_per_lap: int = 1024,
-                   record_trace: bool = False):
+                   record_trace: bool = False, regression: dict | None = None, plant=None):
     """run_lmpc with every car learning from ITS OWN laps: the fleet safe set on `learner` (lmpc_fleet_ss_*: one recorder and one
     ring of max_lap_stored laps per car, on the device) replaces the host recorder of car 0 and the shared store.  Per period, in
     run_lmpc's order: record (x, u_prev, curvature at s, t) for all cars, query every learning car's own ring, solve, plant step,
@@ -299,7 +299,12 @@ def run_lmpc_fleet(tracker, learner, track: dict, x0, u0, warm_laps: int = 2, le
 
     Returns "lap_times" / "lap_kind": per car the list of its closed laps in order (at most warm_laps + learn_laps + 8 are kept),
     device tensors "worst_excess", "n_fail" (failures of the controller the car was driving with), "n_dropped", "laps_in_ring", and
-    "steps", "x"; record_trace=True adds "trace", the (x, u, k, t) handed to the recorder each period."""
+    "steps", "x"; record_trace=True adds "trace", the (x, u, k, t) handed to the recorder each period.
+
+    regression (a dict of Solver.fleet_ss_set_regression's keyword arguments): the learning controller also corrects each car's model
+    by the error-dynamics regression on that car's own closed laps (it is switched on on `learner`, and stays on after the run).
+    plant (a Solver): its plant_step drives the cars instead of the controllers' -- a plant whose vehicle differs from the
+    controllers' gives the regression something to learn."""
     import numpy as np
     import torch
 
@@ -308,6 +313,8 @@ def run_lmpc_fleet(tracker, learner, track: dict, x0, u0, warm_laps: int = 2, le
     B = x0.shape[1]
     dev = x0.device
     learner.fleet_ss_create(B, max_pts_per_lap)
+    if regression is not None:
+        learner.fleet_ss_set_regression(**regression)
     x, u_prev = x0.clone(), u0.clone()
     half_b = float(tracker.vehicle["b"]) / 2.0
     worst_excess = torch.zeros(B, dtype=torch.float64, device=dev)
@@ -388,7 +395,7 @@ def run_lmpc_fleet(tracker, learner, track: dict, x0, u0, warm_laps: int = 2, le
         ok = out["status"] == 0
         n_fail += (~ok).to(torch.int64)
         u_apply = torch.where(ok[None, :], out["U_optm"][:, 0, :], inp["U_ref"][:, 0, :]).contiguous()
-        (learner if every else tracker).plant_step(trk, x, u_apply, dt / n_sub, n_sub)
+        (plant if plant is not None else learner if every else tracker).plant_step(trk, x, u_apply, dt / n_sub, n_sub)
         exc = torch.maximum(x[1] + half_b - inp["bound_left"][0], inp["bound_right"][0] - (x[1] - half_b))
         worst_excess = torch.maximum(worst_excess, exc)
         u_prev = u_apply

@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "lmpc_device.h"
+#include "lmpc_fleet_reg.h"
 #include "lmpc_fleet_ss.h"
 
 namespace {
@@ -111,6 +112,13 @@ struct __attribute__((visibility("hidden"))) lmpc_handle {  // (its members are 
   size_t fleet_meta_n = 0, fleet_metad_n = 0;
   int64_t fleet_bytes = 0;
   double fleet_L = 0.0;  // total_length of the last record / load call: what the query unrolls the laps by
+  // per-car regression on the fleet store (lmpc_fleet_ss_set_regression): csrc/lmpc_fleet_reg.h
+  bool freg_on = false;
+  lmpc_regression_spec freg_spec{};
+  lmpc_fleet_reg_table freg{};  // raw copies of the two owners below, as the kernels take them
+  dev_buf<double> freg_tab;     // [fleet.B][freg.cap][NF + NOUT + 1]
+  dev_buf<int> freg_meta;       // nrow [fleet.B] | stamp [fleet.B]
+  int64_t freg_bytes = 0;
   // staging for the single-problem host entry points (lmpc_solve_host, lmpc_ss_query_host): device buffers and PINNED
   // host mirrors, all sized and allocated by lmpc_create -- the per-step path of one controller allocates nothing
   dev_buf<double> stage_dev;
@@ -403,6 +411,35 @@ int launch_regress(lmpc_handle* h, int batch, const double* X_ref, const double*
   return LMPC_OK;
 }
 
+// the per-car regression (lmpc_fleet_ss_set_regression is in effect): pack what changed, then one wavefront per (car, 64 stages)
+int launch_fleet_regress(lmpc_handle* h, bool ws, const double* X_ref, const double* U_ref, double* A, double* Bm, double* g) {
+  HIP_TRY(h, lmpc_fleet_reg_launch(h->stream, h->fleet, h->P.veh, h->freg_spec, h->freg, h->P.N, ws, X_ref, U_ref, A, Bm, g));
+  return LMPC_OK;
+}
+
+// what lmpc_fleet_ss_set_regression asks of a solve: the store's own batch (query (b, i) runs against car b's laps)
+int fleet_reg_batch_check(lmpc_handle* h, int batch, const char* who) {
+  if (!h->freg_on || batch == h->fleet.B) return LMPC_OK;
+  return fail(h, LMPC_ERR_ARGUMENT, std::string(who) + ": the per-car regression is on (lmpc_fleet_ss_set_regression) and batch " +
+                                        std::to_string(batch) + " is not the fleet store's " + std::to_string(h->fleet.B));
+}
+
+// every stamp stale, on the stream: the next regression packs every car again
+int fleet_reg_invalidate(lmpc_handle* h) {
+  if (h->freg_on) HIP_TRY(h, hipMemsetAsync(h->freg.stamp, 0xff, (size_t)h->fleet.B * sizeof(int), h->stream));
+  return LMPC_OK;
+}
+
+// off, and its table freed (the stream is drained first: a launch may still read it)
+void fleet_reg_off(lmpc_handle* h) {
+  if (h->freg_tab.get() || h->freg_meta.get()) (void)hipStreamSynchronize(h->stream);
+  h->freg_tab.release();
+  h->freg_meta.release();
+  h->freg = lmpc_fleet_reg_table{};
+  h->freg_on = false;
+  h->freg_bytes = 0;
+}
+
 // the polish's save area for `batch` problems of `elem`-byte values: the single-precision entry needs nothing else of
 // lmpc_reserve (no fp64 workspace, no list), and half the bytes
 int reserve_save(lmpc_handle* h, size_t batch, size_t elem) {
@@ -432,6 +469,7 @@ int solve_batch(lmpc_handle* h, solve_args<> a) {
   if (a.B < 0 || !a.x_ic || !a.u_ic || !a.X_ref || !a.U_ref || !a.T_ref || !a.bl || !a.br || !a.curv || !a.vref || !a.X || !a.U ||
       !a.dU || !a.status || !a.iters)
     return fail(h, LMPC_ERR_ARGUMENT, "lmpc_solve_batch: null pointer or negative batch");
+  if (const int rc = fleet_reg_batch_check(h, a.B, "lmpc_solve_batch")) return rc;
   // A configuration the mixed entry has no kernel for (the learning problem at N >= 24, the hard hull equality) is solved in fp64
   // (round 6, VERDICT r5 item 7 / weak 10: it was LMPC_ERR_UNSUPPORTED, and a caller iterating over horizons had to special-case a
   // valid reference configuration); lmpc_last_solve_precision tells the caller which it was.
@@ -451,6 +489,10 @@ int solve_batch(lmpc_handle* h, solve_args<> a) {
   if (rc != LMPC_OK) return rc;
   if (h->reg_on) {  // error-dynamics regression onto the workspace (safe_set.cpp:182-245)
     rc = launch_regress<true>(h, a.B, a.X_ref, a.U_ref, h->ws.get(), nullptr, nullptr);
+    if (rc != LMPC_OK) return rc;
+  }
+  if (h->freg_on) {  // the same against each car's own laps (B controllers, B SafeSetManagers)
+    rc = launch_fleet_regress(h, true, a.X_ref, a.U_ref, h->ws.get(), nullptr, nullptr);
     if (rc != LMPC_OK) return rc;
   }
   if (h->timing) HIP_TRY(h, hipEventRecord(h->ev[1], h->stream));
@@ -502,6 +544,7 @@ int solve_host(lmpc_handle* h, const solve_args<>& r) {
   if (!r.x_ic || !r.u_ic || !r.X_ref || !r.U_ref || !r.T_ref || !r.bl || !r.br || !r.curv || !r.vref || !r.X || !r.U || !r.dU ||
       !r.status || !r.iters)
     return fail(h, LMPC_ERR_ARGUMENT, "lmpc_solve_host: null pointer");
+  if (const int rc = fleet_reg_batch_check(h, 1, "lmpc_solve_host")) return rc;
   const int N = h->P.N, NS = N - 1, S = h->P.S;
   // staging layout (doubles): inputs then outputs, each in the batch = 1 device layout
   const size_t o_x = 0, o_u = 6, o_X = 8, o_U = o_X + 6 * N, o_T = o_U + 2 * NS, o_bl = o_T + NS, o_br = o_bl + N,
@@ -968,6 +1011,7 @@ int lmpc_solve_batch_f32(lmpc_handle* h, int32_t batch, const float* x_ic, const
     return fail(h, LMPC_ERR_ARGUMENT, "lmpc_solve_batch_f32: null pointer or negative batch");
   if (h->P.learning) return fail(h, LMPC_ERR_UNSUPPORTED, "single precision is built for the tracking problem only");
   if (h->reg_on) return fail(h, LMPC_ERR_UNSUPPORTED, "the error-dynamics regression is applied in double precision only");
+  if (h->freg_on) return fail(h, LMPC_ERR_UNSUPPORTED, "the per-car error-dynamics regression is applied in double precision only");
   if (batch == 0) return LMPC_OK;
   HIP_TRY(h, hipSetDevice(h->device));
   const launch_choice k = choose_kernel(h, SOLVE_F32);
@@ -1006,6 +1050,7 @@ int lmpc_solve_full_dynamics_batch(lmpc_handle* h, int32_t batch, const double* 
   if (h->P.learning && !convex_combi_optm) return fail(h, LMPC_ERR_ARGUMENT, "learning=1 needs convex_combi_optm");
   // (solve_batch refuses this too, but only after the outputs below have been overwritten with the start)
   if (h->P.learning && (!ss_x || !ss_j)) return fail(h, LMPC_ERR_ARGUMENT, "lmpc_solve_full_dynamics_batch: learning=1 needs ss_x and ss_j");
+  if (const int rc = fleet_reg_batch_check(h, batch, "lmpc_solve_full_dynamics_batch")) return rc;
   if (batch == 0) return LMPC_OK;
   HIP_TRY(h, hipSetDevice(h->device));
   const size_t B = (size_t)batch, N = (size_t)h->P.N, NS = N - 1, S = (size_t)h->P.S;
@@ -1306,6 +1351,8 @@ int lmpc_set_regression_laps(lmpc_handle* h, int32_t n_laps, const int32_t* n_pt
   h->reg_on = false;
   h->reg_total = 0;
   if (n_laps == 0 || !spec) return LMPC_OK;
+  if (h->freg_on)
+    return fail(h, LMPC_ERR_ARGUMENT, "lmpc_set_regression_laps: the per-car regression is on (lmpc_fleet_ss_set_regression); switch it off first");
   if (n_laps < 0 || !n_pts || !x || !u || !k || !t) return fail(h, LMPC_ERR_ARGUMENT, "lmpc_set_regression_laps: bad argument");
   const int nf = spec->n_in_state + spec->n_in_ctrl;
   if (!((nf == 5 && spec->n_out == 3) || (nf == 8 && spec->n_out == 6)) || spec->n_in_state < 1 || spec->n_in_state > 6 ||
@@ -1429,6 +1476,7 @@ int lmpc_fleet_ss_destroy(lmpc_handle* h) {
   if (!h->fleet.B) return LMPC_OK;
   (void)hipSetDevice(h->device);
   (void)hipStreamSynchronize(h->stream);
+  fleet_reg_off(h);  // its table is sized by this store
   h->fleet_key.release();
   h->fleet_xr.release();
   h->fleet_aux.release();
@@ -1447,7 +1495,7 @@ int lmpc_fleet_ss_reset(lmpc_handle* h) {
   HIP_TRY(h, hipSetDevice(h->device));
   HIP_TRY(h, hipMemsetAsync(h->fleet_meta.get(), 0, h->fleet_meta_n * sizeof(int), h->stream));
   HIP_TRY(h, hipMemsetAsync(h->fleet_metad.get(), 0, h->fleet_metad_n * sizeof(double), h->stream));
-  return LMPC_OK;
+  return fleet_reg_invalidate(h);  // lap_count starts again at 0: a stamp must not meet it
 }
 
 int lmpc_fleet_ss_create(lmpc_handle* h, int32_t batch, int32_t max_pts_per_lap) {
@@ -1509,7 +1557,7 @@ int lmpc_fleet_ss_create(lmpc_handle* h, int32_t batch, int32_t max_pts_per_lap)
 
 int lmpc_fleet_ss_bytes(const lmpc_handle* h, int64_t* bytes) {
   if (!h || !bytes) return LMPC_ERR_ARGUMENT;
-  *bytes = h->fleet_bytes;
+  *bytes = h->fleet_bytes + h->freg_bytes;
   return LMPC_OK;
 }
 
@@ -1598,6 +1646,7 @@ int lmpc_fleet_ss_load(lmpc_handle* h, int32_t car, int32_t n_laps, const int32_
   hipLaunchKernelGGL(lmpc_fleet_ss_load_kernel, dim3(car < 0 ? h->fleet.B : 1), dim3(256), 0, h->stream, h->fleet, (int)car, nl, devi,
                      devi + nl, dx, du, dk, dt);
   LOAD_TRY(hipGetLastError());
+  if (const int rc = fleet_reg_invalidate(h)) return rc;
   LOAD_TRY(hipStreamSynchronize(h->stream));
   if (first > 0) {  // SafeSetRecorder::load counts every lap it adds (safe_set.cpp:270)
     // (the laps that did not fit the ring were added and pushed out again upstream: they count)
@@ -1656,6 +1705,69 @@ int lmpc_fleet_ss_get_laps(lmpc_handle* h, int32_t car, int32_t* n_laps, int32_t
     }
   }
   return LMPC_OK;
+}
+
+// ---- per-car error-dynamics regression on the fleet store (csrc/lmpc_fleet_reg.h, csrc/lmpc_fleet_reg_kernel.hip) ----
+int lmpc_fleet_ss_set_regression(lmpc_handle* h, const lmpc_regression_spec* spec) {
+  if (!h) return LMPC_ERR_ARGUMENT;
+  if (!spec) {
+    (void)hipSetDevice(h->device);
+    fleet_reg_off(h);
+    return LMPC_OK;
+  }
+  if (!h->fleet.B) return fail(h, LMPC_ERR_ARGUMENT, "lmpc_fleet_ss_set_regression: no fleet store (lmpc_fleet_ss_create)");
+  if (h->reg_on)
+    return fail(h, LMPC_ERR_ARGUMENT, "lmpc_fleet_ss_set_regression: lmpc_set_regression_laps is in effect; switch it off first");
+  const int nf = spec->n_in_state + spec->n_in_ctrl;
+  if (!((nf == 5 && spec->n_out == 3) || (nf == 8 && spec->n_out == 6)) || spec->n_in_state < 1 || spec->n_in_state > 6 ||
+      spec->n_in_ctrl < 0 || spec->n_in_ctrl > 2)
+    return fail(h, LMPC_ERR_UNSUPPORTED, "regression built for (features, rows) = (5, 3) and (8, 6)");
+  if (!(spec->dist_max > 0.0)) return fail(h, LMPC_ERR_ARGUMENT, "dist_max must be positive");
+  for (int i = 0; i < spec->n_out; ++i)
+    if (spec->out[i] < 0 || spec->out[i] > 5) return fail(h, LMPC_ERR_ARGUMENT, "regressed row out of range");
+  for (int i = 0; i < spec->n_in_state; ++i)
+    if (spec->in_state[i] < 0 || spec->in_state[i] > 5) return fail(h, LMPC_ERR_ARGUMENT, "feature state out of range");
+  for (int i = 0; i < spec->n_in_ctrl; ++i)
+    if (spec->in_ctrl[i] < 0 || spec->in_ctrl[i] > 1) return fail(h, LMPC_ERR_ARGUMENT, "feature control out of range");
+  if ((long long)h->fleet.R * (h->fleet.C - 1) > (1ll << 30))
+    return fail(h, LMPC_ERR_ARGUMENT, "lmpc_fleet_ss_set_regression: max_lap_stored x max_pts_per_lap is too large for a car's table");
+  HIP_TRY(h, hipSetDevice(h->device));
+  const size_t Bz = (size_t)h->fleet.B, stride = (size_t)(nf + spec->n_out + 1);
+  const int cap = lmpc_fleet_reg_cap(h->fleet.R, h->fleet.C);
+  const size_t tab_n = Bz * (size_t)cap * stride;
+  if (!h->freg_on || cap != h->freg.cap || tab_n * sizeof(double) + 2 * Bz * sizeof(int) != (size_t)h->freg_bytes) {
+    fleet_reg_off(h);
+    // into local owners: a refused allocation leaves the regression off, and nothing behind
+    dev_buf<double> tab;
+    dev_buf<int> meta;
+    HIP_TRY_AS(h, "lmpc_fleet_ss_set_regression", tab.alloc(tab_n ? tab_n : 1));
+    HIP_TRY_AS(h, "lmpc_fleet_ss_set_regression", meta.alloc(2 * Bz));
+    h->freg_tab = std::move(tab);
+    h->freg_meta = std::move(meta);
+    h->freg.cap = cap;
+    h->freg.tab = h->freg_tab.get();
+    h->freg.nrow = h->freg_meta.get();
+    h->freg.stamp = h->freg_meta.get() + Bz;
+    h->freg_bytes = (int64_t)(tab_n * sizeof(double) + 2 * Bz * sizeof(int));
+  }
+  // behind every launch that still reads the old spec's table: no row count, and every stamp stale (a new spec or sign convention
+  // changes every row)
+  HIP_TRY(h, hipMemsetAsync(h->freg.nrow, 0, Bz * sizeof(int), h->stream));
+  HIP_TRY(h, hipMemsetAsync(h->freg.stamp, 0xff, Bz * sizeof(int), h->stream));
+  h->freg_spec = *spec;
+  h->freg_on = true;
+  return LMPC_OK;
+}
+
+int lmpc_fleet_ss_regress_batch(lmpc_handle* h, int32_t batch, const double* X_ref, const double* U_ref, double* A, double* Bm,
+                                double* g) {
+  if (!h) return LMPC_ERR_ARGUMENT;
+  if (!X_ref || !U_ref || !A || !Bm || !g) return fail(h, LMPC_ERR_ARGUMENT, "lmpc_fleet_ss_regress_batch: null pointer");
+  const int rc = fleet_check(h, batch, "lmpc_fleet_ss_regress_batch");
+  if (rc != LMPC_OK) return rc;
+  if (!h->freg_on) return fail(h, LMPC_ERR_ARGUMENT, "lmpc_fleet_ss_regress_batch: not switched on (lmpc_fleet_ss_set_regression)");
+  HIP_TRY(h, hipSetDevice(h->device));
+  return launch_fleet_regress(h, false, X_ref, U_ref, A, Bm, g);
 }
 
 // ---- spline track: the interpolants on the device, global <-> Frenet (lmpc_track_kernel.hip) ----

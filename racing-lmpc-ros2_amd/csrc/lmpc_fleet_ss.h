@@ -9,7 +9,8 @@
 // A sample is 80 bytes in three planes, so that the query streams 16 of them:
 //   key [car][slot][C]     (s, e_y)                         16 B   what the k-NN scan reads
 //   xr  [car][slot][C][4]  (e_psi, vx, vy, omega)           32 B   gathered for the <= S winners only
-//   aux [car][slot][C][4]  (u_lon, steer, curvature, t)     32 B   read by lmpc_fleet_ss_get_laps only (lap files, regression)
+//   aux [car][slot][C][4]  (u_lon, steer, curvature, t)     32 B   read by lmpc_fleet_ss_get_laps (lap files) and by the per-car
+//                                                                   regression's pack kernel (lmpc_fleet_reg_kernel.hip)
 #ifndef LMPC_FLEET_SS_H_
 #define LMPC_FLEET_SS_H_
 
