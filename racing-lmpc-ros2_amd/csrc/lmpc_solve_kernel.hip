@@ -63,6 +63,8 @@
 #define LN_KFF(s) ((s) ? 22 : 20)
 // Which kernels take it: lmpc_lean (lmpc_solve_layout.hip.h), the fp64 kernels from LMPC_LEAN_MIN_KQ = 11 slots per lane on.
 
+#include "lmpc_solve_setup.hip.h"    // the load phase of both layouts (needs LN_DT above)
+
 template <typename real>
 struct ModelStream {
   const real* ws;  // this problem's [N - 1][LN_REC] in the workspace (HBM / L2)
@@ -1565,48 +1567,9 @@ __device__ __forceinline__ void lmpc_solve_problem(
   PT_DECL
 
   // ---------------- load: linearisation records, per-knot data, constant tables ----------------
-  {
-    if constexpr (!LEAN) {  // (the lean layout leaves the model in the workspace and streams it, sweep by sweep)
-      const io* wsb = ws_lin + (size_t)b * NS * LMPC_LIN_RECORD;
-      for (int e = lane; e < NS * LMPC_LIN_RECORD; e += 64) {
-        const int i = e / LMPC_LIN_RECORD, o = e - i * LMPC_LIN_RECORD;
-        const int c = o / 6;
-        L.st(i)[o < 48 ? ST_ROW(c) + (o - c * 6) : ST_G + (o - 48)] = real(wsb[e]);
-      }
-    }
-    for (int i = lane; i < NS; i += 64) L.st(i)[LEAN ? LN_DT : ST_DT] = real(T_ref[(size_t)i * B + b]);
-    for (int i = lane; i < N; i += 64) {
-      real* kn = L.kn(i);
-      kn[KN_QLIN] = P.learning ? real(0) : real(i == N - 1 ? P.qv_term : P.qv_stage) * real(vref[(size_t)i * B + b]);
-      kn[8] = 0.0;
-      kn[9] = 0.0;
-      kn[KN_BHL] = real(bl[(size_t)i * B + b]) - marg;
-      kn[KN_BHL + 1] = real(br[(size_t)i * B + b]) + marg;
-    }
-    if (lane < 6) {
-      KN0[lane] = real((lane == 0) ? x_ic[b] - s_shift : x_ic[(size_t)lane * B + b]);
-      ct[CT_QD + lane] = P.learning ? 0.0 : P.Qd[lane];
-      ct[CT_QT + lane] = P.learning ? 0.0 : P.Qt[lane];
-      // (the abscissa box moves with the abscissa: single precision carries s relative to x_ic[0])
-      ct[CT_HL + 2 * lane] = lane == 0 ? real(io(P.x_max[0]) - s_shift) : real(P.x_max[lane]);
-      ct[CT_HL + 2 * lane + 1] = lane == 0 ? real(io(P.x_min[0]) - s_shift) : real(P.x_min[lane]);
-    } else if (lane < 8) {
-      KN0[lane] = real(u_ic[(size_t)(lane - 6) * B + b]);
-      ct[CT_HL + 2 * lane] = P.u_hi[lane - 6];
-      ct[CT_HL + 2 * lane + 1] = P.u_lo[lane - 6];
-    } else if (lane < 10) {
-      ct[CT_HL + 2 * lane] = P.v_hi[lane - 8];
-      ct[CT_HL + 2 * lane + 1] = P.v_lo[lane - 8];
-    } else if (lane < 14) {
-      ct[CT_QU + lane - 10] = P.Qu[lane - 10];
-    } else if (lane < 18) {
-      ct[CT_SV + lane - 14] = P.Sv[lane - 14];
-    } else if (lane == 18) {
-      ct[CT_ZERO] = 0.0;
-    } else if (lane < 25) {
-      ct[CT_E + lane - 19] = P.chs2[lane - 19];
-    }
-  }
+  // (lmpc_solve_setup.hip.h: every load of the phase in one flight -- two at KQ = 7, more for the longer single-precision records)
+  lmpc_load_problem<real, io, 64, KQ, LEAN, true>(
+      P, B, b, lane, L, ws_lin, x_ic, u_ic, T_ref, bl, br, vref, s_shift);
   wave_sync();
   PT_MARK(0)
 
@@ -1659,8 +1622,8 @@ __device__ __forceinline__ void lmpc_solve_problem(
           pd = k == 0 ? 1 : -1;
         }
       } else {
-        hi = real(bl[(size_t)i * B + b]) - marg;
-        lo = real(br[(size_t)i * B + b]) + marg;
+        hi = lds[kb + KN_BHL];  // real(bl) - marg, real(br) + marg of the knot, as the load left them
+        lo = lds[kb + KN_BHL + 1];
         on = has_sigma || i >= 1;
       }
     }

@@ -392,48 +392,9 @@ __device__ __forceinline__ void lmpc_solve_problem_w2(const lmpc_params& P, cons
   PT_DECL
   (void)pf;
 
-  // ---------------- load ----------------
-  {
-    if constexpr (!LEAN) {
-      const double* wsb = ws_lin + (size_t)b * NS * LMPC_LIN_RECORD;
-      for (int e = tid; e < NS * LMPC_LIN_RECORD; e += W2_THREADS) {
-        const int i = e / LMPC_LIN_RECORD, o = e - i * LMPC_LIN_RECORD;
-        const int c = o / 6;
-        L.st(i)[o < 48 ? ST_ROW(c) + (o - c * 6) : ST_G + (o - 48)] = wsb[e];
-      }
-    }
-    for (int i = tid; i < NS; i += W2_THREADS) L.st(i)[LEAN ? LN_DT : ST_DT] = T_ref[(size_t)i * B + b];
-    for (int i = tid; i < N; i += W2_THREADS) {
-      real* kn = L.kn(i);
-      kn[KN_QLIN] = real(i == N - 1 ? P.qv_term : P.qv_stage) * vref[(size_t)i * B + b];
-      kn[8] = 0.0;
-      kn[9] = 0.0;
-      kn[KN_BHL] = bl[(size_t)i * B + b] - marg;
-      kn[KN_BHL + 1] = br[(size_t)i * B + b] + marg;
-    }
-    if (tid < 6) {
-      KN0[tid] = x_ic[(size_t)tid * B + b];
-      ct[CT_QD + tid] = P.Qd[tid];
-      ct[CT_QT + tid] = P.Qt[tid];
-      ct[CT_HL + 2 * tid] = P.x_max[tid];
-      ct[CT_HL + 2 * tid + 1] = P.x_min[tid];
-    } else if (tid < 8) {
-      KN0[tid] = u_ic[(size_t)(tid - 6) * B + b];
-      ct[CT_HL + 2 * tid] = P.u_hi[tid - 6];
-      ct[CT_HL + 2 * tid + 1] = P.u_lo[tid - 6];
-    } else if (tid < 10) {
-      ct[CT_HL + 2 * tid] = P.v_hi[tid - 8];
-      ct[CT_HL + 2 * tid + 1] = P.v_lo[tid - 8];
-    } else if (tid < 14) {
-      ct[CT_QU + tid - 10] = P.Qu[tid - 10];
-    } else if (tid < 18) {
-      ct[CT_SV + tid - 14] = P.Sv[tid - 14];
-    } else if (tid == 18) {
-      ct[CT_ZERO] = 0.0;
-    } else if (tid < 25) {
-      ct[CT_E + tid - 19] = P.chs2[tid - 19];
-    }
-  }
+  // ---------------- load (lmpc_solve_setup.hip.h: one flight of loads over both waves) ----------------
+  lmpc_load_problem<real, real, W2_THREADS, KQ, LEAN, false>(
+      P, B, b, tid, L, ws_lin, x_ic, u_ic, T_ref, bl, br, vref, real(0));
   wg_sync();
   PT_MARK(0)
 
@@ -476,8 +437,8 @@ __device__ __forceinline__ void lmpc_solve_problem_w2(const lmpc_params& P, cons
           pd = k == 0 ? 1 : -1;
         }
       } else {
-        hi = bl[(size_t)i * B + b] - marg;
-        lo = br[(size_t)i * B + b] + marg;
+        hi = lds[kb + KN_BHL];  // bl - marg, br + marg of the knot, as the load left them
+        lo = lds[kb + KN_BHL + 1];
         on = has_sigma || i >= 1;
       }
     }
