@@ -702,6 +702,65 @@ int lmpc_global_to_frenet_batch(lmpc_handle* h, const lmpc_spline_track* track, 
  * X_optm, or n = 1 for car states x [6][B] --  ->  pose [3][n][B] = (x, y, yaw), yaw in (-pi, pi]. */
 int lmpc_frenet_to_global_batch(lmpc_handle* h, const lmpc_spline_track* track, int32_t B, int32_t n, const double* X, double* pose);
 
+/* Batched extended Kalman filter: EKFStateEstimator (state_estimators/ekf_state_estimator, ekf_state_estimator.cpp:112-214), ONE
+ * FILTER PER CAR on the device, fp64, over the handle's vehicle.  State [X, Y, yaw, vx, vy, omega]: the dynamics are the handle's
+ * single-track model at curvature k = 0, where the Frenet rows (s, e_y, e_psi) are the global ones -- what the reference's rk4_
+ * with {"k", 0.0} is (:47, :142).  One update, per car:
+ *   dt = (timestamp_ns - last timestamp) 1e-9, one scalar per call, shared by the batch;
+ *   x_p = f_d(x, u, 0, dt) (RK4, or Euler with lmpc_vehicle.integrator), F = d x_p / d x, P_p = F P F' + Q -- Q once per update,
+ *   whatever dt is (:146);
+ *   y = z - h(x_p, z), S = H P_p H' + R, K = P_p H' S^-1, x = x_p + K y, P = (I - K H) P_p -- the non-symmetric form as written
+ *   (:190); all 36 entries of P are kept and nothing is symmetrised;
+ *   x is clipped to [x_min, x_max] (:199-202), P is not touched by the clip.
+ * Kept as written upstream:
+ *   - a timestamp that jumps back only sets the time (initialize, :132-135): the negative dt computed before it is still used to
+ *     integrate, x and P are NOT reset (:108-109 are comments), and the yaml key reset_on_timestamp_jump is read by nobody;
+ *   - check_cov (:238-264) visits column 0 only (its inner loop advances i): R(i,0) < 0 becomes 0 for every row i, then R(0,0) <= 0
+ *     becomes 1e-6; a negative R(1,1) is left alone.  It is applied to the kernel's copy; the caller's R is never written;
+ *   - any NaN or Inf in a car's z or R gives that car the pure prediction (:158-167) -- how a per-car sensor dropout is expressed; the
+ *     car's slice of K is then left as it was, and is what Kz_out reports.
+ * Observations: where the reference registers arbitrary CasADi h(x, z), an observation here is an ordered list of 1 .. 6 distinct
+ * state rows, registered before lmpc_ekf_initialize and addressed by the id registration returns (0, 1, ...).  h selects those rows;
+ * a selected yaw (row 2) is first aligned to the measurement with lmpc::utils::align_yaw(x_p[2], z) (utils.hpp:25-31), which is what
+ * h's second argument serves upstream; H is the selection matrix.  The gains of all observations sit side by side in K [6][sum nz]
+ * in the order of registration (:95-98); an update overwrites the columns of its own observation only.  obs_id = -1: pure prediction.
+ * Not upstream (the fleet needs them): per-car start of x and P (lmpc_ekf_set_state; NULL broadcasts the config's x0 / P0, which
+ * lmpc_ekf_create also does), and the per-car flags below.
+ * Store, owned by the handle, batch axis fastest: x [6][B], u [2][B] (zero at creation), P [36][B] row-major, K [6][sum nz][B].
+ * lmpc_ekf_create and every lmpc_ekf_register_observation allocate (the latter synchronises the handle's stream); nothing else does.
+ * Array arguments are DEVICE pointers; launches and copies go on the handle's stream; every call names the store's batch.
+ * LMPC_ERR_ARGUMENT, nothing written, message in lmpc_last_error (the reference's sentence where it throws):
+ *   registration after lmpc_ekf_initialize (EKFAlreadyInitializedException); nz outside 1 .. 6, a row outside 0 .. 5 or twice;
+ *   lmpc_ekf_initialize with nothing registered (NoObservationRegisteredException); an update before it (EKFUninitializedException);
+ *   an id that was not returned by registration (ObservationNameNotFoundException); another batch than the store's; no store.
+ * WHERE IT HOLDS: the single-track model is stiff at low speed (BARC: lateral and yaw modes near -102 / vx and -216 / vx per second),
+ * and RK4 leaves its stability region when 216 dt / vx > 2.78.  Below that bound -- for the BARC car: vx >= 1.5 m/s with updates of
+ * 12.5 ms or less -- fp64 and extended-precision runs of the filter agree to 3e-15 over 800 updates, and that is the regime every
+ * test is pinned to.  Outside it (the reference's sample start x0 ~ 1e-3, P0 = 1e3 is) the filter is sensitive to rounding and two
+ * correct implementations need not agree. */
+typedef struct lmpc_ekf_config {
+  double x0[LMPC_NX];  /* start estimate (ekf.x0)                                  */
+  double P0[36];       /* start covariance, row-major                             */
+  double Q[36];        /* process noise added per update, row-major               */
+  double x_min[LMPC_NX], x_max[LMPC_NX]; /* the clip; +-INFINITY allowed          */
+} lmpc_ekf_config;
+#define LMPC_EKF_FLAG_FALLBACK 1   /* NaN / Inf in this car's z or R: it took the pure prediction */
+#define LMPC_EKF_FLAG_R_REPAIRED 2 /* check_cov changed the kernel's copy of this car's R         */
+#define LMPC_EKF_FLAG_NOT_FINITE 4 /* this car's new estimate or covariance is not finite         */
+int lmpc_ekf_create(lmpc_handle* h, int32_t batch, const lmpc_ekf_config* cfg); /* replaces an earlier filter */
+int lmpc_ekf_destroy(lmpc_handle* h);                                           /* lmpc_destroy does it too   */
+int lmpc_ekf_register_observation(lmpc_handle* h, int32_t nz, const int32_t* rows /* HOST [nz] */, int32_t* obs_id);
+int lmpc_ekf_initialize(lmpc_handle* h, int64_t timestamp_ns);
+int lmpc_ekf_set_state(lmpc_handle* h, int32_t batch, const double* x /* [6][B] or NULL */, const double* P /* [36][B] or NULL */);
+int lmpc_ekf_update_control(lmpc_handle* h, int32_t batch, const double* u /* [2][B] */);
+/* z [nz][B], R [nz][nz][B] (both ignored with obs_id = -1); x_out [6][B], P_out [36][B], Kz_out [6][nz][B] (not written with
+ * obs_id = -1), flags [B]: any of the four NULL.  Two launches (one with obs_id = -1), asynchronous, no host round trip. */
+int lmpc_ekf_update_batch(lmpc_handle* h, int32_t batch, int32_t obs_id, const double* z, const double* R, int64_t timestamp_ns,
+                          double* x_out, double* P_out, double* Kz_out, int32_t* flags);
+/* The store: x [6][B], P [36][B], K [6][sum nz][B] to DEVICE arrays (asynchronous copies); the time of the last update and
+ * `initialized` to HOST values.  Any pointer NULL. */
+int lmpc_ekf_get(lmpc_handle* h, int32_t batch, double* x, double* P, double* K, int64_t* timestamp_ns, int32_t* initialized);
+
 #ifdef __cplusplus
 }
 #endif

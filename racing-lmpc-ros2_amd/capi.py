@@ -29,7 +29,10 @@ _ABI_SYMBOLS = ("lmpc_create", "lmpc_destroy", "lmpc_last_error", "lmpc_set_stre
                 "lmpc_fleet_ss_query_batch", "lmpc_fleet_ss_load", "lmpc_fleet_ss_get_laps", "lmpc_fleet_ss_stats",
                 "lmpc_fleet_ss_set_regression", "lmpc_fleet_ss_regress_batch",
                 "lmpc_spline_track_create", "lmpc_spline_track_destroy", "lmpc_spline_track_tabulate", "lmpc_track_sample_batch",
-                "lmpc_global_to_frenet_batch", "lmpc_frenet_to_global_batch")
+                "lmpc_global_to_frenet_batch", "lmpc_frenet_to_global_batch",
+                "lmpc_ekf_create", "lmpc_ekf_destroy", "lmpc_ekf_register_observation", "lmpc_ekf_initialize", "lmpc_ekf_set_state",
+                "lmpc_ekf_update_control", "lmpc_ekf_update_batch", "lmpc_ekf_get")
+EKF_FALLBACK, EKF_R_REPAIRED, EKF_NOT_FINITE = 1, 2, 4   # bits of the per-car flags of Solver.ekf_update
 
 
 class LmpcError(RuntimeError):
@@ -60,6 +63,11 @@ class CRegressionSpec(C.Structure):
     """lmpc_regression_spec: RegQuery's index lists and bandwidth (safe_set.hpp:57-75)."""
     _fields_ = [("n_out", C.c_int32), ("out", C.c_int32 * 6), ("n_in_state", C.c_int32), ("in_state", C.c_int32 * 6),
                 ("n_in_ctrl", C.c_int32), ("in_ctrl", C.c_int32 * 2), ("as_written", C.c_int32), ("dist_max", C.c_double)]
+
+
+class CEkfConfig(C.Structure):
+    """lmpc_ekf_config: the filter's start, process noise and clip (ekf_state_estimator_config.hpp)."""
+    _fields_ = [("x0", C.c_double * 6), ("P0", C.c_double * 36), ("Q", C.c_double * 36), ("x_min", C.c_double * 6), ("x_max", C.c_double * 6)]
 
 
 class CTrack(C.Structure):
@@ -819,3 +827,83 @@ class Solver:
             out = torch.empty(shape, dtype=torch.float64, device=self.device)
         self._check(self.lib.lmpc_frenet_to_global_batch(self._h, track._p, C.c_int32(B), C.c_int32(n), _ptr(X), _ptr(out)), "lmpc_frenet_to_global_batch")
         return out
+
+    # ---- batched extended Kalman filter, one per car (ekf_state_estimator.cpp:112-214; include/lmpc_hip.h) ----
+    def ekf_create(self, batch: int, x0, P0, Q, x_min, x_max):
+        """lmpc_ekf_create: `batch` filters over this solver's vehicle, every car started at x0 [6], P0 [6,6]; Q [6,6] is added per
+        update, [x_min, x_max] clips the estimate.  Replaces an earlier filter."""
+        import numpy as np
+
+        self.use_current_stream()
+        cfg = CEkfConfig()
+        for name, v, n in (("x0", x0, 6), ("P0", P0, 36), ("Q", Q, 36), ("x_min", x_min, 6), ("x_max", x_max, 6)):
+            a = np.asarray(v, dtype=np.float64).reshape(-1)
+            if a.size != n:
+                raise ValueError(f"ekf_create: {name} needs {n} values")
+            getattr(cfg, name)[:] = [float(e) for e in a]
+        self._check(self.lib.lmpc_ekf_create(self._h, C.c_int32(int(batch)), C.byref(cfg)), "lmpc_ekf_create")
+        self._ekf_nz, self._ekf_B = [], int(batch)
+
+    def ekf_destroy(self):
+        self._check(self.lib.lmpc_ekf_destroy(self._h), "lmpc_ekf_destroy")
+
+    def ekf_register_observation(self, rows) -> int:
+        """lmpc_ekf_register_observation: an observation of the state rows `rows` (1 .. 6 distinct rows, in the order of z; a yaw row
+        is aligned to its measurement).  Returns the id ekf_update takes.  Before ekf_initialize only."""
+        self.use_current_stream()
+        rows = [int(r) for r in rows]
+        arr = (C.c_int32 * max(len(rows), 1))(*rows)
+        oid = C.c_int32(-1)
+        self._check(self.lib.lmpc_ekf_register_observation(self._h, C.c_int32(len(rows)), arr, C.byref(oid)), "lmpc_ekf_register_observation")
+        self._ekf_nz.append(len(rows))
+        return int(oid.value)
+
+    def ekf_initialize(self, timestamp_ns: int):
+        self._check(self.lib.lmpc_ekf_initialize(self._h, C.c_int64(int(timestamp_ns))), "lmpc_ekf_initialize")
+
+    def ekf_set_state(self, x=None, P=None):
+        """lmpc_ekf_set_state: per-car start, x [6][B] and P [36][B] or [6][6][B] device tensors; None broadcasts the config's x0 / P0."""
+        self.use_current_stream()
+        x = None if x is None else self._t(x)
+        P = None if P is None else self._t(P)
+        self._check(self.lib.lmpc_ekf_set_state(self._h, C.c_int32(self._ekf_B), _ptr(x), _ptr(P)), "lmpc_ekf_set_state")
+
+    def ekf_update_control(self, u):
+        """lmpc_ekf_update_control: u [2][B], held over the predictions until the next call.  Asynchronous."""
+        self.use_current_stream()
+        u = self._t(u)
+        self._check(self.lib.lmpc_ekf_update_control(self._h, C.c_int32(u.shape[1]), _ptr(u)), "lmpc_ekf_update_control")
+
+    def ekf_update(self, obs_id: int, z, R, timestamp_ns: int, out=None):
+        """lmpc_ekf_update_batch: one update of every filter -- the prediction to timestamp_ns and, with obs_id >= 0, the correction by
+        z [nz][B], R [nz][nz][B] (a car with a NaN or Inf in either takes the pure prediction); obs_id = -1 (z, R None): prediction
+        only.  Returns (x [6][B], P [6][6][B], Kz [6][nz][B] or None, flags int32 [B]: EKF_*); `out` = such a tuple reuses the
+        caller's buffers, and an entry None in it is not asked of the kernel.  Asynchronous."""
+        torch = self._torch
+        self.use_current_stream()
+        B = self._ekf_B
+        nz = self._ekf_nz[obs_id] if 0 <= obs_id < len(self._ekf_nz) else 0
+        z = None if z is None else self._t(z)
+        R = None if R is None else self._t(R)
+        if out is not None:
+            x, P, Kz, flags = out
+        else:
+            kw = dict(dtype=torch.float64, device=self.device)
+            x, P = torch.empty((6, B), **kw), torch.empty((6, 6, B), **kw)
+            Kz = torch.empty((6, nz, B), **kw) if nz else None
+            flags = torch.empty((B,), dtype=torch.int32, device=self.device)
+        rc = self.lib.lmpc_ekf_update_batch(self._h, C.c_int32(B if z is None else z.shape[-1]), C.c_int32(int(obs_id)), _ptr(z), _ptr(R),
+                                            C.c_int64(int(timestamp_ns)), _ptr(x), _ptr(P), _ptr(Kz), _ptr(flags))
+        self._check(rc, "lmpc_ekf_update_batch")
+        return x, P, Kz, flags
+
+    def ekf_get(self):
+        """lmpc_ekf_get: {"x" [6][B], "P" [6][6][B], "K" [6][sum nz][B]} device tensors, "timestamp_ns", "initialized"."""
+        torch = self._torch
+        self.use_current_stream()
+        B, nzs = self._ekf_B, sum(self._ekf_nz)
+        kw = dict(dtype=torch.float64, device=self.device)
+        x, P, K = torch.empty((6, B), **kw), torch.empty((6, 6, B), **kw), torch.zeros((6, nzs, B), **kw)
+        ns, init = C.c_int64(0), C.c_int32(0)
+        self._check(self.lib.lmpc_ekf_get(self._h, C.c_int32(B), _ptr(x), _ptr(P), _ptr(K), C.byref(ns), C.byref(init)), "lmpc_ekf_get")
+        return {"x": x, "P": P, "K": K, "timestamp_ns": int(ns.value), "initialized": bool(init.value)}

@@ -154,6 +154,122 @@ def run_global(solver, track: dict, spline, x0, u0, steps: int, dt: float = 0.02
             "warm_hit_rate": (float(hits) / (B * max(steps, 1))) if warm else None}
 
 
+SENSORS = {"sig_vel": (0.05, 0.05), "sig_pose": (0.02, 0.02, 0.01), "dropout": 0.1, "sd0": (0.5, 0.5, 0.3, 0.5, 0.2, 0.5),
+           "Q": (1e-4, 1e-4, 1e-4, 1e-2, 1e-2, 1e-2), "clip": (6.0, 1.5, 20.0)}
+
+
+def run_estimated(solver, track: dict, spline, x0, u0, steps: int, dt: float = 0.025, n_sub: int = 2, speed_scale: float = 0.9,
+                  restart_failed: bool = True, sensors: dict | None = None, seed: int = 0, record_trace: bool = False):
+    """The sensor -> estimate -> projection -> solve -> plant chain: `run_global` with the controller fed by the batched extended Kalman
+    filter (lmpc_ekf_*, one filter per car on the device) instead of the plant's exact state.  The filter's state is the global one,
+    [X, Y, yaw, vx, vy, omega].  Per period:
+      the estimate is projected to the Frenet frame (lmpc_global_to_frenet_batch, started from its previous abscissa) and is the
+      controller's x_ic; solve; the first input of the plan (on failure: of the shifted previous plan) goes to the plant AND to the
+      filter (update_control);
+      the TRUTH advances half a period (lmpc_plant_step_batch) and its (vx, omega) plus noise is the velocity observation (rows 3, 5);
+      it advances the other half, goes to a pose (lmpc_frenet_to_global_batch), and pose plus noise -- yaw in (-pi, pi], x = NaN for the
+      cars whose pose drops out this period -- is the pose observation (rows 0, 1, 2);
+      the next period's inputs are the shifted plan (lmpc_shift_batch) and, for a car whose solve failed, a cold start AT THE NEW
+      ESTIMATE (lmpc_prepare_failed_batch).  The controller never sees the truth.
+    These are the unfused entry points: lmpc_loop_advance_batch steps the plant from the state the controller was given.
+    sensors: overrides of SENSORS -- noise sigmas, the dropout rate, the start's standard deviations sd0 (the filters start at truth +
+    0.5 N(0, 1) sd0 with vx floored at 0.5, P0 = diag(sd0^2)), the diagonal of Q, the clip of (vx, vy, omega).  The noise comes from a
+    torch.Generator on the device seeded with `seed`.  n_sub must be even.  The model is stiff at low speed (include/lmpc_hip.h at
+    lmpc_ekf_create): keep the cars above 1.5 m/s for estimates that do not depend on rounding.
+    Returns run_global's statistics (of the truth), "x_est" [6][B] the last estimate, "rms_error" [6] the RMS of estimate - truth in
+    the global frame over all cars and periods (yaw difference wrapped), "ekf_flags" int32 [B] the OR of every update's flags, and
+    "x_est0" / "P0" / "ekf_config" the filters' start; record_trace=True adds "trace": per update (obs_id, z, R, u, timestamp_ns,
+    x_est) with device tensors -- enough to replay the filters, which are open-loop in (u, z, t)."""
+    import math
+
+    import torch
+
+    if n_sub % 2:
+        raise ValueError("run_estimated: n_sub must be even (the velocity observation sits at mid-period)")
+    sn = dict(SENSORS, **(sensors or {}))
+    trk = solver.device_track(track)
+    L = float(track["L"])
+    x, u_prev = x0.clone(), u0.clone()
+    B, dev = x.shape[1], x.device
+    kw = dict(dtype=torch.float64, device=dev)
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(int(seed))
+    col = lambda v: torch.as_tensor(v, **kw)[:, None]  # noqa: E731
+    sig_v, sig_p, sd0 = col(sn["sig_vel"]), col(sn["sig_pose"]), col(sn["sd0"])
+    R_v = torch.diag(sig_v[:, 0] ** 2)[:, :, None].repeat(1, 1, B).contiguous()
+    R_p = torch.diag(sig_p[:, 0] ** 2)[:, :, None].repeat(1, 1, B).contiguous()
+    inf = math.inf
+    cfg = {"x0": [0.0] * 6, "P0": torch.diag(sd0[:, 0] ** 2).cpu().numpy(), "Q": torch.diag(torch.as_tensor(sn["Q"], dtype=torch.float64)).numpy(),
+           "x_min": [-inf] * 3 + [-float(c) for c in sn["clip"]], "x_max": [inf] * 3 + [float(c) for c in sn["clip"]]}
+    solver.ekf_create(B, **cfg)
+    o_vel, o_pose = solver.ekf_register_observation((3, 5)), solver.ekf_register_observation((0, 1, 2))
+    pose = solver.frenet_to_global(spline, x)
+    x_est = torch.cat([pose, x[3:6]]) + 0.5 * torch.randn((6, B), generator=gen, **kw) * sd0
+    x_est[3].clamp_(min=0.5)
+    x_est0 = x_est.clone()
+    P0 = torch.diag(sd0[:, 0] ** 2)[:, :, None].repeat(1, 1, B).contiguous()
+    solver.ekf_set_state(x_est, P0)
+    solver.ekf_initialize(0)
+    frenet, status = solver.global_to_frenet(spline, x_est[0:3].contiguous())
+    track_status = status.clone()
+    x_ic = torch.cat([frenet, x_est[3:6]]).contiguous()
+    inp = solver.prepare(trk, x_ic, dt, speed_scale=speed_scale)
+    out = solver.alloc_outputs(B)
+    dist, worst_excess = torch.zeros(B, **kw), torch.zeros(B, **kw)
+    n_fail = torch.zeros(B, dtype=torch.int64, device=dev)
+    flags_or = torch.zeros(B, dtype=torch.int32, device=dev)
+    sq_err = torch.zeros(6, **kw)
+    half_b = float(solver.vehicle["b"]) / 2.0
+    dt_ns = int(round(dt * 1e9))
+    trace = []
+    for k in range(steps):
+        inp["x_ic"], inp["u_ic"] = x_ic, u_prev
+        solver.solve(inp, out)
+        ok = out["status"] == 0
+        n_fail.add_((~ok).to(torch.int64))
+        u_apply = torch.where(ok[None, :], out["U_optm"][:, 0, :], inp["U_ref"][:, 0, :]).contiguous()
+        solver.ekf_update_control(u_apply)
+        s_before = x[0].clone()
+        solver.plant_step(trk, x, u_apply, dt / n_sub, n_sub // 2)
+        z_v = (x[[3, 5]] + sig_v * torch.randn((2, B), generator=gen, **kw)).contiguous()
+        ts = k * dt_ns + dt_ns // 2
+        xe, _, _, fl = solver.ekf_update(o_vel, z_v, R_v, ts)
+        flags_or |= fl
+        if record_trace:
+            trace.append((o_vel, z_v, R_v, u_apply, ts, xe))
+        solver.plant_step(trk, x, u_apply, dt / n_sub, n_sub // 2)
+        ds = x[0] - s_before
+        dist.add_(torch.where(ds < -L / 2, ds + L, ds))
+        exc = torch.maximum(x[1] + half_b - inp["bound_left"][0], inp["bound_right"][0] - (x[1] - half_b))
+        torch.maximum(worst_excess, exc, out=worst_excess)
+        pose = solver.frenet_to_global(spline, x)
+        z_p = pose + sig_p * torch.randn((3, B), generator=gen, **kw)
+        z_p[2] = torch.atan2(torch.sin(z_p[2]), torch.cos(z_p[2]))
+        z_p[0] = torch.where(torch.rand((B,), generator=gen, **kw) < float(sn["dropout"]), torch.full((B,), math.nan, **kw), z_p[0])
+        ts = (k + 1) * dt_ns
+        x_est, _, _, fl = solver.ekf_update(o_pose, z_p, R_p, ts)
+        flags_or |= fl
+        if record_trace:
+            trace.append((o_pose, z_p, R_p, u_apply, ts, x_est))
+        err = x_est - torch.cat([pose, x[3:6]])
+        err[2] = torch.atan2(torch.sin(err[2]), torch.cos(err[2]))
+        sq_err += (err ** 2).mean(dim=1)
+        # the next period's controller state: the new estimate in the Frenet frame, projected from its previous abscissa
+        frenet, status = solver.global_to_frenet(spline, x_est[0:3].contiguous(), s0=x_ic[0].contiguous())
+        torch.maximum(track_status, status, out=track_status)
+        x_ic = torch.cat([frenet, x_est[3:6]]).contiguous()
+        u_prev = u_apply
+        nxt = solver.shift(trk, inp, out, dt, speed_scale=speed_scale)
+        if restart_failed:
+            solver.prepare_failed(trk, x_ic, out["status"], nxt, dt, speed_scale=speed_scale)
+        inp = nxt
+    res = {"x": x, "distance": dist, "worst_excess": worst_excess, "n_fail": n_fail, "track_status": track_status, "warm_hit_rate": None,
+           "x_est": x_est, "rms_error": torch.sqrt(sq_err / max(steps, 1)), "ekf_flags": flags_or, "x_est0": x_est0, "P0": P0, "ekf_config": cfg}
+    if record_trace:
+        res["trace"] = trace
+    return res
+
+
 def record_laps(solver, track: dict, speed_scales=(0.80, 0.85, 0.90, 0.95, 1.0), dt: float = 0.03, n_sub: int = 3):
     """The laps SURVEY.md 8d config 3 stores in the safe set: "running config 1's tracking loop for 5 laps with seed-indexed speed
     scales {0.80, 0.85, 0.90, 0.95, 1.0}", one sample per 0.03 s (the recorder's period upstream, racing_mpc_node.cpp:66).  One

@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "lmpc_device.h"
+#include "lmpc_ekf.h"
 #include "lmpc_fleet_reg.h"
 #include "lmpc_fleet_ss.h"
 
@@ -119,6 +120,14 @@ struct __attribute__((visibility("hidden"))) lmpc_handle {  // (its members are 
   dev_buf<double> freg_tab;     // [fleet.B][freg.cap][NF + NOUT + 1]
   dev_buf<int> freg_meta;       // nrow [fleet.B] | stamp [fleet.B]
   int64_t freg_bytes = 0;
+  // batched extended Kalman filter (lmpc_ekf_create): one filter per car, csrc/lmpc_ekf.h
+  lmpc_ekf_store ekf{};  // raw copies of the two owners below, as the kernels take them
+  dev_buf<double> ekf_xup;  // x [6][B] | u [2][B] | P [36][B]
+  dev_buf<double> ekf_K;    // [6][nzsum][B], allocated anew by every registration
+  std::vector<lmpc_ekf_obs> ekf_obs;
+  lmpc_ekf_config ekf_cfg{};
+  bool ekf_initialized = false;  // initialized_ upstream: registration is closed, updates are open
+  int64_t ekf_ns = 0;            // nanosec_: the time of the last update
   // staging for the single-problem host entry points (lmpc_solve_host, lmpc_ss_query_host): device buffers and PINNED
   // host mirrors, all sized and allocated by lmpc_create -- the per-step path of one controller allocates nothing
   dev_buf<double> stage_dev;
@@ -678,6 +687,13 @@ int fleet_check(lmpc_handle* h, int32_t batch, const char* who) {
   if (!h->fleet.B) return fail(h, LMPC_ERR_ARGUMENT, std::string(who) + ": no fleet store (lmpc_fleet_ss_create)");
   if (batch != h->fleet.B)
     return fail(h, LMPC_ERR_ARGUMENT, std::string(who) + ": batch " + std::to_string(batch) + " is not the store's " + std::to_string(h->fleet.B));
+  return LMPC_OK;
+}
+
+int ekf_check(lmpc_handle* h, int32_t batch, const char* who) {
+  if (!h->ekf.B) return fail(h, LMPC_ERR_ARGUMENT, std::string(who) + ": no filter (lmpc_ekf_create)");
+  if (batch != h->ekf.B)
+    return fail(h, LMPC_ERR_ARGUMENT, std::string(who) + ": batch " + std::to_string(batch) + " is not the filter's " + std::to_string(h->ekf.B));
   return LMPC_OK;
 }
 
@@ -1768,6 +1784,144 @@ int lmpc_fleet_ss_regress_batch(lmpc_handle* h, int32_t batch, const double* X_r
   if (!h->freg_on) return fail(h, LMPC_ERR_ARGUMENT, "lmpc_fleet_ss_regress_batch: not switched on (lmpc_fleet_ss_set_regression)");
   HIP_TRY(h, hipSetDevice(h->device));
   return launch_fleet_regress(h, false, X_ref, U_ref, A, Bm, g);
+}
+
+// ---- batched extended Kalman filter, one per car (csrc/lmpc_ekf.h, csrc/lmpc_ekf_kernel.hip) ----
+int lmpc_ekf_destroy(lmpc_handle* h) {
+  if (!h) return LMPC_ERR_ARGUMENT;
+  if (!h->ekf.B) return LMPC_OK;
+  (void)hipSetDevice(h->device);
+  (void)hipStreamSynchronize(h->stream);
+  h->ekf_xup.release();
+  h->ekf_K.release();
+  h->ekf = lmpc_ekf_store{};
+  h->ekf_obs.clear();
+  h->ekf_initialized = false;
+  h->ekf_ns = 0;
+  return LMPC_OK;
+}
+
+int lmpc_ekf_create(lmpc_handle* h, int32_t batch, const lmpc_ekf_config* cfg) {
+  if (!h) return LMPC_ERR_ARGUMENT;
+  if (!cfg || batch < 1 || batch > (1 << 24)) return fail(h, LMPC_ERR_ARGUMENT, "lmpc_ekf_create: null config or batch outside 1 .. 2^24");
+  const int rc0 = lmpc_ekf_destroy(h);
+  if (rc0 != LMPC_OK) return rc0;
+  HIP_TRY(h, hipSetDevice(h->device));
+  const size_t Bz = (size_t)batch;
+  dev_buf<double> xup;  // a local owner: a refused allocation leaves the handle without a filter
+  HIP_TRY_AS(h, "lmpc_ekf_create", xup.alloc(44 * Bz));
+  HIP_TRY_AS(h, "lmpc_ekf_create", hipMemsetAsync(xup.get(), 0, 44 * Bz * sizeof(double), h->stream));  // u_ starts at zero (:40)
+  h->ekf_xup = std::move(xup);
+  h->ekf_cfg = *cfg;
+  h->ekf.B = batch;
+  h->ekf.nzsum = 0;
+  h->ekf.x = h->ekf_xup.get();
+  h->ekf.u = h->ekf.x + 6 * Bz;
+  h->ekf.P = h->ekf.u + 2 * Bz;
+  h->ekf.K = nullptr;
+  lmpc_ekf_seed seed;
+  std::memcpy(seed.x0, cfg->x0, sizeof(seed.x0));
+  std::memcpy(seed.P0, cfg->P0, sizeof(seed.P0));
+  HIP_TRY_AS(h, "lmpc_ekf_create", lmpc_ekf_seed_launch(h->stream, h->ekf, seed, nullptr, nullptr));
+  return LMPC_OK;
+}
+
+int lmpc_ekf_register_observation(lmpc_handle* h, int32_t nz, const int32_t* rows, int32_t* obs_id) {
+  if (!h) return LMPC_ERR_ARGUMENT;
+  if (!h->ekf.B) return fail(h, LMPC_ERR_ARGUMENT, "lmpc_ekf_register_observation: no filter (lmpc_ekf_create)");
+  if (h->ekf_initialized) return fail(h, LMPC_ERR_ARGUMENT, "Changes to observations are not allowed after the filter is initialized.");
+  if (!rows || !obs_id || nz < 1 || nz > 6)
+    return fail(h, LMPC_ERR_ARGUMENT, "lmpc_ekf_register_observation: null pointer or nz outside 1 .. 6");
+  lmpc_ekf_obs ob{};
+  ob.nz = nz;
+  ob.koff = h->ekf.nzsum;
+  for (int a = 0; a < nz; ++a) {
+    if (rows[a] < 0 || rows[a] > 5) return fail(h, LMPC_ERR_ARGUMENT, "lmpc_ekf_register_observation: a row outside 0 .. 5");
+    for (int c = 0; c < a; ++c)
+      if (rows[c] == rows[a]) return fail(h, LMPC_ERR_ARGUMENT, "lmpc_ekf_register_observation: the rows of an observation must be distinct");
+    ob.rows[a] = rows[a];
+  }
+  // K_ grows by nz zero columns (:95-98); no update has run yet, so the whole gain is zero
+  HIP_TRY(h, hipSetDevice(h->device));
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  const size_t n = 6 * (size_t)(h->ekf.nzsum + nz) * (size_t)h->ekf.B;
+  dev_buf<double> K;
+  HIP_TRY_AS(h, "lmpc_ekf_register_observation", K.alloc(n));
+  HIP_TRY_AS(h, "lmpc_ekf_register_observation", hipMemsetAsync(K.get(), 0, n * sizeof(double), h->stream));
+  h->ekf_K = std::move(K);
+  h->ekf.K = h->ekf_K.get();
+  h->ekf.nzsum += nz;
+  *obs_id = (int32_t)h->ekf_obs.size();
+  h->ekf_obs.push_back(ob);
+  return LMPC_OK;
+}
+
+int lmpc_ekf_initialize(lmpc_handle* h, int64_t timestamp_ns) {
+  if (!h) return LMPC_ERR_ARGUMENT;
+  if (!h->ekf.B) return fail(h, LMPC_ERR_ARGUMENT, "lmpc_ekf_initialize: no filter (lmpc_ekf_create)");
+  if (h->ekf_obs.empty()) return fail(h, LMPC_ERR_ARGUMENT, "No observation has been registered for the filter.");
+  h->ekf_initialized = true;
+  h->ekf_ns = timestamp_ns;  // x and P are not reset (:108-109 are comments)
+  return LMPC_OK;
+}
+
+int lmpc_ekf_set_state(lmpc_handle* h, int32_t batch, const double* x, const double* P) {
+  if (!h) return LMPC_ERR_ARGUMENT;
+  const int rc = ekf_check(h, batch, "lmpc_ekf_set_state");
+  if (rc != LMPC_OK) return rc;
+  HIP_TRY(h, hipSetDevice(h->device));
+  lmpc_ekf_seed seed;
+  std::memcpy(seed.x0, h->ekf_cfg.x0, sizeof(seed.x0));
+  std::memcpy(seed.P0, h->ekf_cfg.P0, sizeof(seed.P0));
+  HIP_TRY(h, lmpc_ekf_seed_launch(h->stream, h->ekf, seed, x, P));
+  return LMPC_OK;
+}
+
+int lmpc_ekf_update_control(lmpc_handle* h, int32_t batch, const double* u) {
+  if (!h) return LMPC_ERR_ARGUMENT;
+  if (!u) return fail(h, LMPC_ERR_ARGUMENT, "lmpc_ekf_update_control: null pointer");
+  const int rc = ekf_check(h, batch, "lmpc_ekf_update_control");
+  if (rc != LMPC_OK) return rc;
+  HIP_TRY(h, hipSetDevice(h->device));
+  HIP_TRY(h, hipMemcpyAsync(h->ekf.u, u, 2 * (size_t)batch * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+  return LMPC_OK;
+}
+
+int lmpc_ekf_update_batch(lmpc_handle* h, int32_t batch, int32_t obs_id, const double* z, const double* R, int64_t timestamp_ns, double* x_out,
+                          double* P_out, double* Kz_out, int32_t* flags) {
+  if (!h) return LMPC_ERR_ARGUMENT;
+  const int rc = ekf_check(h, batch, "lmpc_ekf_update_batch");
+  if (rc != LMPC_OK) return rc;
+  if (!h->ekf_initialized)
+    return fail(h, LMPC_ERR_ARGUMENT, "Call EKFStateEstimator::initialize() before making any observation updates.");
+  if (obs_id < -1 || obs_id >= (int32_t)h->ekf_obs.size())
+    return fail(h, LMPC_ERR_ARGUMENT, "The observation name \"" + std::to_string(obs_id) + "\" is not found.");
+  if (obs_id >= 0 && (!z || !R)) return fail(h, LMPC_ERR_ARGUMENT, "lmpc_ekf_update_batch: an observation needs z and R");
+  HIP_TRY(h, hipSetDevice(h->device));
+  // a timestamp that jumps back only sets the time upstream; the negative dt computed before is still used (:130-146)
+  const double dt = (double)(timestamp_ns - h->ekf_ns) * 1e-9;
+  lmpc_ekf_consts cst;
+  std::memcpy(cst.Q, h->ekf_cfg.Q, sizeof(cst.Q));
+  std::memcpy(cst.x_min, h->ekf_cfg.x_min, sizeof(cst.x_min));
+  std::memcpy(cst.x_max, h->ekf_cfg.x_max, sizeof(cst.x_max));
+  const lmpc_ekf_out out{x_out, P_out, obs_id >= 0 ? Kz_out : nullptr, flags};
+  HIP_TRY(h, lmpc_ekf_launch(h->stream, h->ekf, h->P.veh, cst, obs_id >= 0 ? &h->ekf_obs[(size_t)obs_id] : nullptr, dt, z, R, out));
+  h->ekf_ns = timestamp_ns;
+  return LMPC_OK;
+}
+
+int lmpc_ekf_get(lmpc_handle* h, int32_t batch, double* x, double* P, double* K, int64_t* timestamp_ns, int32_t* initialized) {
+  if (!h) return LMPC_ERR_ARGUMENT;
+  const int rc = ekf_check(h, batch, "lmpc_ekf_get");
+  if (rc != LMPC_OK) return rc;
+  HIP_TRY(h, hipSetDevice(h->device));
+  const size_t Bz = (size_t)batch * sizeof(double);
+  if (x) HIP_TRY(h, hipMemcpyAsync(x, h->ekf.x, 6 * Bz, hipMemcpyDeviceToDevice, h->stream));
+  if (P) HIP_TRY(h, hipMemcpyAsync(P, h->ekf.P, 36 * Bz, hipMemcpyDeviceToDevice, h->stream));
+  if (K && h->ekf.nzsum) HIP_TRY(h, hipMemcpyAsync(K, h->ekf.K, 6 * (size_t)h->ekf.nzsum * Bz, hipMemcpyDeviceToDevice, h->stream));
+  if (timestamp_ns) *timestamp_ns = h->ekf_ns;
+  if (initialized) *initialized = h->ekf_initialized ? 1 : 0;
+  return LMPC_OK;
 }
 
 // ---- spline track: the interpolants on the device, global <-> Frenet (lmpc_track_kernel.hip) ----
