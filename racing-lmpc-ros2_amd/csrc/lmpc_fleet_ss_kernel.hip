@@ -1,10 +1,9 @@
 // lmpc_fleet_ss_kernel.hip -- the fleet safe set on gfx950: SafeSetRecorder::step for every car in one launch, and the k-NN
 // query of lmpc_ss_kernel.hip against each car's OWN ring of laps.  Layout: lmpc_fleet_ss.h.
 //
-// Query: one wavefront per car, as in the shared-store kernel, with the same selection (per-lane best two, 64-lane bitonic sort
-// lexicographic in (distance, unrolled index), K arg-min rounds when a lane owns two winners) and the same distance expression
-// in the same order, so that on equal stores the results are bit-equal.  What differs is where the bytes come from: a car's
-// keys are nobody else's, so they come from HBM and are read ONCE --
+// Query: one wavefront per car; the selection is lmpc_knn_select.hip.h, the one the shared-store kernel runs, so on equal stores the
+// results are bit-equal.  This file holds the store behind it, a car's ring.  What differs from the shared store is where the bytes
+// come from: a car's keys are nobody else's, so they come from HBM and are read ONCE --
 //   - a lane reads the 16-byte key of sample j and derives the three unrolled candidates (j, n + j, 2n + j: the copies at -L, 0,
 //     +L) arithmetically, instead of visiting 3n rows of [n][6];
 //   - eight independent 16-byte loads per lane are issued before the first is used (8 KB in flight per wave: one trip covers a
@@ -14,13 +13,12 @@
 //     RECOMPUTES the distances from the keys.  Which candidates of a lane's share are already taken needs no bit mask either:
 //     winners leave in increasing (distance, index) order, so a lane's retired candidates are exactly those of its share not
 //     above the last one it gave up -- one (distance, index) threshold per lane.  Waves per CU are bounded by registers alone.
-// A lane's candidates do not come in index order (j ascending, rep inside), so its best two are kept by the full lexicographic
-// comparison rather than by arrival.
 #include <hip/hip_runtime.h>
 
 #include <limits.h>
 
 #include "lmpc_fleet_ss.h"
+#include "lmpc_knn_select.hip.h"
 
 // ---- recorder: SafeSetRecorder::step (safe_set.cpp:278-322) + SafeSetManager::add_lap (:144-151), one thread per car ----
 __global__ __launch_bounds__(256) void lmpc_fleet_ss_record_kernel(lmpc_fleet_store st, const double* __restrict__ x,
@@ -140,67 +138,42 @@ __global__ __launch_bounds__(256) void lmpc_fleet_ss_stats_kernel(lmpc_fleet_sto
   }
 }
 
-// one DPP step of the wave-wide arg-min (as in lmpc_ss_kernel.hip): lanes outside ROW_MASK see the identity (+inf, INT_MAX)
-#define FLEET_ARGMIN_STEP(CTRL, ROW_MASK)                                                                                \
-  {                                                                                                                      \
-    const int od_lo = __builtin_amdgcn_update_dpp(0, __double2loint(d), CTRL, ROW_MASK, 0xf, false);                     \
-    const int od_hi = __builtin_amdgcn_update_dpp(0x7ff00000, __double2hiint(d), CTRL, ROW_MASK, 0xf, false);            \
-    const int oi = __builtin_amdgcn_update_dpp(INT_MAX, i, CTRL, ROW_MASK, 0xf, false);                                  \
-    const double od = __hiloint2double(od_hi, od_lo);                                                                    \
-    if (od < d || (od == d && oi < i)) {                                                                                 \
-      d = od;                                                                                                            \
-      i = oi;                                                                                                            \
-    }                                                                                                                    \
-  }
-
-// the three unrolled candidates of key (ks, ke), sample j of a lap of n: the distance expression of lmpc_ss_query_kernel, operation
-// for operation; a candidate enters the lane's best two by (distance, index), +inf and NaN never do (INT_MAX = no candidate)
-#define FLEET_CANDIDATES(KS, KE, J, FILTER)                                                                              \
-  _Pragma("unroll") for (int rep = 0; rep < 3; ++rep) {                                                                  \
-    const double s = (KS) + (rep - 1) * Lt;                                                                              \
-    const double ds = s - qs, de = (KE) - qe;                                                                            \
-    const double d = ds * ds + de * de;                                                                                  \
-    const int c = rep * n + (J);                                                                                         \
-    if (FILTER) {                                                                                                        \
-      if (d < bestd || (d == bestd && c < besti && d < INFINITY)) {                                                      \
-        secd = bestd;                                                                                                    \
-        seci = besti;                                                                                                    \
-        bestd = d;                                                                                                       \
-        besti = c;                                                                                                       \
-      } else if (d < secd || (d == secd && c < seci && d < INFINITY)) {                                                  \
-        secd = d;                                                                                                        \
-        seci = c;                                                                                                        \
-      }                                                                                                                  \
-    }                                                                                                                    \
-  }
-
-__global__ __launch_bounds__(64) void lmpc_fleet_ss_query_kernel(lmpc_fleet_store st, int S, int K, double Lt,
-                                                                 const double* __restrict__ query, double* __restrict__ ss_x,
-                                                                 double* __restrict__ ss_j, int* __restrict__ n_found) {
-#pragma clang fp contract(off)
-  // XCD-aware assignment, as in lmpc_ss_query_kernel: the 8-byte results of neighbouring cars share 64-byte lines of the
-  // [field][point][batch] arrays and are merged in one XCD's L2
-  const int B = st.B;
-  const int b = (int)(blockIdx.x & 7) * ((B + 7) >> 3) + (int)(blockIdx.x >> 3), lane = threadIdx.x;
-  if (b >= B) return;
-  const double qs = query[b], qe = query[(size_t)B + b];
-  const int R1 = st.R + 1, C = st.C;
-  const int head = st.head[b], cnt = st.cnt[b] < st.R ? st.cnt[b] : st.R;
-  int tot = 0;
-  double last = 0.0;  // lane k < 6: component k of the last point written; lane 6: its J - J0
-  double j0 = 0.0;
-  for (int a = 0; a < cnt && tot < S; ++a) {  // newest lap first
+// A car's ring of laps as the store of lmpc_knn_query.
+struct lmpc_ss_fleet_ring {
+  int n_laps;  // laps in the ring, clamped to its size
+  const lmpc_fleet_store& st;
+  int b, head, n;
+  const double2* __restrict__ kl;  // the current lap: keys (s, e_y), and the other four components
+  const double* __restrict__ xl;
+  double thd;  // the last candidate this lane gave up: everything of its share up to it, by (distance, index), is taken
+  int thi;
+  __device__ __forceinline__ bool open(int a) {
+    const int R1 = st.R + 1, C = st.C;
     int sl = head - 1 - a;
     if (sl < 0) sl += R1;
     const size_t slot = (size_t)b * R1 + sl;
-    int n = st.npts[slot];
+    kl = st.key + slot * C;
+    xl = st.xr + slot * C * 4;
+    n = st.npts[slot];
     if (n > C) n = C;
-    if (n < 1) continue;
-    const int n3 = 3 * n;
-    const double2* __restrict__ kl = st.key + slot * C;
-    const double* __restrict__ xl = st.xr + slot * C * 4;
-    double bestd = INFINITY, secd = INFINITY;
-    int besti = INT_MAX, seci = INT_MAX;  // seci: INT_MAX = the share has no further candidate, -1 = not known (rescan)
+    return n >= 1;
+  }
+  // the three unrolled candidates of key kp, sample j of a lap of n (j, n + j, 2n + j: the copies at -L, 0, +L).  They do not come
+  // in index order (j ascending, rep inside), so they enter by the full lexicographic rule.  FILTERED: only those above the threshold.
+  template <bool FILTERED>
+  __device__ __forceinline__ void candidates(lmpc_knn_best2& m, double2 kp, int j, double Lt, double qs, double qe) const {
+#pragma unroll
+    for (int rep = 0; rep < 3; ++rep) {
+      const double d = lmpc_knn_dist(kp.x, kp.y, rep, Lt, qs, qe);
+      const int c = rep * n + j;
+      if (!FILTERED || d > thd || (d == thd && c > thi)) m.enter<false>(d, c);
+    }
+  }
+  // eight independent 16-byte loads per lane are issued before the first is used (8 KB in flight per wave: one trip covers a lap of
+  // 512 samples), against ~900 cycles of HBM latency
+  __device__ __forceinline__ lmpc_knn_best2 scan(int lane, double Lt, double qs, double qe) const {
+    lmpc_knn_best2 m;
+    m.clear();
     for (int base = 0; base < n; base += 512) {
       double2 kv[8];
 #pragma unroll
@@ -211,117 +184,38 @@ __global__ __launch_bounds__(64) void lmpc_fleet_ss_query_kernel(lmpc_fleet_stor
 #pragma unroll
       for (int t = 0; t < 8; ++t) {
         const int j = base + lane + 64 * t;
-        if (j < n) { FLEET_CANDIDATES(kv[t].x, kv[t].y, j, true) }
+        if (j < n) candidates<false>(m, kv[t], j, Lt, qs, qe);
       }
     }
-    int take = K < n3 ? K : n3;
-    if (take > S - tot) take = S - tot;
-    // Fast path: the 64 lane minima sorted across the wave; valid unless some lane's runner-up beats the take-th of them
-    if (take <= 64) {
-      double d = bestd;
-      int i = besti;
-#pragma unroll
-      for (int k = 2; k <= 64; k <<= 1) {
-#pragma unroll
-        for (int jj = k >> 1; jj > 0; jj >>= 1) {
-          const double od = __shfl_xor(d, jj, 64);
-          const int oi = __shfl_xor(i, jj, 64);
-          const bool other_less = od < d || (od == d && oi < i);
-          const bool keep_min = ((lane & jj) == 0) == ((lane & k) == 0);
-          if (keep_min ? other_less : !other_less) {
-            d = od;
-            i = oi;
-          }
-        }
-      }
-      const double td = __shfl(d, take - 1, 64);
-      const int ti = __shfl(i, take - 1, 64);
-      const bool beaten = seci != INT_MAX && (secd < td || (secd == td && seci < ti));
-      if (!__any(beaten) && ti != INT_MAX) {
-        const bool mine = lane < take;
-        const int ii = mine ? i : 0;
-        const int rep = ii / n, j = ii - rep * n;
-        const double jv = (double)(n - 1 - j) + (1 - rep) * (double)(n - 1);
-        if (tot == 0) j0 = __shfl(jv, 0, 64);
-        if (mine) {
-          const double2 kp = kl[j];
-          const size_t o = (size_t)(tot + lane) * B + b, SB = (size_t)S * B;
-          ss_x[o] = kp.x + (rep - 1) * Lt;
-          ss_x[SB + o] = kp.y + 0.0;
-#pragma unroll
-          for (int k = 0; k < 4; ++k) ss_x[(size_t)(k + 2) * SB + o] = xl[(size_t)j * 4 + k] + 0.0;
-          ss_j[o] = jv - j0;
-        }
-        // the last point written, as the padding below wants it: component k on lane k < 6, J - J0 on lane 6
-        const int il = __shfl(i, take - 1, 64);
-        const int repl = il / n, jl = il - repl * n;
-        if (lane == 0)
-          last = kl[jl].x + (repl - 1) * Lt;
-        else if (lane == 1)
-          last = kl[jl].y + 0.0;
-        else if (lane < 6)
-          last = xl[(size_t)jl * 4 + lane - 2] + 0.0;
-        else if (lane == 6)
-          last = ((double)(n - 1 - jl) + (1 - repl) * (double)(n - 1)) - j0;
-        tot += take;
-        continue;
-      }
-    }
-    double thd = 0.0;  // the last candidate this lane gave up: everything of its share up to it, by (distance, index), is taken
-    int thi = -1;
-    for (int q = 0; q < take; ++q, ++tot) {
-      double d = bestd;
-      int i = besti;
-      FLEET_ARGMIN_STEP(0x128, 0xf)
-      FLEET_ARGMIN_STEP(0x124, 0xf)
-      FLEET_ARGMIN_STEP(0x122, 0xf)
-      FLEET_ARGMIN_STEP(0x121, 0xf)
-      FLEET_ARGMIN_STEP(0x142, 0xa)
-      FLEET_ARGMIN_STEP(0x143, 0xc)
-      d = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(d), 63), __builtin_amdgcn_readlane(__double2loint(d), 63));
-      i = __builtin_amdgcn_readlane(i, 63);
-      if (i == INT_MAX) break;  // no finite distance left (a NaN query): nothing more to take
-      const int rep = i / n, j = i - rep * n;
-      const double jv = (double)(n - 1 - j) + (1 - rep) * (double)(n - 1);
-      if (tot == 0) j0 = jv;
-      if (lane < 6) {
-        if (lane == 0)
-          last = kl[j].x + (rep - 1) * Lt;
-        else if (lane == 1)
-          last = kl[j].y + 0.0;
-        else
-          last = xl[(size_t)j * 4 + lane - 2] + 0.0;
-        ss_x[((size_t)lane * S + tot) * B + b] = last;
-      } else if (lane == 6) {
-        last = jv - j0;
-        ss_j[(size_t)tot * B + b] = last;
-      }
-      if (besti == i) {  // the winner's owner retires it and moves on to its runner-up
-        thd = bestd;
-        thi = besti;
-        if (seci >= 0) {
-          bestd = secd;
-          besti = seci;
-          secd = INFINITY;
-          seci = besti == INT_MAX ? INT_MAX : -1;
-        } else {  // second win in a row without a known runner-up: the share's two smallest above the threshold, from the keys
-          bestd = secd = INFINITY;
-          besti = seci = INT_MAX;
-          for (int jr = lane; jr < n; jr += 64) {
-            const double2 kp = kl[jr];
-            FLEET_CANDIDATES(kp.x, kp.y, jr, (d > thd || (d == thd && c > thi)))
-          }
-        }
-      }
-    }
+    return m;
   }
-  if (lane == 0) n_found[b] = tot;
-  // pad with the last point (racing_mpc.cpp:263-272); nothing found (an empty ring, a NaN query): zero-filled, n_found = 0
-  if (tot == 0) last = 0.0;
-  for (int q = tot; q < S; ++q) {
-    if (lane < 6)
-      ss_x[((size_t)lane * S + q) * B + b] = last;
-    else if (lane == 6)
-      ss_j[(size_t)q * B + b] = last;
+  __device__ __forceinline__ void begin_rounds() {
+    thd = 0.0;
+    thi = -1;
   }
+  __device__ __forceinline__ void retire(double d, int i) {
+    thd = d;
+    thi = i;
+  }
+  // the share's two smallest above the threshold, from the keys
+  __device__ __forceinline__ lmpc_knn_best2 rescan(int lane, double Lt, double qs, double qe) const {
+    lmpc_knn_best2 m;
+    m.clear();
+    for (int jr = lane; jr < n; jr += 64) candidates<true>(m, kl[jr], jr, Lt, qs, qe);
+    return m;
+  }
+  __device__ __forceinline__ double comp(int j, int k) const { return k == 0 ? kl[j].x : (k == 1 ? kl[j].y : xl[(size_t)j * 4 + k - 2]); }
+  __device__ __forceinline__ int code(int, int) const { return -1; }  // (no index mode on a ring)
+};
+
+__global__ __launch_bounds__(64) void lmpc_fleet_ss_query_kernel(lmpc_fleet_store st, int S, int K, double Lt,
+                                                                 const double* __restrict__ query, double* __restrict__ ss_x,
+                                                                 double* __restrict__ ss_j, int* __restrict__ n_found) {
+  // XCD-aware assignment, as in lmpc_ss_query_kernel: the 8-byte results of neighbouring cars share 64-byte lines of the
+  // [field][point][batch] arrays and are merged in one XCD's L2
+  const int B = st.B;
+  const int b = (int)(blockIdx.x & 7) * ((B + 7) >> 3) + (int)(blockIdx.x >> 3), lane = threadIdx.x;
+  if (b >= B) return;
+  lmpc_ss_fleet_ring ring{st.cnt[b] < st.R ? st.cnt[b] : st.R, st, b, st.head[b], 0, nullptr, nullptr, 0.0, -1};
+  lmpc_knn_query(ring, B, b, lane, S, K, Lt, query, ss_x, ss_j, n_found, nullptr, nullptr);
 }

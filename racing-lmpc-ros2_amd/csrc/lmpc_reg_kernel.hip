@@ -38,6 +38,7 @@
 
 #include "lmpc_device.h"
 #include "lmpc_dynamics.hip.h"
+#include "lmpc_reg_core.hip.h"
 
 __global__ void lmpc_reg_residual_kernel(lmpc_vehicle veh, int total, int as_written, const int* __restrict__ lap_end, const double* __restrict__ x,
                                          const double* __restrict__ u, const double* __restrict__ k,
@@ -60,203 +61,58 @@ __global__ void lmpc_reg_residual_kernel(lmpc_vehicle veh, int total, int as_wri
 }
 
 // tab[v][NF + NOUT] for the valid samples (valid[v] = index of a sample that is not the last of its lap), v < nvalid;
-// rows nvalid .. npad-1: features and residuals 0, |z|^2 = 1e30 (out of every bandwidth); zz[v] = |z_v|^2
+// rows nvalid .. npad-1: padding rows; zz[v] = |z_v|^2
 __global__ void lmpc_reg_pack_kernel(lmpc_regression_spec spec, int nvalid, int npad, const int* __restrict__ valid,
                                      const double* __restrict__ x, const double* __restrict__ u, const double* __restrict__ y,
                                      double* __restrict__ tab, double* __restrict__ zz) {
   const int v = blockIdx.x * blockDim.x + threadIdx.x;
   if (v >= npad) return;
-  const int ns = spec.n_in_state, nf = ns + spec.n_in_ctrl, nrow = nf + spec.n_out;
-  double* row = tab + (size_t)v * nrow;
-  if (v >= nvalid) {  // (features 0 with |z|^2 = 1e30: d^2 = 1e30 for every query, and no 0 * inf in the sums)
-    for (int f = 0; f < nf; ++f) row[f] = 0.0;
-    for (int o = 0; o < spec.n_out; ++o) row[nf + o] = 0.0;
-    zz[v] = 1e30;
+  double* row = tab + (size_t)v * (spec.n_in_state + spec.n_in_ctrl + spec.n_out);
+  if (v >= nvalid) {
+    zz[v] = lmpc_reg_table_pad_row(spec, row);
     return;
   }
   const int j = valid[v];
-  double s = 0.0;
-  for (int f = 0; f < nf; ++f) {
-    row[f] = f < ns ? x[(size_t)j * 6 + spec.in_state[f]] : u[(size_t)j * 2 + spec.in_ctrl[f - ns]];
-    s = __builtin_fma(row[f], row[f], s);
+  double xs[6], ys[6], us[2];
+#pragma unroll
+  for (int c = 0; c < 6; ++c) {
+    xs[c] = x[(size_t)j * 6 + c];
+    ys[c] = y[(size_t)j * 6 + c];
   }
-  zz[v] = s;
-  for (int o = 0; o < spec.n_out; ++o) row[nf + o] = y[(size_t)j * 6 + spec.out[o]];
+  us[0] = u[(size_t)j * 2];
+  us[1] = u[(size_t)j * 2 + 1];
+  zz[v] = lmpc_reg_table_row(spec, xs, us, ys, row);
 }
 
+// One lane per query (b, i) of any car, 64 queries per wave; the table is tab with row stride NF + NOUT and |z|^2 apart in zz.
 // WS_LAYOUT: update the handle's linearisation workspace [B][N-1][54]; otherwise the A/B/g arrays of lmpc_linearize_batch.
-// EXACT: the features are large against the bandwidth (lmpc_set_regression_laps decides: the abscissa s of the IAC track runs to
-// 2849 m), where the expanded d^2 below loses the weight to cancellation -- it stays the bandwidth screen, and inside the hit
-// branch each lane recomputes its weight from sum_f (z_f - q_f)^2.
+// EXACT (lmpc_reg_core.hip.h): lmpc_set_regression_laps decides, by the size of the features against the bandwidth.
 template <int NF, int NOUT, bool WS_LAYOUT, bool EXACT>
 __global__ __launch_bounds__(64) void lmpc_regress_kernel(int N, int B, lmpc_regression_spec spec, int npad,
                                                           const double* __restrict__ tab, const double* __restrict__ zz, const double* __restrict__ X_ref,
                                                           const double* __restrict__ U_ref, double* __restrict__ outA,
                                                           double* __restrict__ outB, double* __restrict__ outg) {
-  constexpr int NM = NF + 1;
-  constexpr int NQ = NM * (NM + 1) / 2;
   constexpr int NROW = NF + NOUT;
-  constexpr int UNR = 4;
+  constexpr int UNR = LMPC_REG_UNR;
   const int NS = N - 1;
   const long long gq = (long long)blockIdx.x * 64 + threadIdx.x;
   const bool live = gq < (long long)B * NS;
   const long long gqc = live ? gq : 0;
   const int b = (int)(gqc / NS), i = (int)(gqc - (long long)b * NS);
-  const int ns = spec.n_in_state;
-  double q[NF];
-#pragma unroll
-  for (int f = 0; f < NF; ++f)
-    q[f] = f < ns ? X_ref[((size_t)spec.in_state[f] * N + i) * B + b] : U_ref[((size_t)spec.in_ctrl[f - ns] * NS + i) * B + b];
-  const double h = spec.dist_max, h2 = h * h, nih2 = -1.0 / h2, c0 = 0.75 / h;
-  // d^2 = (|q|^2 + |z|^2) - 2 z.q: one add and NF FMAs per pair instead of NF subtractions and NF FMAs (|z|^2 is formed on the
-  // scalar side of the loop: it is the same for every lane).  A dead lane's query sits out of every bandwidth.
-  double qm2[NF], qq = 0.0;
-#pragma unroll
-  for (int f = 0; f < NF; ++f) {
-    if (!live) q[f] = 1e30;
-    qm2[f] = -2.0 * q[f];
-    qq = __builtin_fma(q[f], q[f], qq);
-  }
-  double acc[NQ + NOUT * NM];
-#pragma unroll
-  for (int a = 0; a < NQ + NOUT * NM; ++a) acc[a] = 0.0;
+  lmpc_reg_lane<NF, NOUT> L;
+  lmpc_reg_query(L, spec, N, B, b, i, live, X_ref, U_ref);
   for (int j0 = 0; j0 < npad; j0 += UNR) {
-    double row[UNR][NROW], sq[UNR];
+    double row[UNR][NROW], zn[UNR];
 #pragma unroll
     for (int t = 0; t < UNR; ++t)
 #pragma unroll
       for (int c = 0; c < NROW; ++c) row[t][c] = tab[(size_t)(j0 + t) * NROW + c];  // wave-uniform address: scalar loads
-    double zn[UNR];
 #pragma unroll
     for (int t = 0; t < UNR; ++t) zn[t] = zz[j0 + t];
-    // every row of the group is "used" here, in scalar registers: left alone, the compiler loads a sample's features, waits, tests
-    // the distance, and only inside the hit branch loads its residuals and waits again -- two exposed scalar-cache round trips per
-    // sample instead of one per group
-    // (where the group fits the scalar registers: (8, 6) would need 120 of them)
-    if constexpr (2 * (NROW + 1) * UNR <= 80) {
-#pragma unroll
-      for (int t = 0; t < UNR; ++t) {
-#pragma unroll
-        for (int c = 0; c < NROW; ++c) asm volatile("" : "+s"(row[t][c]));
-        asm volatile("" : "+s"(zn[t]));
-      }
-    }
-#pragma unroll
-    for (int t = 0; t < UNR; ++t) {
-      double s = qq + zn[t];
-#pragma unroll
-      for (int f = 0; f < NF; ++f) s = __builtin_fma(row[t][f], qm2[f], s);
-      // K / c0 = (1 - (d/h)^2)^2 inside the bandwidth, 0 outside (safe_set.cpp:84-87): max(1 - d^2/h^2, 0)^2; c0 = 0.75/h
-      // multiplies the sums once, after the loop
-      sq[t] = fmax(__builtin_fma(s, nih2, 1.0), 0.0);
-    }
-#pragma unroll
-    for (int t = 0; t < UNR; ++t) {
-      if (!__any(sq[t] > 0.0)) continue;
-      double wt = sq[t];
-      if constexpr (EXACT) {
-        // |q|^2 + |z|^2 - 2 z.q carries a rounding error of a few ulp of |q|^2 + |z|^2 (4e-9 at s = 2849 m against h^2 = 0.36).
-        // A sample one form puts inside the bandwidth and the other outside weighs (delta / h^2)^2: negligible either way.
-        // (z_f - q_f from qm2 = -2 q, exactly: q itself need not stay live across the loop -- it would take the (8, 6) instance past
-        // the 256-VGPR budget and halve its occupancy)
-        double s = 0.0;
-#pragma unroll
-        for (int f = 0; f < NF; ++f) {
-          const double df = __builtin_fma(qm2[f], 0.5, row[t][f]);
-          s = __builtin_fma(df, df, s);
-        }
-        wt = fmax(__builtin_fma(s, nih2, 1.0), 0.0);
-      }
-      const double w = wt * wt;
-      double wm[NM];
-#pragma unroll
-      for (int r = 0; r < NF; ++r) wm[r] = w * row[t][r];
-      wm[NF] = w;
-      int a = 0;
-#pragma unroll
-      for (int r = 0; r < NM; ++r)
-#pragma unroll
-        for (int c = r; c < NM; ++c) {
-          acc[a] += c < NF ? wm[r] * row[t][c] : wm[r];
-          ++a;
-        }
-#pragma unroll
-      for (int o = 0; o < NOUT; ++o) {
-        const double yo = row[t][NF + o];
-#pragma unroll
-        for (int r = 0; r < NM; ++r) acc[a++] += wm[r] * yo;
-      }
-    }
+    lmpc_reg_pin<NF, NOUT>(row, zn);
+    lmpc_reg_group<NF, NOUT, EXACT>(L, row, zn);
   }
-#pragma unroll
-  for (int a = 0; a < NQ + NOUT * NM; ++a) acc[a] *= c0;
-  // "if there are no points left, skip the regression" (safe_set.cpp:207-210): the weight sum is M'KM's last entry
-  if (!live || !(acc[NQ - 1] > 0.0)) return;
-  // Cholesky of Q = M'KM + 1e-3 I, this lane's own system
-  double Lc[NM * NM];
-  {
-    double Q[NM * NM];
-    int a = 0;
-#pragma unroll
-    for (int r = 0; r < NM; ++r)
-#pragma unroll
-      for (int c = r; c < NM; ++c) {
-        Q[r * NM + c] = acc[a] + (r == c ? 1e-3 : 0.0);
-        Q[c * NM + r] = Q[r * NM + c];
-        ++a;
-      }
-#pragma unroll
-    for (int jn = 0; jn < NM; ++jn) {
-      double dd = Q[jn * NM + jn];
-#pragma unroll
-      for (int k = 0; k < jn; ++k) dd -= Lc[jn * NM + k] * Lc[jn * NM + k];
-      const double id = 1.0 / sqrt(dd);
-      Lc[jn * NM + jn] = id;  // reciprocal of the pivot
-#pragma unroll
-      for (int r = jn + 1; r < NM; ++r) {
-        double tt = Q[r * NM + jn];
-#pragma unroll
-        for (int k = 0; k < jn; ++k) tt -= Lc[r * NM + k] * Lc[jn * NM + k];
-        Lc[r * NM + jn] = tt * id;
-      }
-    }
-  }
-#pragma unroll
-  for (int o = 0; o < NOUT; ++o) {
-    double yv[NM], R[NM];
-#pragma unroll
-    for (int r = 0; r < NM; ++r) {
-      double tt = spec.as_written ? -acc[NQ + o * NM + r] : acc[NQ + o * NM + r];  // b = M'K y  (as written: -M'K y)
-#pragma unroll
-      for (int k = 0; k < r; ++k) tt -= Lc[r * NM + k] * yv[k];
-      yv[r] = tt * Lc[r * NM + r];
-    }
-#pragma unroll
-    for (int r = NM - 1; r >= 0; --r) {
-      double tt = yv[r];
-#pragma unroll
-      for (int k = r + 1; k < NM; ++k) tt -= Lc[k * NM + r] * R[k];
-      R[r] = tt * Lc[r * NM + r];
-    }
-    const int rowo = spec.out[o];
-#pragma unroll
-    for (int f = 0; f < NM; ++f) {
-      if (f < NF) {
-        const int col = f < ns ? spec.in_state[f] : 6 + spec.in_ctrl[f - ns];  // column of [A B]
-        if (WS_LAYOUT)
-          outA[((size_t)b * NS + i) * LMPC_LIN_RECORD + col * 6 + rowo] += R[f];
-        else if (col < 6)
-          outA[((size_t)(rowo * 6 + col) * NS + i) * B + b] += R[f];
-        else
-          outB[((size_t)(rowo * 2 + (col - 6)) * NS + i) * B + b] += R[f];
-      } else {
-        if (WS_LAYOUT)
-          outA[((size_t)b * NS + i) * LMPC_LIN_RECORD + 48 + rowo] += R[f];
-        else
-          outg[((size_t)rowo * NS + i) * B + b] += R[f];
-      }
-    }
-  }
+  lmpc_reg_finish<NF, NOUT, WS_LAYOUT>(L, spec, N, B, b, i, live, outA, outB, outg);
 }
 
 #define LMPC_REG_INSTANTIATE(NF, NOUT, WS, EXACT)                                                                             \

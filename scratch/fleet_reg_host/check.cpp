@@ -1,4 +1,4 @@
-// check.cpp -- csrc/lmpc_fleet_reg_kernel.hip compiled for the HOST (hip/hip_runtime.h in this directory stands in for the runtime)
+// check.cpp -- csrc/lmpc_fleet_reg_kernel.hip and csrc/lmpc_reg_kernel.hip compiled for the HOST (hip/hip_runtime.h in this directory stands in for the runtime)
 // and run one thread at a time on a hand-built fleet store, before the kernels are ever launched on a device.  Built with
 // -fsanitize=address,undefined, so an out-of-bounds row index is a crash here.  check.py writes the cases, runs this program and
 // holds its output to oracle.regression; see there for the build line.
@@ -8,7 +8,10 @@
 //   out: A, Bm, g after each phase (the arrays of lmpc_linearize_batch)
 // Checked here, beside the bounds: the workspace layout against the array layout bit for bit; a car whose lap_count did not move is
 // NOT packed again (a sentinel left in its table survives) unless every stamp was invalidated; counters of a store that hold garbage
-// (head, cnt, npts, nrow out of range) read and write nothing outside the car's slots and table.
+// (head, cnt, npts, nrow out of range) read and write nothing outside the car's slots and table; the shared-store kernels of
+// lmpc_reg_kernel.hip (residual, pack, lmpc_regress_kernel) on each car's laps in turn, sized as lmpc_set_regression_laps sizes them:
+// the EXACT instances return the fleet kernel's bits for that car's queries (one core, the same rows in the same order), the
+// expanded-distance instances agree to the oracle's bound.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -16,6 +19,7 @@
 
 #define LMPC_FLEET_REG_NO_LAUNCHER
 #include "lmpc_fleet_reg_kernel.hip"
+#include "lmpc_reg_kernel.hip"
 
 dim3 blockIdx, threadIdx, blockDim;
 
@@ -80,6 +84,82 @@ static void run_regress(int N, int B, const lmpc_regression_spec& spec, int cap,
       else
         lmpc_fleet_regress_kernel<8, 6, WS>(N, B, chunks, spec, cap, tab, nrow, X, U, A, Bm, g);
     }
+}
+
+// The shared-store path on car c's closed laps (oldest first, as its table has them; a lap of one sample is refused by
+// lmpc_set_regression_laps and adds nothing to the car's table): every query of the batch runs against the table, car c's own
+// queries are held to what the fleet kernel left in (A, Bm, g).  Returns the number of findings.
+template <int NF, int NOUT>
+static int run_shared(const Store& s, int c, const lmpc_vehicle& veh, const lmpc_regression_spec& spec, int N, const double* X, const double* U,
+                      const std::vector<double>& A0, const std::vector<double>& B0, const std::vector<double>& g0, const std::vector<double>& A,
+                      const std::vector<double>& Bm, const std::vector<double>& g) {
+  const int B = s.st.B, R1 = s.st.R + 1, C = s.st.C, NS = N - 1, cnt = s.st.cnt[c], head = s.st.head[c];
+  std::vector<double> x, u, k, t;
+  std::vector<int> end, valid;
+  for (int a = 0; a < cnt; ++a) {
+    const int sl = ((head - cnt + a) % R1 + R1) % R1, n = s.st.npts[(size_t)c * R1 + sl];
+    if (n < 2) continue;
+    const size_t r0 = ((size_t)c * R1 + sl) * C;
+    for (int j = 0; j < n; ++j) {
+      x.push_back(s.key[r0 + j].x), x.push_back(s.key[r0 + j].y);
+      for (int q = 0; q < 4; ++q) x.push_back(s.xr[(r0 + j) * 4 + q]);
+      u.push_back(s.aux[(r0 + j) * 4]), u.push_back(s.aux[(r0 + j) * 4 + 1]);
+      k.push_back(s.aux[(r0 + j) * 4 + 2]), t.push_back(s.aux[(r0 + j) * 4 + 3]);
+      if (j + 1 < n) valid.push_back((int)end.size());
+      end.push_back(j + 1 == n);
+    }
+  }
+  const int total = (int)end.size(), nvalid = (int)valid.size(), npad = (nvalid + 3) / 4 * 4;
+  if (!total) return 0;
+  std::vector<double> y((size_t)total * 6, NAN), tab((size_t)npad * (NF + NOUT + 1), NAN);
+  double* zz = tab.data() + (size_t)npad * (NF + NOUT);
+  blockDim = dim3(256);
+  for (int j = 0; j < (total + 255) / 256 * 256; ++j) {
+    blockIdx = dim3((unsigned)j / 256), threadIdx = dim3((unsigned)j % 256);
+    lmpc_reg_residual_kernel(veh, total, spec.as_written, end.data(), x.data(), u.data(), k.data(), t.data(), y.data());
+  }
+  for (int v = 0; v < (npad + 255) / 256 * 256; ++v) {
+    blockIdx = dim3((unsigned)v / 256), threadIdx = dim3((unsigned)v % 256);
+    lmpc_reg_pack_kernel(spec, nvalid, npad, valid.data(), x.data(), u.data(), y.data(), tab.data(), zz);
+  }
+  int bad = 0;
+  blockDim = dim3(64);
+  const unsigned blocks = (unsigned)((B * NS + 63) / 64);
+  for (int exact = 1; exact >= 0; --exact) {
+    std::vector<double> As(A0), Bs(B0), gs(g0), ws((size_t)B * NS * LMPC_LIN_RECORD, 0.0);
+    for (unsigned blk = 0; blk < blocks; ++blk)
+      for (unsigned th = 0; th < 64; ++th) {
+        blockIdx = dim3(blk), threadIdx = dim3(th);
+        if (exact) {
+          lmpc_regress_kernel<NF, NOUT, false, true>(N, B, spec, npad, tab.data(), zz, X, U, As.data(), Bs.data(), gs.data());
+          lmpc_regress_kernel<NF, NOUT, true, true>(N, B, spec, npad, tab.data(), zz, X, U, ws.data(), nullptr, nullptr);
+        } else {
+          lmpc_regress_kernel<NF, NOUT, false, false>(N, B, spec, npad, tab.data(), zz, X, U, As.data(), Bs.data(), gs.data());
+          lmpc_regress_kernel<NF, NOUT, true, false>(N, B, spec, npad, tab.data(), zz, X, U, ws.data(), nullptr, nullptr);
+        }
+      }
+    // car c's queries: the array layout against the fleet kernel's result, the record (started from zero) against its increment
+    double scale = 1.0;
+    for (int pass = 0; pass < 2; ++pass)
+      for (int i = 0; i < NS; ++i) {
+        const double* rec = &ws[((size_t)c * NS + i) * LMPC_LIN_RECORD];
+        for (int e = 0; e < 54; ++e) {
+          const int col = e / 6, r = e % 6;  // e < 48: [A B] column col, row r; then g
+          const size_t o = e >= 48 ? ((size_t)(e - 48) * NS + i) * B + c
+                                   : (col < 6 ? ((size_t)(r * 6 + col) * NS + i) * B + c : ((size_t)(r * 2 + col - 6) * NS + i) * B + c);
+          const double got = e >= 48 ? gs[o] : (col < 6 ? As[o] : Bs[o]), ref = e >= 48 ? g[o] : (col < 6 ? A[o] : Bm[o]);
+          const double was = e >= 48 ? g0[o] : (col < 6 ? A0[o] : B0[o]);
+          if (!pass) {
+            scale = std::fmax(scale, 1.0 + std::fabs(ref));
+            continue;
+          }
+          if (exact ? memcmp(&got, &ref, 8) != 0 : !(std::fabs(got - ref) <= 1e-9 * scale)) ++bad;
+          if (!(std::fabs(was + rec[e] - got) <= 1e-12 * scale)) ++bad;
+        }
+      }
+  }
+  if (bad) fprintf(stderr, "shared kernels on car %d's laps: %d findings\n", c, bad);
+  return bad;
 }
 
 int main(int argc, char** argv) {
@@ -185,6 +265,9 @@ int main(int argc, char** argv) {
         for (int r = 0; r < 6; ++r)
           if (memcmp(&g[((size_t)r * NS + i) * B + b], &rec[48 + r], 8)) ++bad;
       }
+    for (int c = 0; c < B; ++c)
+      bad += nf == 5 ? run_shared<5, 3>(s, c, veh, spec, N, X.data(), U.data(), A0, B0, g0, A, Bm, g)
+                     : run_shared<8, 6>(s, c, veh, spec, N, X.data(), U.data(), A0, B0, g0, A, Bm, g);
     fwrite(A.data(), 8, nA, fout), fwrite(Bm.data(), 8, nB, fout), fwrite(g.data(), 8, nG, fout);
   }
   // garbage in every counter: nothing outside the slots is read, nothing outside the table written (the sanitizer's to say)

@@ -1,4 +1,4 @@
-"""The per-car regression kernels on the CPU, before any launch: writes the cases, runs ./check (check.cpp: the kernel file compiled for
+"""The regression kernels (per car, and the shared-store ones) on the CPU, before any launch: writes the cases, runs ./check (check.cpp: the kernel file compiled for
 the host, address and undefined-behaviour sanitizers on) and holds what it returns to oracle.regression at the GPU test's bound,
 1e-9 (1 + max|ref|), untouched queries bit-identical.  From the repository root:
 
@@ -8,7 +8,10 @@ the host, address and undefined-behaviour sanitizers on) and holds what it retur
 
 Phases of one store (R = 3, C = 24): (0) every car loaded -- paddings 0..3, a car without a lap, one-sample and two-sample laps, full
 rings; (1) every other car gets a new ring and a moved lap_count, the rest must not be packed again and must return the same bits;
-(2) every car gets other laps under the SAME lap_count with every stamp invalidated (a reset and a load of as many laps)."""
+(2) every car gets other laps under the SAME lap_count with every stamp invalidated (a reset and a load of as many laps).
+After each phase check.cpp also runs the shared-store kernels of lmpc_reg_kernel.hip (residual, pack, lmpc_regress_kernel<5, 3> or
+<8, 6>, both layouts, EXACT and not) on every car's laps in turn and holds that car's queries to the per-car kernel's result: the
+EXACT instances bit for bit, the others at 1e-9 (1 + max|ref|)."""
 import ctypes as C
 import struct
 import subprocess
