@@ -174,6 +174,8 @@ int lmpc_linearize_batch(lmpc_handle* h, int32_t batch, const double* X_ref, con
 /* RacingMPC::solve for `batch` independent problems (racing_mpc.cpp:209-372).
  *   in : x_ic [6][B], u_ic [2][B], X_ref [6][N][B], U_ref [2][N-1][B], T_ref [N-1][B],
  *        bound_left/bound_right/curvatures/vel_ref [N][B], total_length (scalar, host value)
+ *        T_ref is per stage and per problem, every entry > 0: t_i = T_ref[i][b] is the integration step from knot i to knot i + 1
+ *        and the step of stage i's rate row u_{i-1} + dU_i t_i = u_i, u_{-1} = u_ic (racing_mpc.cpp:190-196), in every entry point.
  *        ss_x [6][S][B], ss_j [S][B]  (learning only, already padded/truncated to S and
  *        with J - J[0] applied: racing_mpc.cpp:263-280; NULL for tracking)
  *   out: X_optm [6][N][B], U_optm [2][N-1][B], dU_optm [2][N-1][B],

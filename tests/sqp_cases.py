@@ -200,6 +200,11 @@ def chain_counts(logs) -> dict:
 B_SAMPLE = 65
 TRACKING = {"tracking N = 3": (3, "rk4"), "tracking N = 8": (8, "rk4"), "tracking N = 20": (20, "rk4"), "tracking N = 8, Euler": (8, "euler")}
 LEARNING = {"learning (3, 32)": (3, 1, 81), "learning (10, 32)": (10, 1, 80), "learning (10, 96)": (10, 3, 80)}
+# The N = 20 tracking sample on a time step that differs per stage and per problem (tests/timestep_cases.py draw_t_ref: 0.0125 .. 0.05,
+# problem 0 strictly increasing): t_i is the step of the line search's rollout, of the linearisation and of the rate rows.  The start
+# (X_ref, U_ref) stays the rollout at 0.025, so the first iterate has a defect at the steps it is now held to.
+NONUNIFORM_T = {"tracking N = 20, non-uniform T_ref": 9320}
+TRACKING.update({name: (20, "rk4") for name in NONUNIFORM_T})
 SAMPLES = tuple(TRACKING) + tuple(LEARNING)
 _cache: dict = {}
 
@@ -215,6 +220,10 @@ def sample(pkg, name: str) -> dict:
         u_lo, u_hi, _, _ = Q.effective_bounds(cfg, veh)
         x, u = pkg.workloads.sample_initial_states("barc", B_SAMPLE, tr["L"], u_lo, u_hi, 8)
         inp = S.cold_start_inputs(cfg, veh, tr, x, u, 0.025)
+        if name in NONUNIFORM_T:
+            from timestep_cases import draw_t_ref
+
+            inp["T_ref"] = draw_t_ref(N, B_SAMPLE, NONUNIFORM_T[name])
         out = dict(cfg=cfg, veh=veh, inp=inp, ss_x=None, ss_j=None, S=0, laps=None,
                    preset=(pkg.presets.barc_tracking_mpc(N), dict(pkg.presets.barc_vehicle(), integrator=integrator)))
     else:
