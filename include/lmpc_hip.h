@@ -763,6 +763,42 @@ int lmpc_ekf_update_batch(lmpc_handle* h, int32_t batch, int32_t obs_id, const d
  * `initialized` to HOST values.  Any pointer NULL. */
 int lmpc_ekf_get(lmpc_handle* h, int32_t batch, double* x, double* P, double* K, int64_t* timestamp_ns, int32_t* initialized);
 
+/* Batched time-varying LQR: RacingLQR::solve (mpc/racing_lqr, racing_lqr.cpp:45-96), ONE CONTROLLER PER CAR on the device, fp64,
+ * over the handle's vehicle at curvature k = 0 (dynamics_jacobian() and rk4_ are called without k: rows 0 - 2 are global X, Y, yaw,
+ * as in the filter above).  Per car, with P = Qf and k = N-2 .. 0:
+ *   (Ac, Bc) = df/dx, df/du of the CONTINUOUS dynamics at (X_ref[:,k], U_ref[:,k]);
+ *   [A B; 0 I] = expm([Ac Bc; 0 0] dt), the exact zero-order hold (lmpc_utils/src/utils.cpp:52-65);
+ *   K_k = solve(R + B'PB, B'PA), a general 2 x 2 solve;   P <- Q + A'P(A - B K_k), not symmetrised;
+ * then X[:,0] = x_ic, U[:,k] = U_ref[:,k] - K_k (X[:,k] - X_ref[:,k]) (the yaw difference is not wrapped, as written) and
+ * X[:,k+1] = rk4(f, X[:,k], U[:,k], dt, k = 0) -- ALWAYS RK4: the class builds its own integrator (racing_lqr.cpp:36) and does not
+ * read lmpc_vehicle.integrator.  Q, R, Qf are general dense matrices, row-major; nothing makes or assumes them symmetric.  There
+ * are no input or state bounds.  N is the controller's own, independent of the handle's horizon; N = 2 is the smallest problem.
+ * Not upstream: the batch, K and P0 = P after the last step as outputs, and the per-car flag.
+ * expm: the matrix is halved until its infinity norm is at most 1/2, a Taylor polynomial of degree 14, then squared back.  The
+ * halvings are limited to 20; a stage whose norm is larger than 2^19, or not finite, is given NaN and its car ends flagged.  Every
+ * loop count is a constant or N, so a NaN or huge input cannot lengthen a solve, and one car's NaN never touches another car.
+ * Only lmpc_lqr_create allocates (the workspace of max_batch cars, 60 (N-1) max_batch + 76 doubles; it synchronises the handle's
+ * stream).  Array arguments are DEVICE pointers, batch axis fastest; a solve is two launches on the handle's stream, no host round trip.
+ * LMPC_ERR_ARGUMENT, nothing written: N < 2, dt <= 0 or not finite, max_batch < 1, batch outside 1 .. max_batch, a null required
+ * pointer, a solve without a controller.
+ * WHERE IT HOLDS: an LQR has no bounds, and the rollout is RK4 on the stiff single-track model: past 216 dt / vx = 2.78 (BARC) the
+ * integration itself is unstable, and a reference the car cannot stay near (BARC N = 81 at dt = 0.01; IAC from 15 m/s with metre
+ * offsets) makes the closed loop sensitive to rounding.  The tests are pinned to references where fp64 and extended precision agree. */
+typedef struct lmpc_lqr_config {
+  int32_t N;        /* knot points, >= 2 */
+  int32_t reserved; /* 0 */
+  double dt;
+  double Q[36];     /* row-major */
+  double R[4];
+  double Qf[36];
+} lmpc_lqr_config;
+#define LMPC_LQR_FLAG_NOT_FINITE 1 /* this car's X_optm, U_optm, K or P0 holds a NaN or Inf */
+int lmpc_lqr_create(lmpc_handle* h, int32_t max_batch, const lmpc_lqr_config* cfg); /* allocates the workspace; replaces an earlier one */
+int lmpc_lqr_destroy(lmpc_handle* h);                                               /* lmpc_destroy does it too */
+int lmpc_lqr_solve_batch(lmpc_handle* h, int32_t batch, const double* x_ic /* [6][B] */, const double* X_ref /* [6][N][B] */,
+                         const double* U_ref /* [2][N-1][B] */, double* X_optm /* [6][N][B] */, double* U_optm /* [2][N-1][B] */,
+                         double* K /* [2][6][N-1][B] or NULL */, double* P0 /* [36][B] or NULL */, int32_t* flags /* [B] or NULL */);
+
 #ifdef __cplusplus
 }
 #endif

@@ -31,8 +31,10 @@ _ABI_SYMBOLS = ("lmpc_create", "lmpc_destroy", "lmpc_last_error", "lmpc_set_stre
                 "lmpc_spline_track_create", "lmpc_spline_track_destroy", "lmpc_spline_track_tabulate", "lmpc_track_sample_batch",
                 "lmpc_global_to_frenet_batch", "lmpc_frenet_to_global_batch",
                 "lmpc_ekf_create", "lmpc_ekf_destroy", "lmpc_ekf_register_observation", "lmpc_ekf_initialize", "lmpc_ekf_set_state",
-                "lmpc_ekf_update_control", "lmpc_ekf_update_batch", "lmpc_ekf_get")
+                "lmpc_ekf_update_control", "lmpc_ekf_update_batch", "lmpc_ekf_get",
+                "lmpc_lqr_create", "lmpc_lqr_destroy", "lmpc_lqr_solve_batch")
 EKF_FALLBACK, EKF_R_REPAIRED, EKF_NOT_FINITE = 1, 2, 4   # bits of the per-car flags of Solver.ekf_update
+LQR_NOT_FINITE = 1   # per-car flag of Solver.lqr_solve: the car's X_optm, U_optm, K or P0 holds a NaN or Inf
 
 
 class LmpcError(RuntimeError):
@@ -68,6 +70,12 @@ class CRegressionSpec(C.Structure):
 class CEkfConfig(C.Structure):
     """lmpc_ekf_config: the filter's start, process noise and clip (ekf_state_estimator_config.hpp)."""
     _fields_ = [("x0", C.c_double * 6), ("P0", C.c_double * 36), ("Q", C.c_double * 36), ("x_min", C.c_double * 6), ("x_max", C.c_double * 6)]
+
+
+class CLqrConfig(C.Structure):
+    """lmpc_lqr_config: horizon, time step and the three general dense weights, row-major (racing_lqr_config.hpp)."""
+    _fields_ = [("N", C.c_int32), ("reserved", C.c_int32), ("dt", C.c_double), ("Q", C.c_double * 36), ("R", C.c_double * 4),
+                ("Qf", C.c_double * 36)]
 
 
 class CTrack(C.Structure):
@@ -907,3 +915,51 @@ class Solver:
         ns, init = C.c_int64(0), C.c_int32(0)
         self._check(self.lib.lmpc_ekf_get(self._h, C.c_int32(B), _ptr(x), _ptr(P), _ptr(K), C.byref(ns), C.byref(init)), "lmpc_ekf_get")
         return {"x": x, "P": P, "K": K, "timestamp_ns": int(ns.value), "initialized": bool(init.value)}
+
+    # ---- batched time-varying LQR, one controller per car (racing_lqr.cpp:45-96; include/lmpc_hip.h) ----
+    def lqr_create(self, cfg: dict, max_batch: int):
+        """lmpc_lqr_create: controllers for up to `max_batch` cars over this solver's vehicle.  cfg: N (its own horizon, >= 2), dt,
+        Q [6,6], R [2,2], Qf [6,6] -- general dense matrices, nothing is symmetrised (presets.sample_lqr).  Allocates the workspace
+        and replaces an earlier controller."""
+        import numpy as np
+
+        self.use_current_stream()
+        c = CLqrConfig()
+        c.N, c.reserved, c.dt = int(cfg["N"]), 0, float(cfg["dt"])
+        for name, n in (("Q", 36), ("R", 4), ("Qf", 36)):
+            a = np.asarray(cfg[name], dtype=np.float64).reshape(-1)
+            if a.size != n:
+                raise ValueError(f"lqr_create: {name} needs {n} values")
+            getattr(c, name)[:] = [float(e) for e in a]
+        self._check(self.lib.lmpc_lqr_create(self._h, C.c_int32(int(max_batch)), C.byref(c)), "lmpc_lqr_create")
+        self._lqr_N = int(cfg["N"])
+
+    def lqr_destroy(self):
+        self._check(self.lib.lmpc_lqr_destroy(self._h), "lmpc_lqr_destroy")
+        self._lqr_N = None
+
+    def lqr_solve(self, x_ic, X_ref, U_ref, out=None, gains=False):
+        """lmpc_lqr_solve_batch: x_ic [6][B], X_ref [6][N][B], U_ref [2][N-1][B] -> {"X_optm" [6][N][B], "U_optm" [2][N-1][B],
+        "u" [2][B] (a view of U_optm), "flags" int32 [B]: LQR_NOT_FINITE}, and with gains=True "K" [2][6][N-1][B] and "P0" [6][6][B].
+        `out` = such a dict reuses the caller's buffers; its "K", "P0" and "flags" may be None or missing and are then not asked of
+        the kernels.  Two launches, asynchronous."""
+        torch = self._torch
+        self.use_current_stream()
+        x_ic, X_ref, U_ref = self._t(x_ic), self._t(X_ref), self._t(U_ref)
+        N = getattr(self, "_lqr_N", None)
+        B = x_ic.shape[-1]
+        if N is not None and (tuple(x_ic.shape) != (6, B) or tuple(X_ref.shape) != (6, N, B) or tuple(U_ref.shape) != (2, N - 1, B)):
+            raise ValueError(f"lqr_solve: x_ic [6][B], X_ref [6][{N}][B], U_ref [2][{N - 1}][B] with one B, got "
+                             f"{tuple(x_ic.shape)}, {tuple(X_ref.shape)}, {tuple(U_ref.shape)}")
+        if out is None:
+            kw = dict(dtype=torch.float64, device=self.device)
+            n = N if N is not None else X_ref.shape[1]
+            out = {"X_optm": torch.empty((6, n, B), **kw), "U_optm": torch.empty((2, n - 1, B), **kw),
+                   "flags": torch.empty((B,), dtype=torch.int32, device=self.device)}
+            if gains:
+                out["K"], out["P0"] = torch.empty((2, 6, n - 1, B), **kw), torch.empty((6, 6, B), **kw)
+        rc = self.lib.lmpc_lqr_solve_batch(self._h, C.c_int32(B), _ptr(x_ic), _ptr(X_ref), _ptr(U_ref), _ptr(out["X_optm"]), _ptr(out["U_optm"]),
+                                           _ptr(out.get("K")), _ptr(out.get("P0")), _ptr(out.get("flags")))
+        self._check(rc, "lmpc_lqr_solve_batch")
+        out["u"] = out["U_optm"][:, 0, :]
+        return out

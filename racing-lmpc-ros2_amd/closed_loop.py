@@ -531,3 +531,37 @@ def run_lmpc_fleet(tracker, learner, track: dict, x0, u0, warm_laps: int = 2, le
             "lap_kind": [["lmpc" if v else "tracking" for v in lk[:n_closed[b], b]] for b in range(B)],
             "worst_excess": worst_excess, "n_fail": n_fail, "n_dropped": stats["n_dropped"].clone(),
             "laps_in_ring": stats["laps_in_ring"].clone(), "steps": k + 1, "x": x, "trace": trace}
+
+
+def run_lqr(solver, x0, X_traj, U_traj, steps: int):
+    """Receding-horizon LQR tracking of a long reference, the loop of the reference's own test (test_racing_lqr.cpp): period t solves
+    on the window t .. t+N-1 of the trajectory (N = the horizon of solver.lqr_create, which the caller has made for at least B cars)
+    and the plan's second knot X_optm[:, 1] -- one RK4 step of the model under u = U_optm[:, 0] -- is the next state: the model is
+    the plant.  x0 [6][B]; X_traj [B][6][M], U_traj [B][2][M-1] with M >= steps + N - 1.  The windows are slices of one device
+    copy of the trajectory, batch axis last; nothing goes through the host inside the loop.
+    Returns {"X" [6][steps+1][B] the states from x0 on, "U" [2][steps][B] the applied inputs, "flags" int32 [B] the OR of every
+    solve's flags (LQR_NOT_FINITE)}."""
+    import torch
+
+    if getattr(solver, "_lqr_N", None) is None:
+        raise ValueError("run_lqr: no controller (Solver.lqr_create)")
+    N = int(solver._lqr_N)
+    X_all = solver._t(X_traj).permute(1, 2, 0).contiguous()  # [6][M][B]
+    U_all = solver._t(U_traj).permute(1, 2, 0).contiguous()  # [2][M-1][B]
+    M = X_all.shape[1]
+    if M < steps + N - 1 or U_all.shape[1] < steps + N - 2:
+        raise ValueError(f"run_lqr: {steps} periods of horizon {N} need a reference of {steps + N - 1} knots, got {M}")
+    x = solver._t(x0).clone()
+    B = x.shape[1]
+    kw = dict(dtype=torch.float64, device=x.device)
+    X, U = torch.empty((6, steps + 1, B), **kw), torch.empty((2, steps, B), **kw)
+    flags_or = torch.zeros(B, dtype=torch.int32, device=x.device)
+    out = None
+    X[:, 0] = x
+    for t in range(steps):
+        out = solver.lqr_solve(x, X_all[:, t:t + N].contiguous(), U_all[:, t:t + N - 1].contiguous(), out=out)
+        flags_or |= out["flags"]
+        U[:, t] = out["u"]
+        x = out["X_optm"][:, 1].contiguous()
+        X[:, t + 1] = x
+    return {"X": X, "U": U, "flags": flags_or}

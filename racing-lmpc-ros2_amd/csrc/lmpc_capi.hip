@@ -22,6 +22,7 @@
 
 #include "lmpc_device.h"
 #include "lmpc_ekf.h"
+#include "lmpc_lqr.h"
 #include "lmpc_fleet_reg.h"
 #include "lmpc_fleet_ss.h"
 
@@ -128,6 +129,9 @@ struct __attribute__((visibility("hidden"))) lmpc_handle {  // (its members are 
   lmpc_ekf_config ekf_cfg{};
   bool ekf_initialized = false;  // initialized_ upstream: registration is closed, updates are open
   int64_t ekf_ns = 0;            // nanosec_: the time of the last update
+  // batched time-varying LQR (lmpc_lqr_create): one controller per car, csrc/lmpc_lqr.h
+  lmpc_lqr_store lqr{};     // raw copies of the owner below, as the kernels take them
+  dev_buf<double> lqr_ws;   // cfg [76] | AB [N-1][8][max_batch][6] | K [N-1][2][max_batch][6]
   // staging for the single-problem host entry points (lmpc_solve_host, lmpc_ss_query_host): device buffers and PINNED
   // host mirrors, all sized and allocated by lmpc_create -- the per-step path of one controller allocates nothing
   dev_buf<double> stage_dev;
@@ -1921,6 +1925,58 @@ int lmpc_ekf_get(lmpc_handle* h, int32_t batch, double* x, double* P, double* K,
   if (K && h->ekf.nzsum) HIP_TRY(h, hipMemcpyAsync(K, h->ekf.K, 6 * (size_t)h->ekf.nzsum * Bz, hipMemcpyDeviceToDevice, h->stream));
   if (timestamp_ns) *timestamp_ns = h->ekf_ns;
   if (initialized) *initialized = h->ekf_initialized ? 1 : 0;
+  return LMPC_OK;
+}
+
+// ---- batched time-varying LQR, one controller per car (csrc/lmpc_lqr.h, csrc/lmpc_lqr_kernel.hip) ----
+int lmpc_lqr_destroy(lmpc_handle* h) {
+  if (!h) return LMPC_ERR_ARGUMENT;
+  if (!h->lqr.max_batch) return LMPC_OK;
+  (void)hipSetDevice(h->device);
+  (void)hipStreamSynchronize(h->stream);
+  h->lqr_ws.release();
+  h->lqr = lmpc_lqr_store{};
+  return LMPC_OK;
+}
+
+int lmpc_lqr_create(lmpc_handle* h, int32_t max_batch, const lmpc_lqr_config* cfg) {
+  if (!h) return LMPC_ERR_ARGUMENT;
+  if (!cfg) return fail(h, LMPC_ERR_ARGUMENT, "lmpc_lqr_create: null config");
+  if (max_batch < 1 || max_batch > (1 << 22)) return fail(h, LMPC_ERR_ARGUMENT, "lmpc_lqr_create: max_batch outside 1 .. 2^22");
+  if (cfg->N < 2 || cfg->N > 4096) return fail(h, LMPC_ERR_ARGUMENT, "lmpc_lqr_create: N outside 2 .. 4096");
+  if (!(cfg->dt > 0.0) || !std::isfinite(cfg->dt)) return fail(h, LMPC_ERR_ARGUMENT, "lmpc_lqr_create: dt must be positive and finite");
+  const int rc0 = lmpc_lqr_destroy(h);
+  if (rc0 != LMPC_OK) return rc0;
+  HIP_TRY(h, hipSetDevice(h->device));
+  const size_t stages = (size_t)(cfg->N - 1) * (size_t)max_batch;
+  dev_buf<double> ws;  // a local owner: a refused allocation leaves the handle without a controller
+  HIP_TRY_AS(h, "lmpc_lqr_create", ws.alloc(76 + 60 * stages));
+  double host[76];
+  std::memcpy(host, cfg->Q, sizeof(cfg->Q));
+  std::memcpy(host + 36, cfg->R, sizeof(cfg->R));
+  std::memcpy(host + 40, cfg->Qf, sizeof(cfg->Qf));
+  HIP_TRY_AS(h, "lmpc_lqr_create", hipMemcpyAsync(ws.get(), host, sizeof(host), hipMemcpyHostToDevice, h->stream));
+  HIP_TRY_AS(h, "lmpc_lqr_create", hipStreamSynchronize(h->stream));  // `host` is on this frame
+  h->lqr_ws = std::move(ws);
+  h->lqr.max_batch = max_batch;
+  h->lqr.N = cfg->N;
+  h->lqr.dt = cfg->dt;
+  h->lqr.cfg = h->lqr_ws.get();
+  h->lqr.AB = h->lqr.cfg + 76;
+  h->lqr.K = h->lqr.AB + 48 * stages;
+  return LMPC_OK;
+}
+
+int lmpc_lqr_solve_batch(lmpc_handle* h, int32_t batch, const double* x_ic, const double* X_ref, const double* U_ref, double* X_optm,
+                         double* U_optm, double* K, double* P0, int32_t* flags) {
+  if (!h) return LMPC_ERR_ARGUMENT;
+  if (!h->lqr.max_batch) return fail(h, LMPC_ERR_ARGUMENT, "lmpc_lqr_solve_batch: no controller (lmpc_lqr_create)");
+  if (batch < 1 || batch > h->lqr.max_batch)
+    return fail(h, LMPC_ERR_ARGUMENT, "lmpc_lqr_solve_batch: batch " + std::to_string(batch) + " outside 1 .. " + std::to_string(h->lqr.max_batch));
+  if (!x_ic || !X_ref || !U_ref || !X_optm || !U_optm) return fail(h, LMPC_ERR_ARGUMENT, "lmpc_lqr_solve_batch: null pointer");
+  HIP_TRY(h, hipSetDevice(h->device));
+  const lmpc_lqr_io io{x_ic, X_ref, U_ref, X_optm, U_optm, K, P0, flags};
+  HIP_TRY(h, lmpc_lqr_launch(h->stream, h->lqr, h->P.veh, batch, io));
   return LMPC_OK;
 }
 

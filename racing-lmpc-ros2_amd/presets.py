@@ -57,3 +57,10 @@ def iac_lmpc(N: int = 60, n_laps: int = 3) -> dict:
              convex_hull_slack=[200.0, 20.0, 2.0, 200.0, 2.0, 20.0],
              num_ss_pts=32 * n_laps, num_ss_pts_per_lap=32, max_lap_stored=n_laps)
     return c
+
+
+def sample_lqr(N: int = 20, dt: float = 0.01) -> dict:
+    """Solver.lqr_create's config with the weights of mpc/racing_lqr/param/sample_lqr.param.yaml: Q = I, R = I (the two-control
+    layout [u_lon, steer]; the file's 3 x 3 `r` is for a control layout this model does not have), Qf = diag(10, 10, 10, 1, 1, 10)."""
+    eye = lambda d: [[float(d[i]) if i == j else 0.0 for j in range(len(d))] for i in range(len(d))]  # noqa: E731
+    return dict(N=N, dt=dt, Q=eye([1.0] * 6), R=eye([1.0] * 2), Qf=eye([10.0, 10.0, 10.0, 1.0, 1.0, 10.0]))
