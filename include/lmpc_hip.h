@@ -799,6 +799,62 @@ int lmpc_lqr_solve_batch(lmpc_handle* h, int32_t batch, const double* x_ic /* [6
                          const double* U_ref /* [2][N-1][B] */, double* X_optm /* [6][N][B] */, double* U_optm /* [2][N-1][B] */,
                          double* K /* [2][6][N-1][B] or NULL */, double* P0 /* [36][B] or NULL */, int32_t* flags /* [B] or NULL */);
 
+/* Batched vanilla controller: VanillaController::solve (controllers/vanilla_controller, vanilla_controller.cpp:49-109) with its
+ * PidController (lmpc_utils/src/pid_controller.cpp:83-127), ONE CONTROLLER PER CAR on the device, fp64, one lane per car.  Per car, on
+ * the state x = (s, e_y, e_psi, vx, vy, omega):
+ *   pose (x, y, yaw) = frenet_to_global(s, e_y, e_psi), the arithmetic of lmpc_frenet_to_global_batch;   v = hypot(vx, vy);
+ *   la = clamp(v lookahead_speed_ratio, min_lookahead_distance, max_lookahead_distance);   s_la = align_abscissa(s + la, L/2, L);
+ *   (x_la, y_la) = the centre line at s_la;   dir = atan2(y_la - y, x_la - x);   alpha = dir - yaw wrapped into (-pi, pi] as
+ *   atan2(sin d, cos d) (upstream goes through tf2 quaternions, lmpc_transform_helper.cpp:63-75: the same angle);
+ *   STEER = clamp(atan(2 wheel_base sin(alpha) / la), -max_steer, max_steer);
+ *   PID on e = vel_ref - v with the controller's dt: a NaN e returns NaN and leaves the state; else last_error <- error, error <- e,
+ *   integral <- clamp(integral + e dt, min_i, max_i), cmd = k_p e + k_i integral + k_d (error - last_error) / dt (the first call
+ *   sees e / dt, as upstream), cmd <= min_cmd -> min_cmd, cmd >= max_cmd -> max_cmd;
+ *   aero = 0.5 rho A cd v^2, down = aero (cl_f + cl_r), roll = fr (m 9.81 + down) (9.81: that file's own GRAVITY, not the model's
+ *   9.8), F = m cmd + roll + aero;   (FD, FB) = F > 0 ? (F, 0) : (0, F);   u_out [3][B] = (FD, FB, STEER), newtons and radians.
+ * Not upstream, for the fleet: the batch; the node's fold u_a = |FD| > |FB| ? FD : FB (vanilla_controller_node.cpp:118-122) and the
+ * command on this library's two-control layout, u_model [2][B] = (u_a force_to_lon, STEER); vel_ref = NULL, which takes the track's
+ * velocity interpolant at the car's abscissa times speed_scale (speed_scale = 1: what the node passes, :104); the per-car flag; and
+ * lmpc_vanilla_rollout_batch, which runs controller and plant for `periods` control periods in one launch.
+ * force_to_lon: in the model fd + fb = 1000 u_lon exactly (single_track_planar_model.cpp:215-216; the two blending weights add to
+ * one), so 1e-3 hands the plant the total force the controller asked for; 1.0 is upstream's chain as written, newtons into a model
+ * whose unit is kN.
+ * The flag LMPC_VANILLA_FLAG_NOT_FINITE marks a car whose u_out holds a NaN or Inf; its PID state is left as it was and no other
+ * car's bits change.  An abscissa beyond LMPC_VANILLA_LAPS_MAX laps is given a NaN u_out (align_abscissa has lost its digits long
+ * before 1e300 and would wrap it to a finite 0).  Every loop count is a constant, n_sub or periods: no input lengthens a launch.
+ * lmpc_vanilla_rollout_batch: per period the decision above at the current state, then n_sub plant sub-steps of dt_sim with the
+ * arithmetic of lmpc_plant_step_batch (the |vx| < 1e-6 guard, curvature from the lmpc_track table at the current abscissa, the
+ * model's integrator, the abscissa wrap).  Every output is optional: X_log [6][periods][B] the state the decision was taken at,
+ * U_log [2][periods][B] the u_model applied, k_log [periods][B] the table's curvature at that state -- what
+ * lmpc_fleet_ss_record_batch takes -- and the accumulators distance [B] (+= the unwrapped abscissa travelled) and worst_excess [B]
+ * (max with max(e_y + b/2 - left, right - (e_y - b/2)) after the period, the bounds from the table at the abscissa of the decision),
+ * as lmpc_loop_advance_batch defines them.  x [6][B] is updated in place.  A car whose decision, or whose state after the plant, is
+ * not finite is flagged and frozen for the rest of the launch: that period is undone (x and the PID state stay as they were before
+ * it, nothing is accumulated) and its logs are NaN from that period on.  flags is written (0 or the flag), not accumulated.
+ * Only lmpc_vanilla_create allocates (3 doubles per car; it synchronises the handle's stream); every other call names the store's
+ * batch.  Array arguments are DEVICE pointers, batch axis fastest; launches go on the handle's stream.
+ * LMPC_ERR_ARGUMENT, nothing written, message in lmpc_last_error: no store, another batch than the store's, a null required pointer
+ * or track, a track of another device, periods < 1, n_sub < 1, dt_sim or dt not positive and finite, min_lookahead_distance <= 0
+ * or > max_lookahead_distance, min_i > max_i, min_cmd > max_cmd (std::clamp is undefined there), batch < 1. */
+typedef struct lmpc_vanilla_config {
+  double lookahead_speed_ratio, min_lookahead_distance, max_lookahead_distance;
+  double k_p, k_i, k_d, min_cmd, max_cmd, min_i, max_i; /* lon_kp, lon_ki, lon_kd, lon_min_acc, lon_max_acc, lon_ki_min, lon_ki_max */
+  double dt;            /* the PID's dt (vanilla_controller.dt) */
+  double force_to_lon;  /* newtons -> model command; 1e-3 physical, 1.0 as written upstream */
+} lmpc_vanilla_config;
+#define LMPC_VANILLA_FLAG_NOT_FINITE 1 /* this car's u_out holds a NaN or Inf (rollout: or its state after the plant does) */
+#define LMPC_VANILLA_LAPS_MAX 1e9      /* |s| > LMPC_VANILLA_LAPS_MAX L: u_out is NaN */
+int lmpc_vanilla_create(lmpc_handle* h, int32_t batch, const lmpc_vanilla_config* cfg); /* per-car PID state, zeroed; replaces an earlier one */
+int lmpc_vanilla_destroy(lmpc_handle* h);                                               /* lmpc_destroy does it too */
+int lmpc_vanilla_reset(lmpc_handle* h, int32_t batch, const double* integral /* [B] or NULL: 0 */); /* error and last_error <- 0 */
+int lmpc_vanilla_get(lmpc_handle* h, int32_t batch, double* integral, double* error, double* last_error); /* DEVICE [B], any NULL */
+int lmpc_vanilla_solve_batch(lmpc_handle* h, int32_t batch, const lmpc_spline_track* track, const double* x_ic /* [6][B] */,
+                             const double* vel_ref /* [B] or NULL */, double speed_scale, double* u_out /* [3][B] */,
+                             double* u_model /* [2][B] or NULL */, int32_t* flags /* [B] or NULL */);
+int lmpc_vanilla_rollout_batch(lmpc_handle* h, int32_t batch, const lmpc_spline_track* track, const lmpc_track* table, double* x /* [6][B] */,
+                               int32_t periods, double dt_sim, int32_t n_sub, double speed_scale, double* X_log, double* U_log, double* k_log,
+                               double* distance, double* worst_excess, int32_t* flags);
+
 #ifdef __cplusplus
 }
 #endif

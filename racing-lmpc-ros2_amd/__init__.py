@@ -7,8 +7,8 @@ built library raises.
 """
 from . import closed_loop, presets, racing_trajectory, ros_params, safe_set, workloads  # noqa: F401
 from .capi import (LmpcError, Solver, SplineTrack, SOLVE_INFEASIBLE, SOLVE_MAX_ITER, SOLVE_OPTIMAL,  # noqa: F401
-                   TRACK_BAD_INPUT, TRACK_NOT_CONVERGED, TRACK_OK, EKF_FALLBACK, EKF_NOT_FINITE, EKF_R_REPAIRED, LQR_NOT_FINITE, CLqrConfig, library_path, load_library)
+                   TRACK_BAD_INPUT, TRACK_NOT_CONVERGED, TRACK_OK, EKF_FALLBACK, EKF_NOT_FINITE, EKF_R_REPAIRED, LQR_NOT_FINITE, CLqrConfig, VANILLA_NOT_FINITE, CVanillaConfig, library_path, load_library)
 
 __all__ = ["presets", "ros_params", "workloads", "closed_loop", "safe_set", "racing_trajectory", "Solver", "SplineTrack", "LmpcError", "load_library", "library_path",
            "SOLVE_OPTIMAL", "SOLVE_MAX_ITER", "SOLVE_INFEASIBLE", "TRACK_OK", "TRACK_NOT_CONVERGED", "TRACK_BAD_INPUT",
-           "EKF_FALLBACK", "EKF_R_REPAIRED", "EKF_NOT_FINITE", "LQR_NOT_FINITE", "CLqrConfig"]
+           "EKF_FALLBACK", "EKF_R_REPAIRED", "EKF_NOT_FINITE", "LQR_NOT_FINITE", "CLqrConfig", "VANILLA_NOT_FINITE", "CVanillaConfig"]

@@ -32,9 +32,12 @@ _ABI_SYMBOLS = ("lmpc_create", "lmpc_destroy", "lmpc_last_error", "lmpc_set_stre
                 "lmpc_global_to_frenet_batch", "lmpc_frenet_to_global_batch",
                 "lmpc_ekf_create", "lmpc_ekf_destroy", "lmpc_ekf_register_observation", "lmpc_ekf_initialize", "lmpc_ekf_set_state",
                 "lmpc_ekf_update_control", "lmpc_ekf_update_batch", "lmpc_ekf_get",
-                "lmpc_lqr_create", "lmpc_lqr_destroy", "lmpc_lqr_solve_batch")
+                "lmpc_lqr_create", "lmpc_lqr_destroy", "lmpc_lqr_solve_batch",
+                "lmpc_vanilla_create", "lmpc_vanilla_destroy", "lmpc_vanilla_reset", "lmpc_vanilla_get", "lmpc_vanilla_solve_batch",
+                "lmpc_vanilla_rollout_batch")
 EKF_FALLBACK, EKF_R_REPAIRED, EKF_NOT_FINITE = 1, 2, 4   # bits of the per-car flags of Solver.ekf_update
 LQR_NOT_FINITE = 1   # per-car flag of Solver.lqr_solve: the car's X_optm, U_optm, K or P0 holds a NaN or Inf
+VANILLA_NOT_FINITE = 1   # per-car flag of Solver.vanilla_solve / vanilla_rollout: u_out (rollout: or the state after the plant) holds a NaN or Inf
 
 
 class LmpcError(RuntimeError):
@@ -76,6 +79,13 @@ class CLqrConfig(C.Structure):
     """lmpc_lqr_config: horizon, time step and the three general dense weights, row-major (racing_lqr_config.hpp)."""
     _fields_ = [("N", C.c_int32), ("reserved", C.c_int32), ("dt", C.c_double), ("Q", C.c_double * 36), ("R", C.c_double * 4),
                 ("Qf", C.c_double * 36)]
+
+
+class CVanillaConfig(C.Structure):
+    """lmpc_vanilla_config: pure pursuit's lookahead, the PID's coefficients and dt, newtons -> model command
+    (vanilla_controller_config.hpp, lmpc_utils/pid_controller.hpp)."""
+    _fields_ = [(n, C.c_double) for n in ("lookahead_speed_ratio min_lookahead_distance max_lookahead_distance k_p k_i k_d min_cmd max_cmd "
+                                          "min_i max_i dt force_to_lon").split()]
 
 
 class CTrack(C.Structure):
@@ -962,4 +972,85 @@ class Solver:
                                            _ptr(out.get("K")), _ptr(out.get("P0")), _ptr(out.get("flags")))
         self._check(rc, "lmpc_lqr_solve_batch")
         out["u"] = out["U_optm"][:, 0, :]
+        return out
+
+    # ---- batched vanilla controller, one per car: pure pursuit + PID (vanilla_controller.cpp:49-109; include/lmpc_hip.h) ----
+    def vanilla_create(self, cfg: dict, batch: int):
+        """lmpc_vanilla_create: one controller per car for `batch` cars over this solver's vehicle, PID state zeroed.  cfg: the fields
+        of lmpc_vanilla_config (presets.vanilla_controller).  Replaces an earlier store."""
+        self.use_current_stream()
+        c = _fill(CVanillaConfig(), cfg)
+        self._check(self.lib.lmpc_vanilla_create(self._h, C.c_int32(int(batch)), C.byref(c)), "lmpc_vanilla_create")
+        self._vanilla_B = int(batch)
+
+    def vanilla_destroy(self):
+        self._check(self.lib.lmpc_vanilla_destroy(self._h), "lmpc_vanilla_destroy")
+        self._vanilla_B = None
+
+    def vanilla_reset(self, B: int, integral=None):
+        """lmpc_vanilla_reset: error and last_error to zero, the integral to `integral` [B] (None: zero).  Asynchronous."""
+        self.use_current_stream()
+        if integral is not None:
+            integral = self._t(integral)
+            if tuple(integral.shape) != (int(B),):
+                raise ValueError(f"vanilla_reset: integral is [{B}]")
+        self._check(self.lib.lmpc_vanilla_reset(self._h, C.c_int32(int(B)), _ptr(integral)), "lmpc_vanilla_reset")
+
+    def vanilla_get(self, B: int) -> dict:
+        """lmpc_vanilla_get: {"integral", "error", "last_error"} float64 [B], device tensors.  Asynchronous."""
+        torch = self._torch
+        self.use_current_stream()
+        out = torch.empty((3, int(B)), dtype=torch.float64, device=self.device)
+        self._check(self.lib.lmpc_vanilla_get(self._h, C.c_int32(int(B)), _ptr(out[0]), _ptr(out[1]), _ptr(out[2])), "lmpc_vanilla_get")
+        return {"integral": out[0], "error": out[1], "last_error": out[2]}
+
+    def vanilla_solve(self, track: SplineTrack, x_ic, vel_ref=None, speed_scale: float = 1.0, out=None):
+        """lmpc_vanilla_solve_batch: one control decision per car.  x_ic [6][B]; vel_ref [B], or None for the track's velocity
+        interpolant at the car's abscissa times speed_scale -> {"u_out" [3][B] = (FD, FB, STEER) in newtons and radians, "u_model"
+        [2][B] = (u_a force_to_lon, STEER), "flags" int32 [B]: VANILLA_NOT_FINITE}.  `out` = such a dict reuses the caller's buffers;
+        its "u_model" and "flags" may be None or missing and are then not asked of the kernel.  One launch, asynchronous."""
+        torch = self._torch
+        self.use_current_stream()
+        x_ic = self._t(x_ic)
+        if x_ic.dim() != 2 or x_ic.shape[0] != 6:
+            raise ValueError(f"vanilla_solve: x_ic is [6][B], got {tuple(x_ic.shape)}")
+        B = x_ic.shape[1]
+        if vel_ref is not None:
+            vel_ref = self._t(vel_ref)
+            if tuple(vel_ref.shape) != (B,):
+                raise ValueError(f"vanilla_solve: vel_ref is [{B}], got {tuple(vel_ref.shape)}")
+        if out is None:
+            kw = dict(dtype=torch.float64, device=self.device)
+            out = {"u_out": torch.empty((3, B), **kw), "u_model": torch.empty((2, B), **kw),
+                   "flags": torch.empty((B,), dtype=torch.int32, device=self.device)}
+        rc = self.lib.lmpc_vanilla_solve_batch(self._h, C.c_int32(B), track._p if track is not None else None, _ptr(x_ic), _ptr(vel_ref),
+                                               C.c_double(float(speed_scale)), _ptr(out.get("u_out")), _ptr(out.get("u_model")), _ptr(out.get("flags")))
+        self._check(rc, "lmpc_vanilla_solve_batch")
+        return out
+
+    def vanilla_rollout(self, track: SplineTrack, table: dict, x, periods: int, dt_sim: float, n_sub: int = 1, speed_scale: float = 1.0,
+                        logs: bool = True, distance=None, worst_excess=None, out=None):
+        """lmpc_vanilla_rollout_batch: `periods` control periods of controller + plant per car in ONE launch.  x [6][B] is updated in
+        place, as is the PID state; table: the track's uniform tables (device_track / tabulate_track); dt_sim, n_sub: the plant's
+        sub-steps per period.  Returns {"X_log" [6][periods][B] the state each decision was taken at, "U_log" [2][periods][B] the
+        u_model applied, "k_log" [periods][B] the table's curvature there (None with logs=False), "flags" int32 [B]}; distance and
+        worst_excess (float64 [B], optional) are accumulated as loop_advance accumulates them.  `out` = such a dict reuses buffers; a
+        None or missing entry is not asked of the kernel.  A flagged car is frozen at its last finite state and its logs are NaN
+        from that period on.  Asynchronous."""
+        torch = self._torch
+        self.use_current_stream()
+        if x.dim() != 2 or x.shape[0] != 6 or x.dtype != torch.float64 or not x.is_contiguous():
+            raise ValueError("vanilla_rollout: x is a contiguous float64 [6][B] device tensor (it is updated in place)")
+        B, P = x.shape[1], int(periods)
+        ct = self._ctrack(table)
+        if out is None:
+            kw = dict(dtype=torch.float64, device=self.device)
+            out = {"flags": torch.empty((B,), dtype=torch.int32, device=self.device)}
+            if logs and P >= 1:
+                out.update(X_log=torch.empty((6, P, B), **kw), U_log=torch.empty((2, P, B), **kw), k_log=torch.empty((P, B), **kw))
+        rc = self.lib.lmpc_vanilla_rollout_batch(self._h, C.c_int32(B), track._p if track is not None else None, C.byref(ct), _ptr(x), C.c_int32(P),
+                                                 C.c_double(float(dt_sim)), C.c_int32(int(n_sub)), C.c_double(float(speed_scale)),
+                                                 _ptr(out.get("X_log")), _ptr(out.get("U_log")), _ptr(out.get("k_log")), _ptr(distance),
+                                                 _ptr(worst_excess), _ptr(out.get("flags")))
+        self._check(rc, "lmpc_vanilla_rollout_batch")
         return out

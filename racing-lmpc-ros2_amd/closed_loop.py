@@ -565,3 +565,95 @@ def run_lqr(solver, x0, X_traj, U_traj, steps: int):
         x = out["X_optm"][:, 1].contiguous()
         X[:, t + 1] = x
     return {"X": X, "U": U, "flags": flags_or}
+
+
+def _table_lookup(tab, M: int, L: float, s):
+    """The periodic linear interpolation of an lmpc_track table at s [B], operation by operation as lmpc_vanilla_rollout_batch forms
+    k_log and the bounds of worst_excess (no contraction there): the same bits."""
+    import torch
+
+    u = torch.fmod(s, L)
+    u = torch.where(u < 0.0, u + L, u)
+    u = u / torch.full_like(u, L / M)   # (a tensor divisor: torch divides by a Python scalar as a product with its reciprocal)
+    fl = torch.floor(u)
+    fr = u - fl
+    i0 = torch.remainder(torch.nan_to_num(fl, nan=0.0, posinf=0.0, neginf=0.0).long(), M)
+    i1 = torch.where(i0 + 1 == M, torch.zeros_like(i0), i0 + 1)
+    return tab[i0] * (1.0 - fr) + tab[i1] * fr
+
+
+def run_vanilla(solver, track: dict, spline, x0, steps: int, dt: float = 0.025, n_sub: int = 2, speed_scale: float = 1.0, chunk: int = 64,
+                fused: bool = True, fleet_record: bool = False):
+    """A fleet driven by the vanilla controller (pure pursuit + PID, lmpc_vanilla_*), one controller per car: what buys an LMPC
+    experiment its first feasible laps without a QP.  The caller has made the controllers (solver.vanilla_create for B cars; their PID
+    state is used as it stands and is left where the run ends); `track` holds the uniform tables the plant reads, `spline` is
+    Solver.spline_track of the same track.  x0 [6][B]; `steps` control periods of n_sub plant sub-steps of dt / n_sub each.  (dt is the
+    period the plant is stepped over; the PID integrates with the dt of its own config, as upstream.)
+
+    fused=True: lmpc_vanilla_rollout_batch in chunks of `chunk` periods -- ceil(steps / chunk) launches in all.  fused=False: one
+    vanilla_solve, one plant_step and the bookkeeping in torch per period, the same arithmetic (the plant is compiled into two
+    translation units, so nothing guarantees the same contraction: tests/test_gpu_vanilla.py compares at the rollout's tolerance,
+    demands the decision bit for bit, and finds the 700-period laps both paths record identical with this compiler).  A car whose decision or state turns non-finite is frozen at its last finite state in both; what the
+    unfused path cannot do is take back the PID update of a period whose plant step went non-finite.
+
+    fleet_record=True: every logged sample (x, u_model, curvature, t = period * dt) goes to the fleet safe set's recorder
+    (solver.fleet_ss_record, one call per period; the caller has made the store with fleet_ss_create); frozen cars are skipped.
+
+    Returns run's statistics -- "x" [6][B], "distance" [B], "worst_excess" [B] (from 0, as run keeps it), "n_fail" int64 [B] (the
+    periods a car was not driven: frozen), "trace" [], "warm_hit_rate" None -- and "flags" int32 [B] (the OR over the run:
+    VANILLA_NOT_FINITE), "X_log" [6][steps][B], "U_log" [2][steps][B], "k_log" [steps][B]."""
+    import torch
+
+    if getattr(solver, "_vanilla_B", None) is None:
+        raise ValueError("run_vanilla: no controller (Solver.vanilla_create)")
+    if chunk < 1:
+        raise ValueError("run_vanilla: chunk must be at least 1")
+    trk = solver.device_track(track)
+    L, M = float(trk["L"]), int(trk["M"])
+    x = solver._t(x0).clone()
+    B, dev = x.shape[1], x.device
+    kw = dict(dtype=torch.float64, device=dev)
+    dist, worst = torch.zeros(B, **kw), torch.zeros(B, **kw)
+    flags = torch.zeros(B, dtype=torch.int32, device=dev)
+    X_log, U_log, k_log = torch.empty((6, steps, B), **kw), torch.empty((2, steps, B), **kw), torch.empty((steps, B), **kw)
+    half_b = float(solver.vehicle["b"]) / 2.0
+
+    def record(p0, p1):
+        for p in range(p0, p1):
+            solver.fleet_ss_record(X_log[:, p], U_log[:, p], k_log[p], p * dt, L, active=torch.isfinite(k_log[p]).to(torch.int32))
+
+    if fused:
+        for p0 in range(0, steps, chunk):
+            n = min(chunk, steps - p0)
+            out = solver.vanilla_rollout(spline, trk, x, n, dt / n_sub, n_sub, speed_scale=speed_scale, distance=dist, worst_excess=worst)
+            # (a car frozen in an earlier chunk freezes again at once: the period that froze it was undone, so the kernel meets the
+            # same state and the same PID state, and its logs are NaN again)
+            X_log[:, p0:p0 + n], U_log[:, p0:p0 + n], k_log[p0:p0 + n] = out["X_log"], out["U_log"], out["k_log"]
+            flags |= out["flags"]
+            if fleet_record:
+                record(p0, p0 + n)
+    else:
+        out = None
+        nan = torch.full((), float("nan"), **kw)
+        for p in range(steps):
+            out = solver.vanilla_solve(spline, x, None, speed_scale=speed_scale, out=out)
+            frozen = flags != 0
+            live = (out["flags"] == 0) & ~frozen
+            xs = torch.where(live, x, torch.zeros_like(x)).contiguous()
+            u = torch.where(live, out["u_model"], torch.zeros_like(out["u_model"])).contiguous()
+            solver.plant_step(trk, xs, u, dt / n_sub, n_sub)
+            live = live & torch.isfinite(xs).all(dim=0)
+            flags |= (~live).to(torch.int32)
+            X_log[:, p] = torch.where(live, x, nan)
+            U_log[:, p] = torch.where(live, out["u_model"], nan)
+            k_log[p] = torch.where(live, _table_lookup(trk["curvature"], M, L, x[0]), nan)
+            ds = xs[0] - x[0]
+            dist += torch.where(live, torch.where(ds < -L / 2.0, ds + L, ds), torch.zeros_like(ds))
+            bl, br = _table_lookup(trk["bound_left"], M, L, x[0]), _table_lookup(trk["bound_right"], M, L, x[0])
+            exc = torch.maximum(xs[1] + half_b - bl, br - (xs[1] - half_b))
+            worst = torch.where(live, torch.maximum(worst, exc), worst)
+            x = torch.where(live, xs, x).contiguous()
+            if fleet_record:
+                record(p, p + 1)
+    return {"x": x, "distance": dist, "worst_excess": worst, "n_fail": torch.isnan(k_log).sum(dim=0).to(torch.int64), "trace": [],
+            "warm_hit_rate": None, "flags": flags, "X_log": X_log, "U_log": U_log, "k_log": k_log}

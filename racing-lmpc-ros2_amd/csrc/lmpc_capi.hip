@@ -23,6 +23,7 @@
 #include "lmpc_device.h"
 #include "lmpc_ekf.h"
 #include "lmpc_lqr.h"
+#include "lmpc_vanilla.h"
 #include "lmpc_fleet_reg.h"
 #include "lmpc_fleet_ss.h"
 
@@ -132,6 +133,9 @@ struct __attribute__((visibility("hidden"))) lmpc_handle {  // (its members are 
   // batched time-varying LQR (lmpc_lqr_create): one controller per car, csrc/lmpc_lqr.h
   lmpc_lqr_store lqr{};     // raw copies of the owner below, as the kernels take them
   dev_buf<double> lqr_ws;   // cfg [76] | AB [N-1][8][max_batch][6] | K [N-1][2][max_batch][6]
+  // batched vanilla controller (lmpc_vanilla_create): one pure-pursuit + PID controller per car, csrc/lmpc_vanilla.h
+  lmpc_vanilla_store vanilla{};  // the config and a raw copy of the owner below, as the kernels take them
+  dev_buf<double> vanilla_pid;   // [3][batch]: integral | error | last_error
   // staging for the single-problem host entry points (lmpc_solve_host, lmpc_ss_query_host): device buffers and PINNED
   // host mirrors, all sized and allocated by lmpc_create -- the per-step path of one controller allocates nothing
   dev_buf<double> stage_dev;
@@ -2112,6 +2116,108 @@ int lmpc_frenet_to_global_batch(lmpc_handle* h, const lmpc_spline_track* track, 
   HIP_TRY(h, hipSetDevice(h->device));
   hipLaunchKernelGGL(lmpc_track_to_global_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, h->stream, track->view, count, X, pose);
   HIP_TRY(h, hipGetLastError());
+  return LMPC_OK;
+}
+
+}  // extern "C"
+
+// ---- batched vanilla controller, one per car (csrc/lmpc_vanilla.h, csrc/lmpc_vanilla_kernel.hip) ----
+namespace {
+// what every call but create and destroy checks first: a store, and the store's batch
+int vanilla_check(lmpc_handle* h, int32_t batch, const char* who) {
+  if (!h->vanilla.batch) return fail(h, LMPC_ERR_ARGUMENT, std::string(who) + ": no controller (lmpc_vanilla_create)");
+  if (batch != h->vanilla.batch)
+    return fail(h, LMPC_ERR_ARGUMENT, std::string(who) + ": batch " + std::to_string(batch) + ", the store holds " + std::to_string(h->vanilla.batch));
+  return LMPC_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int lmpc_vanilla_destroy(lmpc_handle* h) {
+  if (!h) return LMPC_ERR_ARGUMENT;
+  if (!h->vanilla.batch) return LMPC_OK;
+  (void)hipSetDevice(h->device);
+  (void)hipStreamSynchronize(h->stream);
+  h->vanilla_pid.release();
+  h->vanilla = lmpc_vanilla_store{};
+  return LMPC_OK;
+}
+
+int lmpc_vanilla_create(lmpc_handle* h, int32_t batch, const lmpc_vanilla_config* cfg) {
+  if (!h) return LMPC_ERR_ARGUMENT;
+  if (!cfg) return fail(h, LMPC_ERR_ARGUMENT, "lmpc_vanilla_create: null config");
+  if (batch < 1 || batch > (1 << 24)) return fail(h, LMPC_ERR_ARGUMENT, "lmpc_vanilla_create: batch outside 1 .. 2^24");
+  if (!(cfg->dt > 0.0) || !std::isfinite(cfg->dt)) return fail(h, LMPC_ERR_ARGUMENT, "lmpc_vanilla_create: dt must be positive and finite");
+  if (!(cfg->min_lookahead_distance > 0.0) || !(cfg->min_lookahead_distance <= cfg->max_lookahead_distance))
+    return fail(h, LMPC_ERR_ARGUMENT, "lmpc_vanilla_create: needs 0 < min_lookahead_distance <= max_lookahead_distance");
+  if (!(cfg->min_i <= cfg->max_i)) return fail(h, LMPC_ERR_ARGUMENT, "lmpc_vanilla_create: min_i > max_i");
+  if (!(cfg->min_cmd <= cfg->max_cmd)) return fail(h, LMPC_ERR_ARGUMENT, "lmpc_vanilla_create: min_cmd > max_cmd");
+  const int rc0 = lmpc_vanilla_destroy(h);
+  if (rc0 != LMPC_OK) return rc0;
+  HIP_TRY(h, hipSetDevice(h->device));
+  dev_buf<double> pid;  // a local owner: a refused allocation leaves the handle without a controller
+  HIP_TRY_AS(h, "lmpc_vanilla_create", pid.alloc((size_t)3 * (size_t)batch));
+  HIP_TRY_AS(h, "lmpc_vanilla_create", hipMemsetAsync(pid.get(), 0, (size_t)3 * (size_t)batch * sizeof(double), h->stream));
+  HIP_TRY_AS(h, "lmpc_vanilla_create", hipStreamSynchronize(h->stream));
+  h->vanilla_pid = std::move(pid);
+  h->vanilla.batch = batch;
+  h->vanilla.cfg = *cfg;
+  h->vanilla.pid = h->vanilla_pid.get();
+  return LMPC_OK;
+}
+
+int lmpc_vanilla_reset(lmpc_handle* h, int32_t batch, const double* integral) {
+  if (!h) return LMPC_ERR_ARGUMENT;
+  const int rc = vanilla_check(h, batch, "lmpc_vanilla_reset");
+  if (rc != LMPC_OK) return rc;
+  HIP_TRY(h, hipSetDevice(h->device));
+  const size_t row = (size_t)batch * sizeof(double);
+  HIP_TRY(h, hipMemsetAsync(h->vanilla.pid, 0, 3 * row, h->stream));
+  if (integral) HIP_TRY(h, hipMemcpyAsync(h->vanilla.pid, integral, row, hipMemcpyDeviceToDevice, h->stream));
+  return LMPC_OK;
+}
+
+int lmpc_vanilla_get(lmpc_handle* h, int32_t batch, double* integral, double* error, double* last_error) {
+  if (!h) return LMPC_ERR_ARGUMENT;
+  const int rc = vanilla_check(h, batch, "lmpc_vanilla_get");
+  if (rc != LMPC_OK) return rc;
+  HIP_TRY(h, hipSetDevice(h->device));
+  const size_t row = (size_t)batch * sizeof(double);
+  double* const dst[3] = {integral, error, last_error};
+  for (int k = 0; k < 3; ++k)
+    if (dst[k]) HIP_TRY(h, hipMemcpyAsync(dst[k], h->vanilla.pid + (size_t)k * batch, row, hipMemcpyDeviceToDevice, h->stream));
+  return LMPC_OK;
+}
+
+int lmpc_vanilla_solve_batch(lmpc_handle* h, int32_t batch, const lmpc_spline_track* track, const double* x_ic, const double* vel_ref,
+                             double speed_scale, double* u_out, double* u_model, int32_t* flags) {
+  if (!h) return LMPC_ERR_ARGUMENT;
+  int rc = vanilla_check(h, batch, "lmpc_vanilla_solve_batch");
+  if (rc != LMPC_OK) return rc;
+  rc = spline_track_check(h, track, "lmpc_vanilla_solve_batch");
+  if (rc != LMPC_OK) return rc;
+  if (!x_ic || !u_out) return fail(h, LMPC_ERR_ARGUMENT, "lmpc_vanilla_solve_batch: null pointer");
+  HIP_TRY(h, hipSetDevice(h->device));
+  HIP_TRY(h, lmpc_vanilla_launch_solve(h->stream, h->vanilla, h->P.veh, track->view, batch, x_ic, vel_ref, speed_scale, u_out, u_model, flags));
+  return LMPC_OK;
+}
+
+int lmpc_vanilla_rollout_batch(lmpc_handle* h, int32_t batch, const lmpc_spline_track* track, const lmpc_track* table, double* x, int32_t periods,
+                               double dt_sim, int32_t n_sub, double speed_scale, double* X_log, double* U_log, double* k_log, double* distance,
+                               double* worst_excess, int32_t* flags) {
+  if (!h) return LMPC_ERR_ARGUMENT;
+  int rc = vanilla_check(h, batch, "lmpc_vanilla_rollout_batch");
+  if (rc != LMPC_OK) return rc;
+  rc = spline_track_check(h, track, "lmpc_vanilla_rollout_batch");
+  if (rc != LMPC_OK) return rc;
+  if (!track_ok(table)) return fail(h, LMPC_ERR_ARGUMENT, "lmpc_vanilla_rollout_batch: null or empty track table");
+  if (!x) return fail(h, LMPC_ERR_ARGUMENT, "lmpc_vanilla_rollout_batch: null pointer");
+  if (periods < 1 || n_sub < 1) return fail(h, LMPC_ERR_ARGUMENT, "lmpc_vanilla_rollout_batch: periods and n_sub must be at least 1");
+  if (!(dt_sim > 0.0) || !std::isfinite(dt_sim)) return fail(h, LMPC_ERR_ARGUMENT, "lmpc_vanilla_rollout_batch: dt_sim must be positive and finite");
+  HIP_TRY(h, hipSetDevice(h->device));
+  const lmpc_vanilla_rollout_io io{x, X_log, U_log, k_log, distance, worst_excess, flags};
+  HIP_TRY(h, lmpc_vanilla_launch_rollout(h->stream, h->vanilla, h->P.veh, track->view, *table, batch, periods, dt_sim, n_sub, speed_scale, io));
   return LMPC_OK;
 }
 

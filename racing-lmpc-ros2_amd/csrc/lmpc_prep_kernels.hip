@@ -9,6 +9,7 @@
 
 #include "lmpc_device.h"
 #include "lmpc_dynamics.hip.h"
+#include "lmpc_track.hip.h"  // track_lookup: the periodic linear lookup into an lmpc_track's tables
 
 // One thread per (problem b, stage i).  blockIdx.y = stage, so a wave covers 64 consecutive
 // problems of one stage.  Forward-mode chain rule through the four RK4 stages:
@@ -119,20 +120,6 @@ template __global__ void lmpc_linearize_kernel<true, double, 2>(lmpc_params, int
                                                              const double*, double*, double*, double*);
 template __global__ void lmpc_linearize_kernel<true, float, 2>(lmpc_params, int, const float*, const float*, const float*, const float*,
                                                             float*, float*, float*);
-
-// periodic linear interpolation on a uniform table of M samples over [0, L)
-__device__ __forceinline__ double track_lookup(const double* __restrict__ tab, int M, double L, double s) {
-  double u = fmod(s, L);
-  if (u < 0.0) u += L;
-  u = u / (L / M);
-  double fl = floor(u);
-  const double fr = u - fl;
-  int i0 = (int)fl;
-  i0 = i0 % M;
-  if (i0 < 0) i0 += M;
-  const int i1 = (i0 + 1 == M) ? 0 : i0 + 1;
-  return tab[i0] * (1.0 - fr) + tab[i1] * fr;
-}
 
 // Reference sampling at one knot (racing_mpc_node.cpp:261-292): bounds, curvature, clamped velocity reference.
 __device__ __forceinline__ void sample_refs(const lmpc_track& trk, double s, double cur, double d, double speed_scale,

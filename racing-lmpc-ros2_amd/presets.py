@@ -3,6 +3,7 @@
 Transcribed from the reference's YAML (values only):
   vehicles  src/launch/racing_lmpc_launch/param/{barc,iac_car}/*_base.param.yaml, *_single_track.param.yaml
   MPC       src/launch/racing_lmpc_launch/param/racing_mpc/{barc_tracking_mpc,barc_lmpc,iac_car_tracking_mpc}.param.yaml
+  vanilla   src/controllers/vanilla_controller/param/{vanilla_controller,vanilla_controller_2}.param.yaml
 Field names are those of lmpc_vehicle / lmpc_config in include/lmpc_hip.h.
 """
 from __future__ import annotations
@@ -64,3 +65,18 @@ def sample_lqr(N: int = 20, dt: float = 0.01) -> dict:
     layout [u_lon, steer]; the file's 3 x 3 `r` is for a control layout this model does not have), Qf = diag(10, 10, 10, 1, 1, 10)."""
     eye = lambda d: [[float(d[i]) if i == j else 0.0 for j in range(len(d))] for i in range(len(d))]  # noqa: E731
     return dict(N=N, dt=dt, Q=eye([1.0] * 6), R=eye([1.0] * 2), Qf=eye([10.0, 10.0, 10.0, 1.0, 1.0, 10.0]))
+
+
+def vanilla_controller(force_to_lon: float = 1e-3) -> dict:
+    """Solver.vanilla_create's config with the values of controllers/vanilla_controller/param/vanilla_controller.param.yaml: a
+    proportional speed controller (no integral, no derivative), lookahead one second of travel between 1 and 10 m.  force_to_lon is
+    not in the file: 1e-3 hands the model the force the controller asked for, 1.0 is the reference's chain as written (newtons into a
+    model whose unit is kN) -- include/lmpc_hip.h at lmpc_vanilla_create."""
+    return dict(lookahead_speed_ratio=1.0, min_lookahead_distance=1.0, max_lookahead_distance=10.0,
+                k_p=1.0, k_i=0.0, k_d=0.0, min_cmd=-5.0, max_cmd=5.0, min_i=0.0, max_i=0.0, dt=0.1, force_to_lon=force_to_lon)
+
+
+def vanilla_controller_2(force_to_lon: float = 1e-3) -> dict:
+    """vanilla_controller_2.param.yaml: lookahead between 3 and 40 m, a full PID (k_i = k_d = 0.1, integral within +- 3)."""
+    return dict(lookahead_speed_ratio=1.0, min_lookahead_distance=3.0, max_lookahead_distance=40.0,
+                k_p=1.0, k_i=0.1, k_d=0.1, min_cmd=-5.0, max_cmd=5.0, min_i=-3.0, max_i=3.0, dt=0.1, force_to_lon=force_to_lon)

@@ -5,6 +5,7 @@ file; each is `/**: ros__parameters: <group>: <key>: value`.  The loaders below 
   base_vehicle_model/src/ros_param_loader.cpp:30-174        (chassis.*, aero.*, steer.*, front_tyre.*, ...)
   single_track_planar_model/src/ros_param_loader.cpp:30-52  (single_track_planar.*)
   mpc/racing_mpc/src/ros_param_loader.cpp:30-104            (racing_mpc.*)
+  controllers/vanilla_controller/src/ros_param_loader.cpp:30-76   (vanilla_controller.*)
 and keep their contract: every key the reference declares is mandatory (declare_parameter rethrows,
 lmpc_utils/ros_param_helper.hpp:28-54) -- a missing one raises KeyError naming it.  Keys the device path has no use for
 (tyre geometry, brake hardware, powertrain map) are not required here.
@@ -16,7 +17,8 @@ from __future__ import annotations
 import math
 from pathlib import Path
 
-__all__ = ["load_ros_params", "vehicle_from_params", "mpc_config_from_params", "host_options_from_params"]
+__all__ = ["load_ros_params", "vehicle_from_params", "mpc_config_from_params", "host_options_from_params",
+           "vanilla_config_from_params"]
 
 
 def _scalar(v):
@@ -172,3 +174,18 @@ def host_options_from_params(params: dict, strict: bool = True) -> dict:
     return dict(record=get("record", bool, False), path_prefix=get("path_prefix", str, ""),
                 load=get("load", bool, False), load_path=list(load_path),
                 step_mode=_need(params, "racing_mpc.step_mode", str), verbose=_need(params, "racing_mpc.verbose", bool))
+
+
+def vanilla_config_from_params(params: dict, force_to_lon: float = 1e-3) -> dict:
+    """lmpc_vanilla_config fields from `vanilla_controller.*` (controllers/vanilla_controller/src/ros_param_loader.cpp:48-73): every
+    key the reference declares is mandatory, step_mode included ("step" or "continuous", anything else raises as upstream throws; it
+    configures the node's timer, not the controller, and is returned beside the fields as "step_mode").  force_to_lon is not a
+    parameter of the reference (include/lmpc_hip.h at lmpc_vanilla_create)."""
+    f = lambda k: _need(params, "vanilla_controller." + k, float)  # noqa: E731
+    mode = _need(params, "vanilla_controller.step_mode", str)
+    if mode not in ("step", "continuous"):
+        raise ValueError("Invalid step mode: " + mode)
+    return dict(lookahead_speed_ratio=f("lookahead_speed_ratio"), min_lookahead_distance=f("min_lookahead_distance"),
+                max_lookahead_distance=f("max_lookahead_distance"), k_p=f("lon_kp"), k_i=f("lon_ki"), k_d=f("lon_kd"),
+                min_cmd=f("lon_min_acc"), max_cmd=f("lon_max_acc"), min_i=f("lon_ki_min"), max_i=f("lon_ki_max"), dt=f("dt"),
+                force_to_lon=float(force_to_lon), step_mode=mode)
