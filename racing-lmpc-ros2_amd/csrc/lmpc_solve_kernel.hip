@@ -157,7 +157,10 @@ __device__ __forceinline__ real qz_entry(const real* ct, bool terminal, int r, i
 // is one number per knot (c_sigma on e_y: KN_CSIG), generated on the fly.  The arithmetic of either recursion is the unfused one's,
 // operation for operation.  riccati_solve<2, true> then runs the forward half only.
 #define KN_TEY 35  // (the knot record's spare cell)
-template <bool HAS_PT, bool JOSEPH, bool FUSE = false, typename real, typename ptreal>
+// CHAIN_ADDR (lmpc_chain_addr, lmpc_solve_layout.hip.h): what the loop reads and writes in the stage and knot records -- the cells that
+// move from stage to stage; P, W, Y in the tail stay where they are -- goes through LDS byte addresses, one per lane pattern, each
+// advanced once per stage, every access at a compile-time offset from one of them: the same cells in the same order.
+template <bool HAS_PT, bool JOSEPH, bool FUSE = false, bool CHAIN_ADDR = false, typename real, typename ptreal>
 __device__ __forceinline__ void riccati_factor(const Lds<real>& L, int lane, const ptreal* PT, const int th_off = KN_R0, const int tey_off = KN_EY) {
   FRESH_LANE(lane);
   CHAIN_PRIO_ENTER();
@@ -224,9 +227,31 @@ __device__ __forceinline__ void riccati_factor(const Lds<real>& L, int lane, con
     pown = MP[MROWS(r) + c];
     ISSUE_ORDER();
   }
+  // CHAIN_ADDR: wave-uniform cells of the stage and of the knot, the knot's weight by row, the sweep's q_z, the rows r and c of the
+  // stage fetched ahead (stride 0 once it is stage 0), and the two store targets (a dead cell: stride 0)
+  unsigned a_stu = 0, a_knu = 0, a_thr = 0, a_foq = 0, a_nr = 0, a_nc = 0, a_res = 0, a_kff = 0, s_res = 0, s_kff = 0;
+  constexpr unsigned ca_kb = LMPC_KNOT_STRIDE * sizeof(real);
+  const unsigned ca_sb = L.stride * sizeof(real);
+  if constexpr (CHAIN_ADDR) {
+    const int in = N > 2 ? N - 3 : 0;
+    a_stu = lds_addr(L.st(N - 2));
+    a_knu = lds_addr(L.kn(N - 2));
+    a_thr = lds_addr(L.kn(N - 2) + th_off + r);
+    a_foq = lds_addr(L.kn(N - 2) + f_oq);
+    a_nr = lds_addr(L.st(in) + ST_ROW(r));
+    a_nc = lds_addr(L.st(in) + ST_ROW(c));
+    a_res = lds_addr(res_on ? L.st(N - 2) + res_off : res_junk);
+    a_kff = lds_addr(f_own ? L.st(N - 2) + ST_KFF(fs) + c : res_junk);
+    s_res = res_on ? ca_sb : 0u;
+    s_kff = f_own ? ca_sb : 0u;
+  }
   for (int i = N - 2; i >= 0; --i) {
     real* st = L.st(i);
     const real* kn = L.kn(i);
+    if constexpr (CHAIN_ADDR) {
+      CHAIN_ADDR_PIN16(a_stu); CHAIN_ADDR_PIN16(a_knu); CHAIN_ADDR_PIN(a_thr); CHAIN_ADDR_PIN16(a_nr); CHAIN_ADDR_PIN16(a_nc); CHAIN_ADDR_PIN(a_res);
+      if constexpr (FUSE) { CHAIN_ADDR_PIN(a_foq); CHAIN_ADDR_PIN(a_kff); }
+    }
     // W = Abar' P : W[r][c] = sum_k Abar[k][r] P[k][c]  (+ P[r][c] for the u rows); P[k][c] read as P[c][k]
     if constexpr (!FUSE) {
 #pragma unroll
@@ -235,11 +260,22 @@ __device__ __forceinline__ void riccati_factor(const Lds<real>& L, int lane, con
       ISSUE_ORDER();
     }
     // phase-3 operands of this stage, queued behind the P row
-    const real t = st[ST_DT], thr = kn[th_off + r], ey = kn[tey_off], thv0 = kn[th_off + 8], thv1 = kn[th_off + 9];
-    if constexpr (FUSE) {
-      fqz = kn[f_oq];
-      fqv0 = kn[KN_R0 + 8];
-      fqv1 = kn[KN_R0 + 9];
+    real t, thr, ey, thv0, thv1;
+    if constexpr (CHAIN_ADDR) {
+      const LMPC_LDS real* const knu = lds_at<real>(a_knu);
+      t = lds_at<real>(a_stu)[ST_DT], thr = *lds_at<real>(a_thr), ey = knu[tey_off], thv0 = knu[th_off + 8], thv1 = knu[th_off + 9];
+      if constexpr (FUSE) {
+        fqz = *lds_at<real>(a_foq);
+        fqv0 = knu[KN_R0 + 8];
+        fqv1 = knu[KN_R0 + 9];
+      }
+    } else {
+      t = st[ST_DT], thr = kn[th_off + r], ey = kn[tey_off], thv0 = kn[th_off + 8], thv1 = kn[th_off + 9];
+      if constexpr (FUSE) {
+        fqz = kn[f_oq];
+        fqv0 = kn[KN_R0 + 8];
+        fqv1 = kn[KN_R0 + 9];
+      }
     }
     ISSUE_ORDER();
     real w = m_r6 * pown;
@@ -270,11 +306,19 @@ __device__ __forceinline__ void riccati_factor(const Lds<real>& L, int lane, con
     const real y6c = MY[MROWS(6) + c], y7c = MY[MROWS(7) + c];
     AFTER_VALUE(y);
     if constexpr (!JOSEPH) {  // phase-1/2 operands of the next stage (their registers are dead by now), queued behind the Y rows
-      const real* stn = L.st(i > 0 ? i - 1 : 0);
+      if constexpr (CHAIN_ADDR) {
 #pragma unroll
-      for (int k = 0; k < 6; ++k) {
-        ar[k] = stn[ST_ROW(r) + k];
-        ac[k] = stn[ST_ROW(c) + k];
+        for (int k = 0; k < 6; ++k) {
+          ar[k] = lds_at<real>(a_nr)[k];
+          ac[k] = lds_at<real>(a_nc)[k];
+        }
+      } else {
+        const real* stn = L.st(i > 0 ? i - 1 : 0);
+#pragma unroll
+        for (int k = 0; k < 6; ++k) {
+          ar[k] = stn[ST_ROW(r) + k];
+          ac[k] = stn[ST_ROW(c) + k];
+        }
       }
     }
     ISSUE_ORDER();
@@ -307,8 +351,13 @@ __device__ __forceinline__ void riccati_factor(const Lds<real>& L, int lane, con
         real b0[6], b1[6];
 #pragma unroll
         for (int k = 0; k < 6; ++k) {
-          b0[k] = st[ST_ROW(6) + k];
-          b1[k] = st[ST_ROW(7) + k];
+          if constexpr (CHAIN_ADDR) {
+            b0[k] = lds_at<real>(a_stu)[ST_ROW(6) + k];
+            b1[k] = lds_at<real>(a_stu)[ST_ROW(7) + k];
+          } else {
+            b0[k] = st[ST_ROW(6) + k];
+            b1[k] = st[ST_ROW(7) + k];
+          }
         }
 #pragma unroll
         for (int k = 0; k < 6; ++k) {
@@ -339,7 +388,13 @@ __device__ __forceinline__ void riccati_factor(const Lds<real>& L, int lane, con
         for (int k = 0; k < 6; ++k) y2 += w2r[k] * ac[k];
         y2 += w2r[6] * fc6 + w2r[7] * fc7;
       }
-      {  // operands of the next stage
+      if constexpr (CHAIN_ADDR) {  // operands of the next stage
+#pragma unroll
+        for (int k = 0; k < 6; ++k) {
+          ar[k] = lds_at<real>(a_nr)[k];
+          ac[k] = lds_at<real>(a_nc)[k];
+        }
+      } else {
         const real* stn = L.st(i > 0 ? i - 1 : 0);
 #pragma unroll
         for (int k = 0; k < 6; ++k) {
@@ -357,7 +412,10 @@ __device__ __forceinline__ void riccati_factor(const Lds<real>& L, int lane, con
     *p_dst0 = pn;  // (not used after stage 0)
     *p_dst1 = pn;
     const real res = lane < 8 ? k0c : (lane < 16 ? k1c : (lane == 16 ? hi00 : (lane == 17 ? hi01 : hi11)));
-    *(res_on ? st + res_off : res_junk) = res;
+    if constexpr (CHAIN_ADDR)
+      *lds_at<real>(a_res) = res;
+    else
+      *(res_on ? st + res_off : res_junk) = res;
     wave_sync();
     if constexpr (FUSE) {
       if (i > 0) {  // the next stage's P row, behind the stores above
@@ -373,7 +431,15 @@ __device__ __forceinline__ void riccati_factor(const Lds<real>& L, int lane, con
       fp = f_mq * fqz + fws - (k0c * hv0 + k1c * hv1);
       const real ha = c == 0 ? hi00 : hi01, hb = c == 0 ? hi01 : hi11;
       const real kff = ha * hv0 + hb * hv1;
-      *(f_own ? st + ST_KFF(fs) + c : res_junk) = kff;
+      if constexpr (CHAIN_ADDR)
+        *lds_at<real>(a_kff) = kff;
+      else
+        *(f_own ? st + ST_KFF(fs) + c : res_junk) = kff;
+    }
+    if constexpr (CHAIN_ADDR) {
+      const unsigned s_nxt = i >= 2 ? ca_sb : 0u;  // (the fetch ahead stops at stage 0)
+      a_stu -= ca_sb; a_knu -= ca_kb; a_thr -= ca_kb; a_res -= s_res; a_nr -= s_nxt; a_nc -= s_nxt;
+      if constexpr (FUSE) { a_foq -= ca_kb; a_kff -= s_kff; }
     }
   }
   if constexpr (FUSE) wave_sync();
@@ -390,7 +456,9 @@ __device__ __forceinline__ void riccati_factor(const Lds<real>& L, int lane, con
 // nothing on the chain goes through LDS (it did until round 2: one write + broadcast reads per stage, and a ds_swizzle
 // for the condensed 2-vector; ~400 cycles per stage under load).  Stage operands are fetched one stage ahead; the
 // results a stage leaves behind (kff, dz, dv) are stored off the chain.
-template <int NRHS, bool FWD_ONLY = false, typename real>  // (FWD_ONLY: the backward half ran inside the factorisation, riccati_factor<.., FUSE>)
+// CHAIN_ADDR (lmpc_chain_addr, lmpc_solve_layout.hip.h): the stage loops walk LDS byte addresses, one per lane pattern, each advanced
+// once per stage, and every access of a stage is a compile-time offset from one of them -- the same cells in the same order.
+template <int NRHS, bool FWD_ONLY = false, bool CHAIN_ADDR = false, typename real>  // (FWD_ONLY: the backward half ran inside the factorisation, riccati_factor<.., FUSE>)
 __device__ __forceinline__ void riccati_solve(const Lds<real>& L, int lane, Prof& pf) {
   FRESH_LANE(lane);
   CHAIN_PRIO_ENTER();
@@ -412,6 +480,44 @@ __device__ __forceinline__ void riccati_solve(const Lds<real>& L, int lane, Prof
 #pragma unroll
     for (int k = 0; k < 6; ++k) row[k] = st[ST_ROW(r) + k];
   }
+  if constexpr (CHAIN_ADDR && !FWD_ONLY) {
+    const unsigned sb = L.stride * sizeof(real), kb = LMPC_KNOT_STRIDE * sizeof(real);
+    const bool kown = own && r < 2;
+    unsigned a_row = lds_addr(L.st(N - 2) + ST_ROW(r));                 // row-indexed: K(:, r) of this stage
+    unsigned a_nxt = lds_addr(L.st(N > 2 ? N - 3 : 0) + ST_ROW(r));     // ... and [A B](:, r) of the stage fetched ahead
+    unsigned a_uni = lds_addr(L.st(N - 2));                             // wave-uniform: dt
+    unsigned a_ha = lds_addr(L.st(N - 2) + o_ha), a_hb = lds_addr(L.st(N - 2) + o_hb);
+    unsigned a_qz = lds_addr(L.kn(N - 2) + reg + r);                    // knot-indexed: q_z by lane, q_v by right-hand side
+    unsigned a_qv = lds_addr(L.kn(N - 2) + reg);
+    unsigned a_kff = lds_addr(kown ? L.st(N - 2) + ST_KFF(s) + r : junk1);  // store target (a dead cell: stride 0)
+    const unsigned s_kff = kown ? sb : 0u;
+    for (int i = N - 2; i >= 0; --i) {
+      CHAIN_ADDR_PIN16(a_row); CHAIN_ADDR_PIN16(a_nxt); CHAIN_ADDR_PIN(a_uni); CHAIN_ADDR_PIN(a_ha);
+      CHAIN_ADDR_PIN(a_hb); CHAIN_ADDR_PIN(a_qz); CHAIN_ADDR_PIN16(a_qv); CHAIN_ADDR_PIN(a_kff);
+      const LMPC_LDS real* const p_row = lds_at<real>(a_row);
+      const LMPC_LDS real* const p_nxt = lds_at<real>(a_nxt);
+      const LMPC_LDS real* const p_qv = lds_at<real>(a_qv);
+      const real k0r = p_row[6], k1r = p_row[7], t = lds_at<real>(a_uni)[ST_DT];
+      const real qz = *lds_at<real>(a_qz), qv0 = p_qv[8], qv1 = p_qv[9];
+      const real ha = *lds_at<real>(a_ha), hb = *lds_at<real>(a_hb);
+      real pb[6];
+      row_bcast6(p, pb);
+      real w = m6 * p;
+#pragma unroll
+      for (int k = 0; k < 6; ++k) w = rfma(row[k], pb[k], w);
+      real w6, w7;
+      row_bcast67(w, w6, w7);
+#pragma unroll
+      for (int k = 0; k < 6; ++k) row[k] = p_nxt[k];
+      const real hv0 = rfma(t, w6, qv0);
+      const real hv1 = rfma(t, w7, qv1);
+      p = qz + w - (k0r * hv0 + k1r * hv1);
+      const real kff = ha * hv0 + hb * hv1;
+      *lds_at<real>(a_kff) = kff;
+      a_row -= sb; a_uni -= sb; a_ha -= sb; a_hb -= sb; a_qz -= kb; a_qv -= kb; a_kff -= s_kff;
+      a_nxt -= i >= 2 ? sb : 0u;  // (the fetch ahead stops at stage 0)
+    }
+  } else
   for (int i = FWD_ONLY ? -1 : N - 2; i >= 0; --i) {
     real* st = L.st(i);
     const real* kn = L.kn(i);
@@ -449,6 +555,46 @@ __device__ __forceinline__ void riccati_solve(const Lds<real>& L, int lane, Prof
     for (int k = 0; k < 8; ++k) col[k] = st[ST_ROW(k) + r];
     a0 = st[ST_KFF(s) + (r & 1)];
   }
+  if constexpr (CHAIN_ADDR) {
+    const unsigned sb = L.stride * sizeof(real);
+    unsigned a_col = lds_addr(L.st(0) + r);                      // column-indexed: Bbar(r, :) of this stage
+    unsigned a_nxt = lds_addr(L.st(N > 2 ? 1 : 0) + r);          // ... and M(r, :) of the stage fetched ahead
+    unsigned a_kff = lds_addr(L.st(N > 2 ? 1 : 0) + ST_KFF(s) + (r & 1));
+    unsigned a_uni = lds_addr(L.st(0));                          // wave-uniform: dt
+    unsigned a_dz = lds_addr(own ? L.kn(1) + reg + r : junk0);   // store targets (a dead cell: stride 0)
+    unsigned a_dv = lds_addr((own && r >= 6) ? L.kn(0) + reg + 2 + r : junk1);
+    const unsigned s_dz = own ? unsigned(LMPC_KNOT_STRIDE * sizeof(real)) : 0u;
+    const unsigned s_dv = (own && r >= 6) ? unsigned(LMPC_KNOT_STRIDE * sizeof(real)) : 0u;
+    for (int i = 0; i < N - 1; ++i) {
+      CHAIN_ADDR_PIN(a_col); CHAIN_ADDR_PIN(a_nxt); CHAIN_ADDR_PIN(a_kff);
+      CHAIN_ADDR_PIN(a_uni); CHAIN_ADDR_PIN(a_dz); CHAIN_ADDR_PIN(a_dv);
+      const LMPC_LDS real* const p_col = lds_at<real>(a_col);
+      const LMPC_LDS real* const p_nxt = lds_at<real>(a_nxt);
+      const real b0 = p_col[ST_ROW(6)], b1 = p_col[ST_ROW(7)], t = lds_at<real>(a_uni)[ST_DT];
+      real dz[8];
+      row_bcast8(d, dz);
+      real acc = m6 * a0;
+#pragma unroll
+      for (int k = 0; k < 6; ++k) acc = rfma(col[k], dz[k], acc);
+      const real ax = acc;
+      acc = rfma(col[6], dz[6], acc);
+      acc = rfma(col[7], dz[7], acc);
+      const real dv = -acc;
+      const real du = rfma(t, dv, d);
+      real du0, du1;
+      row_bcast67(du, du0, du1);
+#pragma unroll
+      for (int k = 0; k < 8; ++k) col[k] = p_nxt[ST_ROW(k)];
+      a0 = *lds_at<real>(a_kff);
+      const real nx = rfma(b1, du1, rfma(b0, du0, ax));
+      d = (r < 6) ? nx : du;
+      *lds_at<real>(a_dz) = d;
+      *lds_at<real>(a_dv) = dv;
+      a_col += sb; a_uni += sb; a_dz += s_dz; a_dv += s_dv;
+      const unsigned s_nxt = i < N - 3 ? sb : 0u;  // (the fetch ahead stops at the last stage)
+      a_nxt += s_nxt; a_kff += s_nxt;
+    }
+  } else
   for (int i = 0; i < N - 1; ++i) {
     const real* st = L.st(i);
     real* kn = L.kn(i);
@@ -1548,6 +1694,7 @@ __device__ __forceinline__ void lmpc_solve_problem(
   // (the warm-start kernels too: their cold path is this iteration -- except at two waves per SIMD, where the fused iteration is only
   //  trusted with the polish behind a call, lmpc_fuse_bwd's comment, and the warm kernels keep theirs inline)
   constexpr bool FUSEK = lmpc_fuse_bwd(sizeof(real), KQ, KS) && !(WARMK && lmpc_waves_per_simd(sizeof(real), KQ, KS) >= 2);
+  constexpr bool CHAINA = lmpc_chain_addr(sizeof(real), KQ, KS);  // the stage chains on explicit LDS addresses
   const bool fuse = FUSEK && P.has_sigma != 0;
   Lds<real> L{lds, N, LEAN ? LMPC_LEAN_STAGE_STRIDE : LMPC_STAGE_STRIDE, !SECOND && lmpc_waves_per_simd(sizeof(real), KQ, KS) >= 2};
   if constexpr (SECOND && LMPC_CHAIN_PRIO) __builtin_amdgcn_s_setprio(3);
@@ -2395,14 +2542,14 @@ __device__ __forceinline__ void lmpc_solve_problem(
         }
       } else if (sizeof(real) == 8 && mu <= real(JOSEPH_MU)) {  // (single precision stops at mu ~ 2e-6)
         if (FUSEK && fuse)
-          riccati_factor<(KS > 0), (sizeof(real) == 8), FUSEK>(L, lane, TT + TL_PT, KN_R1, KN_TEY);
+          riccati_factor<(KS > 0), (sizeof(real) == 8), FUSEK, CHAINA>(L, lane, TT + TL_PT, KN_R1, KN_TEY);
         else
-          riccati_factor<(KS > 0), (sizeof(real) == 8)>(L, lane, TT + TL_PT);
+          riccati_factor<(KS > 0), (sizeof(real) == 8), false, CHAINA>(L, lane, TT + TL_PT);
       } else {
         if (FUSEK && fuse)
-          riccati_factor<(KS > 0), false, FUSEK>(L, lane, TT + TL_PT, KN_R1, KN_TEY);
+          riccati_factor<(KS > 0), false, FUSEK, CHAINA>(L, lane, TT + TL_PT, KN_R1, KN_TEY);
         else
-          riccati_factor<(KS > 0), false>(L, lane, TT + TL_PT);
+          riccati_factor<(KS > 0), false, false, CHAINA>(L, lane, TT + TL_PT);
       }
       PT_MARK(3)
     }
@@ -2431,11 +2578,11 @@ __device__ __forceinline__ void lmpc_solve_problem(
       } else {
         if (pass == 0 && ipm && has_sigma) {
           if (FUSEK && fuse)
-            riccati_solve<2, FUSEK>(L, lane, pf);
+            riccati_solve<2, FUSEK, CHAINA>(L, lane, pf);
           else
-            riccati_solve<2>(L, lane, pf);
+            riccati_solve<2, false, CHAINA>(L, lane, pf);
         } else
-          riccati_solve<1>(L, lane, pf);
+          riccati_solve<1, false, CHAINA>(L, lane, pf);
       }
       PT_MARK(5)
       // ======== step of every constrained value; boundary slack by Schur complement ========

@@ -177,4 +177,11 @@ __host__ __device__ constexpr bool lmpc_fuse_bwd(int real_bytes, int kq, int ks)
   return false;                 // fp32 / mixed learning -- measured: -4 %, but 5 instead of 3 of 32768 answers past 1e-3 of the fp64 ones
 }
 
+// The stage chains on explicit LDS byte addresses (CHAIN_ADDR, lmpc_solve_kernel.hip): one address per lane pattern, advanced once
+// per stage, every access of the stage at a compile-time offset from one of them; the clamp of the one-stage-ahead fetch and the
+// `own ? cell : junk` selects become strides of 0.  Same cells, same values, same order: only how an address is formed changes.
+// On for the fp64 tracking classes of N <= 23 (KQ <= 4, KS = 0: the one-wave cold, warm and second-pass instances), whose two waves
+// per SIMD share the VALU with the chain's integer work; off elsewhere (not measured there).  profiles/chain_addresses.md.
+__host__ __device__ constexpr bool lmpc_chain_addr(int real_bytes, int kq, int ks) { return real_bytes == 8 && kq <= 4 && ks == 0; }
+
 #endif

@@ -266,6 +266,19 @@ __device__ __forceinline__ void row_bcast67(real v, real& a, real& b) {  // lane
   b = row_bcast<7>(v);
 }
 
+// LDS byte addresses for the stage chains that walk them (CHAIN_ADDR, lmpc_solve_kernel.hip): the address of a cell of the workgroup's
+// block as a 32-bit number, a typed LDS pointer back from it (its constant indices become the DS instructions' immediate offsets), and
+// the pin that keeps an address a register of its own from stage to stage -- left to itself the optimiser rewrites the walk as
+// base + index * stride and forms every address again at its use.
+#define LMPC_LDS __attribute__((address_space(3)))
+template <typename T>
+__device__ __forceinline__ unsigned lds_addr(const T* p) { return (unsigned)(unsigned long long)(LMPC_LDS const T*)p; }
+template <typename T>
+__device__ __forceinline__ LMPC_LDS T* lds_at(unsigned a) { return (LMPC_LDS T*)(unsigned long long)a; }
+#define CHAIN_ADDR_PIN(a) asm volatile("" : "+v"(a))
+// ... and, for the addresses of 16-byte rows, what the pin hides: that they are 16-byte aligned (ds_read_b128, not two ds_read_b64)
+#define CHAIN_ADDR_PIN16(a) do { CHAIN_ADDR_PIN(a); __builtin_assume(((a) & 15u) == 0u); } while (0)
+
 __device__ __forceinline__ int uni(int x) { return __builtin_amdgcn_readfirstlane(x); }
 template <typename T>
 __device__ __forceinline__ T* uni_ptr(T* p) {
