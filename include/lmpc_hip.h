@@ -626,6 +626,81 @@ int lmpc_fleet_ss_get_laps(lmpc_handle* h, int32_t car, int32_t* n_laps, int32_t
 int lmpc_fleet_ss_stats(lmpc_handle* h, int32_t batch, int32_t* laps_in_ring, int32_t* lap_count, int32_t* n_dropped,
                         double* last_lap_time);
 
+/* Everything between two solves of a FLEET LMPC period in ONE launch: what lmpc_loop_advance_batch does for the tracking loop, for
+ * the experiment in which every car learns from its own laps (each car a RacingMPCNode with its own SafeSetRecorder and
+ * SafeSetManager, driven by the tracking controller until its ring holds warm_laps laps and by the learning controller after).  The
+ * per-car phase, the lap book and the next k-NN query point live on the device; the host may run many periods without reading
+ * anything.  Called on the LEARNING handle (the one that owns the fleet store); the tracking controller is a second handle with the
+ * same N and vehicle, and only its results come here.  Per car b, in this order:
+ *   1 the solution     -- sel = phase[b] as it stands at entry (0 tracking, 1 learning) picks (X_trk, U_trk, status_trk) or (X_lrn,
+ *                         U_lrn, status_lrn), X [6][N][B], U [2][N-1][B], status [B]; a triple may be absent (all three NULL: that
+ *                         controller did not run), and a car of an absent triple counts as a failed solve;
+ *   2 input and plant  -- as lmpc_loop_advance_batch: U_sel[:, 0], or U_ref[:, 0] after a failed solve (racing_mpc_node.cpp:322-332),
+ *                         written to u_prev [2][B]; n_sub sub-steps of dt_sim on x [6][B] in place (racing_simulator.cpp:46-69,97-112),
+ *                         with the vehicle *plant (HOST, may be NULL: the handle's) -- a plant that differs from the controllers'
+ *                         model is what gives the per-car regression something to learn; the optional accumulators distance [B],
+ *                         worst_excess [B] (against knot 0 of the bounds of the period just driven), n_fail [B], any of them NULL;
+ *   3 the next inputs  -- the shift of the solution (racing_mpc_node.cpp:245-254), the shift of the old plan in place after a failed
+ *                         solve, or with restart_failed != 0 the cold start at the new state (:210-235, 261-292), with the phase's
+ *                         own speed_scale[sel], speed_limit[sel], max_vel_ref_diff[sel] (each controller node has its own) and the
+ *                         handle's vehicle; X_ref [6][N][B], U_ref [2][N-1][B], T_ref [N-1][B], bound_left, bound_right, curvatures,
+ *                         vel_ref [N][B] are updated IN PLACE (they must not alias a solution);
+ *   4 x_ic [6][B]      -- the new state; for sel = 1 projected onto the handle's [x_min, x_max] (the state box also binds knot 0,
+ *                         racing_mpc.cpp:147,201);
+ *   5 the recorder     -- lmpc_fleet_ss_record_batch with (new state, input applied, track curvature at the new abscissa, t) and
+ *                         the track's L (RacingMPC::solve, racing_mpc.cpp:246): seeding, the discarded partial lap, the close, the
+ *                         eviction, the overflowed lap dropped, the duration ring;
+ *   6 the lap book     -- when that sample closed a lap and lap_count before it was >= 1: lap_time [n_rec][B] and lap_kind
+ *                         [n_rec][B] at slot lap_count_before - 1 get the lap's duration and sel (slots >= n_rec are not written),
+ *                         n_learn[b] += sel, and counters[1] += 1 when n_learn[b] reaches learn_laps;
+ *   7 the phase        -- with switch_phase != 0: phase[b] 0 -> 1 when the car's ring holds >= warm_laps laps, counters[0] += 1.
+ *                         With switch_phase == 0 no phase changes (the host that polls every p periods passes it only then, so
+ *                         that which controllers it launches stays true until it looks again);
+ *   8 query [2][B]     -- the point lmpc_fleet_ss_query_batch is asked next: (s, e_y) of the last knot of the new X_ref, s aligned
+ *                         with the new (unprojected) abscissa by align_abscissa (racing_mpc.cpp:219-223,249-254).
+ * HEAD-ONLY call: with all six solution pointers NULL steps 1 - 3 are skipped -- no input, no plant, the references stay as
+ * lmpc_prepare_batch left them -- and steps 4 - 8 run on x as given with u_prev as the recorded input: period 0.
+ * phase, n_learn [B], lap_kind [n_rec][B], counters [2] are int32, caller-owned and zero-filled for a fresh experiment, as are
+ * lap_time, x_ic and query; counters are monotone and never zeroed here: cars that have entered the learning phase, cars that have
+ * their learn_laps.  The same arithmetic as the entry points it replaces (tests/test_gpu_fleet_loop.py: bit for bit but for the
+ * last knot's one-step rollout, as lmpc_loop_advance_batch).  Asynchronous on the handle's stream; allocates nothing and reads
+ * nothing back.  LMPC_ERR_ARGUMENT, with nothing written: no fleet store or a batch other than its; a NULL required pointer or a bad
+ * track; one or two members of a solution triple NULL; dt, dt_sim not positive, n_sub, warm_laps, learn_laps or n_rec < 1; a plant
+ * whose model_id or integrator is not built; references aliasing a solution.  LMPC_ERR_UNSUPPORTED with LMPC_LAYOUT_AOS on the
+ * handle.  All pointers DEVICE except plant. */
+typedef struct lmpc_fleet_loop {
+  const double* X_trk;         /* the tracking controller's solution, or all three NULL */
+  const double* U_trk;
+  const int32_t* status_trk;
+  const double* X_lrn;         /* the learning controller's solution, or all three NULL */
+  const double* U_lrn;
+  const int32_t* status_lrn;
+  double* x;                   /* [6][B] in place */
+  double* u_prev;              /* [2][B] */
+  double* X_ref;
+  double* U_ref;
+  double* T_ref;
+  double* bound_left;
+  double* bound_right;
+  double* curvatures;
+  double* vel_ref;
+  double dt, dt_sim, t;        /* control period, plant sub-step, the time stamp of the sample recorded */
+  double speed_scale[2], speed_limit[2], max_vel_ref_diff[2]; /* [0] tracking, [1] learning */
+  int32_t n_sub, restart_failed, warm_laps, learn_laps, switch_phase, n_rec;
+  const lmpc_vehicle* plant;   /* HOST, may be NULL */
+  int32_t* phase;              /* [B] */
+  int32_t* n_learn;            /* [B] */
+  double* lap_time;            /* [n_rec][B] */
+  int32_t* lap_kind;           /* [n_rec][B] */
+  int32_t* counters;           /* [2] */
+  double* x_ic;                /* [6][B] */
+  double* query;               /* [2][B] */
+  double* distance;            /* [B], optional */
+  double* worst_excess;        /* [B], optional */
+  int64_t* n_fail;             /* [B], optional */
+} lmpc_fleet_loop;
+int lmpc_fleet_loop_advance_batch(lmpc_handle* h, int32_t batch, const lmpc_track* track, const lmpc_fleet_loop* io);
+
 /* Per-car error-dynamics regression: SafeSetManager::query(RegQuery) (safe_set.cpp:182-245) as B controllers call it, each on the
  * laps of its OWN SafeSetManager -- lmpc_set_regression_laps / lmpc_regress_batch above with query (b, i) run against the closed laps
  * in car b's ring at the time of each call.  Same spec, same arithmetic, same two sign conventions (the comment at

@@ -27,7 +27,7 @@ _ABI_SYMBOLS = ("lmpc_create", "lmpc_destroy", "lmpc_last_error", "lmpc_set_stre
                 "lmpc_get_warm_accepted", "lmpc_set_waves_per_problem",
                 "lmpc_fleet_ss_create", "lmpc_fleet_ss_destroy", "lmpc_fleet_ss_reset", "lmpc_fleet_ss_bytes", "lmpc_fleet_ss_record_batch",
                 "lmpc_fleet_ss_query_batch", "lmpc_fleet_ss_load", "lmpc_fleet_ss_get_laps", "lmpc_fleet_ss_stats",
-                "lmpc_fleet_ss_set_regression", "lmpc_fleet_ss_regress_batch",
+                "lmpc_fleet_ss_set_regression", "lmpc_fleet_ss_regress_batch", "lmpc_fleet_loop_advance_batch",
                 "lmpc_spline_track_create", "lmpc_spline_track_destroy", "lmpc_spline_track_tabulate", "lmpc_track_sample_batch",
                 "lmpc_global_to_frenet_batch", "lmpc_frenet_to_global_batch",
                 "lmpc_ekf_create", "lmpc_ekf_destroy", "lmpc_ekf_register_observation", "lmpc_ekf_initialize", "lmpc_ekf_set_state",
@@ -68,6 +68,17 @@ class CRegressionSpec(C.Structure):
     """lmpc_regression_spec: RegQuery's index lists and bandwidth (safe_set.hpp:57-75)."""
     _fields_ = [("n_out", C.c_int32), ("out", C.c_int32 * 6), ("n_in_state", C.c_int32), ("in_state", C.c_int32 * 6),
                 ("n_in_ctrl", C.c_int32), ("in_ctrl", C.c_int32 * 2), ("as_written", C.c_int32), ("dist_max", C.c_double)]
+
+
+class CFleetLoop(C.Structure):
+    """lmpc_fleet_loop: everything lmpc_fleet_loop_advance_batch takes beside the handle, the batch and the track."""
+    _fields_ = ([(n, C.c_void_p) for n in "X_trk U_trk status_trk X_lrn U_lrn status_lrn x u_prev X_ref U_ref T_ref bound_left bound_right "
+                                          "curvatures vel_ref".split()]
+                + [("dt", C.c_double), ("dt_sim", C.c_double), ("t", C.c_double), ("speed_scale", C.c_double * 2),
+                   ("speed_limit", C.c_double * 2), ("max_vel_ref_diff", C.c_double * 2)]
+                + [(n, C.c_int32) for n in "n_sub restart_failed warm_laps learn_laps switch_phase n_rec".split()]
+                + [("plant", C.POINTER(CVehicle))]
+                + [(n, C.c_void_p) for n in "phase n_learn lap_time lap_kind counters x_ic query distance worst_excess n_fail".split()])
 
 
 class CEkfConfig(C.Structure):
@@ -745,6 +756,58 @@ class Solver:
                                           _ptr(out.get("n_dropped")), _ptr(out.get("last_lap_time")))
         self._check(rc, "lmpc_fleet_ss_stats")
         return out
+
+    def fleet_loop_state(self, B: int, n_rec: int):
+        """The caller-owned device arrays of fleet_loop_advance for a fresh experiment, zero-filled: phase, n_learn [B], lap_kind
+        [n_rec][B], counters [2] (int32), lap_time [n_rec][B], x_ic [6][B], query [2][B] (float64)."""
+        torch = self._torch
+        i32, f64 = dict(dtype=torch.int32, device=self.device), dict(dtype=torch.float64, device=self.device)
+        return {"phase": torch.zeros(B, **i32), "n_learn": torch.zeros(B, **i32), "lap_kind": torch.zeros((n_rec, B), **i32),
+                "counters": torch.zeros(2, **i32), "lap_time": torch.zeros((n_rec, B), **f64), "x_ic": torch.zeros((6, B), **f64),
+                "query": torch.zeros((2, B), **f64)}
+
+    def fleet_loop_advance(self, track: dict, inp: dict, sol_trk, sol_lrn, x, u_prev, state: dict, dt: float, dt_sim: float, n_sub: int = 1,
+                           t: float = 0.0, speed_scale=(1.0, 1.0), speed_limit=(None, None), max_vel_ref_diff=(None, None),
+                           restart_failed: bool = False, warm_laps: int = 2, learn_laps: int = 4, switch_phase: bool = True, plant=None,
+                           distance=None, worst_excess=None, n_fail=None, n_rec: int | None = None):
+        """lmpc_fleet_loop_advance_batch on this (the learning) solver, which owns the fleet store: everything between two solves of a
+        fleet LMPC period in one launch -- per car the solution of the controller it drives with (state["phase"]: 0 `sol_trk`, 1
+        `sol_lrn`; each a dict with X_optm, U_optm, status, or None when that controller did not run), input and plant, the next
+        references in place in `inp`, state["x_ic"], the car's recorder and ring, the lap book (state["lap_time"], ["lap_kind"],
+        ["n_learn"]), the phase and state["counters"], and state["query"].  Both solutions None: the head-only call of period 0.
+        speed_scale / speed_limit / max_vel_ref_diff: (tracking, learning) pairs; a None limit is this solver's x_max[3], a None
+        difference its max_vel_ref_diff.  plant: a vehicle dict for the plant (None: this solver's).  `state` is fleet_loop_state's
+        dict; n_rec (default: the lap book's first dimension) is how many of its rows the call may write.  Asynchronous; nothing is
+        read back."""
+        self.use_current_stream()
+        ct = self._ctrack(track)
+        io = CFleetLoop()
+        for pre, sol in (("trk", sol_trk), ("lrn", sol_lrn)):
+            for name, key in (("X_", "X_optm"), ("U_", "U_optm"), ("status_", "status")):
+                setattr(io, name + pre, _ptr(None if sol is None else sol.get(key)))
+        io.x, io.u_prev = _ptr(x), _ptr(u_prev)
+        for key in ("X_ref", "U_ref", "T_ref", "bound_left", "bound_right", "curvatures", "vel_ref"):
+            setattr(io, key, _ptr(inp.get(key)))
+        io.dt, io.dt_sim, io.t = float(dt), float(dt_sim), float(t)
+        for i in range(2):
+            io.speed_scale[i] = float(speed_scale[i])
+            io.speed_limit[i] = float(self.config["x_max"][3] if speed_limit[i] is None else speed_limit[i])
+            io.max_vel_ref_diff[i] = float(self.config["max_vel_ref_diff"] if max_vel_ref_diff[i] is None else max_vel_ref_diff[i])
+        io.n_sub, io.restart_failed, io.warm_laps, io.learn_laps = int(n_sub), int(bool(restart_failed)), int(warm_laps), int(learn_laps)
+        io.switch_phase = int(bool(switch_phase))
+        lap_time = state.get("lap_time")
+        io.n_rec = int(n_rec) if n_rec is not None else (int(lap_time.shape[0]) if lap_time is not None else 0)
+        if lap_time is not None and io.n_rec > int(lap_time.shape[0]):
+            raise ValueError("fleet_loop_advance: n_rec exceeds the lap book's rows")
+        cv = None
+        if plant is not None:
+            cv = _fill(CVehicle(), plant)
+            io.plant = C.pointer(cv)
+        for key in ("phase", "n_learn", "lap_time", "lap_kind", "counters", "x_ic", "query"):
+            setattr(io, key, _ptr(state.get(key)))
+        io.distance, io.worst_excess, io.n_fail = _ptr(distance), _ptr(worst_excess), _ptr(n_fail)
+        rc = self.lib.lmpc_fleet_loop_advance_batch(self._h, C.c_int32(x.shape[1]), C.byref(ct), C.byref(io))
+        self._check(rc, "lmpc_fleet_loop_advance_batch")
 
     # ---- per-car error-dynamics regression on the fleet safe set (safe_set.cpp:182-245, one SafeSetManager per car) ----
     def fleet_ss_set_regression(self, in_state=(3, 4, 5), in_ctrl=(0, 1), out_rows=(3, 4, 5), dist_max: float = 1.0,

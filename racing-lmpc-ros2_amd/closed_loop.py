@@ -533,6 +533,94 @@ def run_lmpc_fleet(tracker, learner, track: dict, x0, u0, warm_laps: int = 2, le
             "laps_in_ring": stats["laps_in_ring"].clone(), "steps": k + 1, "x": x, "trace": trace}
 
 
+def run_lmpc_fleet_fused(tracker, learner, track: dict, x0, u0, warm_laps: int = 2, learn_laps: int = 4, dt: float = 0.025,
+                         n_sub: int = 2, warm_speed_scale: float = 0.7, max_steps: int = 20000, max_pts_per_lap: int = 1024,
+                         record_trace: bool = False, regression: dict | None = None, plant=None, poll: int = 1):
+    """run_lmpc_fleet with everything between two solves in one launch, lmpc_fleet_loop_advance_batch on `learner`: input selection
+    between the two controllers' results, plant, shift, x_ic, every car's recorder and ring, the lap book, the per-car phase and the
+    next query point.  Same arguments, same experiment, same return dictionary; per period the fleet query when any car learns, the
+    solve of each controller that has cars, and that one call.
+
+    The phase, the lap book and the query live on the device.  The host reads two int32 counters -- cars in the learning phase, cars
+    that have their learning laps -- every `poll` periods, and only the call of such a period may switch a car's phase, so what the
+    host knows about which controllers have cars stays true in between: with poll > 1 whole runs of periods are enqueued without a
+    read, a car switches up to poll - 1 periods after its ring is full, and the run ends up to poll - 1 periods late.  poll = 1 is
+    run_lmpc_fleet's schedule.
+
+    plant (a Solver): its VEHICLE drives the cars (the call takes the plant's vehicle by value).  record_trace: the curvature in the
+    (x, u, k, t) tuples is run_lmpc_fleet's torch interpolation; the ring holds the kernel's own lookup at the same abscissa.
+    Raises ValueError when the two solvers differ in N or vehicle: one launch shifts both controllers' plans with one model."""
+    import numpy as np
+    import torch
+
+    if int(tracker.N) != int(learner.N) or dict(tracker.vehicle) != dict(learner.vehicle):
+        raise ValueError("run_lmpc_fleet_fused: tracker and learner must have the same N and the same vehicle")
+    if poll < 1:
+        raise ValueError("run_lmpc_fleet_fused: poll must be >= 1")
+    trk = tracker.device_track(track)
+    L = float(track["L"])
+    B = x0.shape[1]
+    dev = x0.device
+    learner.fleet_ss_create(B, max_pts_per_lap)
+    if regression is not None:
+        learner.fleet_ss_set_regression(**regression)
+    x, u_prev = x0.clone(), u0.clone()
+    worst_excess = torch.zeros(B, dtype=torch.float64, device=dev)
+    n_fail = torch.zeros(B, dtype=torch.int64, device=dev)
+    inp = tracker.prepare(trk, x, dt, speed_scale=warm_speed_scale)
+    out_t, out_l = tracker.alloc_outputs(B), learner.alloc_outputs(B)
+    S = int(learner.config["num_ss_pts"])
+    out_l["convex_combi_optm"] = torch.zeros((S, B), dtype=torch.float64, device=dev)
+    ss_buf = (torch.zeros((6, S, B), dtype=torch.float64, device=dev), torch.zeros((S, B), dtype=torch.float64, device=dev),
+              torch.zeros((B,), dtype=torch.int32, device=dev))
+    n_rec = warm_laps + learn_laps + 8
+    state = learner.fleet_loop_state(B, n_rec)
+    kw = dict(dt=dt, dt_sim=dt / n_sub, n_sub=n_sub, speed_scale=(warm_speed_scale, 1.0),
+              speed_limit=(float(tracker.config["x_max"][3]), float(learner.config["x_max"][3])),
+              max_vel_ref_diff=(float(tracker.config["max_vel_ref_diff"]), float(learner.config["max_vel_ref_diff"])),
+              restart_failed=False, warm_laps=warm_laps, learn_laps=learn_laps, plant=None if plant is None else plant.vehicle,
+              worst_excess=worst_excess, n_fail=n_fail)
+    curv = trk["curvature"]
+    M = int(curv.numel())
+    trace, t, k = [], 0.0, -1
+
+    def note():
+        pos = torch.remainder(x[0], L) * (M / L)
+        i0 = torch.clamp(pos.floor().long(), 0, M - 1)
+        fr = pos - i0
+        trace.append((x.clone(), u_prev.clone(), curv[i0] * (1.0 - fr) + curv[(i0 + 1) % M] * fr, t))
+
+    # period 0: nothing to apply yet -- the recorder's first sample, x_ic and the query on the prepared references
+    learner.fleet_loop_advance(trk, inp, None, None, x, u_prev, state, t=t, switch_phase=True, **kw)
+    if record_trace:
+        note()
+    n_lrn = n_done = 0
+    for k in range(max_steps):
+        if k % poll == 0:
+            n_lrn, n_done = (int(v) for v in state["counters"].cpu())   # the only read, every `poll` periods
+        if n_done == B:
+            break
+        some, every = n_lrn > 0, n_lrn == B
+        inp["x_ic"], inp["u_ic"] = state["x_ic"], u_prev
+        if some:
+            ss_x, ss_j, _ = learner.fleet_ss_query(state["query"], out=ss_buf)
+            learner.solve(inp, out_l, ss_x=ss_x, ss_j=ss_j)
+        if not every:
+            tracker.solve(inp, out_t)
+        t += dt
+        learner.fleet_loop_advance(trk, inp, None if every else out_t, out_l if some else None, x, u_prev, state, t=t,
+                                   switch_phase=(k + 1) % poll == 0, **kw)
+        if record_trace:
+            note()
+    stats = learner.fleet_ss_stats(B)
+    n_closed = np.minimum(np.maximum(stats["lap_count"].cpu().numpy() - 1, 0), n_rec)
+    lt, lk = state["lap_time"].cpu().numpy(), state["lap_kind"].cpu().numpy()
+    return {"lap_times": [[float(v) for v in lt[:n_closed[b], b]] for b in range(B)],
+            "lap_kind": [["lmpc" if v else "tracking" for v in lk[:n_closed[b], b]] for b in range(B)],
+            "worst_excess": worst_excess, "n_fail": n_fail, "n_dropped": stats["n_dropped"], "laps_in_ring": stats["laps_in_ring"],
+            "steps": k + 1, "x": x, "trace": trace}
+
+
 def run_lqr(solver, x0, X_traj, U_traj, steps: int):
     """Receding-horizon LQR tracking of a long reference, the loop of the reference's own test (test_racing_lqr.cpp): period t solves
     on the window t .. t+N-1 of the trajectory (N = the horizon of solver.lqr_create, which the caller has made for at least B cars)

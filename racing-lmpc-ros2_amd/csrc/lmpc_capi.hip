@@ -26,6 +26,7 @@
 #include "lmpc_vanilla.h"
 #include "lmpc_fleet_reg.h"
 #include "lmpc_fleet_ss.h"
+#include "lmpc_fleet_loop.h"
 
 namespace {
 // Move-only owner of one device (PINNED: pinned host) allocation: freed by the destructor, and by alloc() before it allocates anew.
@@ -1620,6 +1621,46 @@ int lmpc_fleet_ss_stats(lmpc_handle* h, int32_t batch, int32_t* laps_in_ring, in
   HIP_TRY(h, hipSetDevice(h->device));
   hipLaunchKernelGGL(lmpc_fleet_ss_stats_kernel, dim3((batch + 255) / 256), dim3(256), 0, h->stream, h->fleet, laps_in_ring, lap_count,
                      n_dropped, last_lap_time);
+  HIP_TRY(h, hipGetLastError());
+  return LMPC_OK;
+}
+
+// ---- everything between two solves of a fleet LMPC period (csrc/lmpc_fleet_loop_kernel.hip) ----
+int lmpc_fleet_loop_advance_batch(lmpc_handle* h, int32_t batch, const lmpc_track* track, const lmpc_fleet_loop* io) {
+  if (!h) return LMPC_ERR_ARGUMENT;
+  const char* who = "lmpc_fleet_loop_advance_batch";
+  if (!io) return fail(h, LMPC_ERR_ARGUMENT, std::string(who) + ": io is NULL");
+  const int rc = fleet_check(h, batch, who);
+  if (rc != LMPC_OK) return rc;
+  if (!track_ok(track)) return fail(h, LMPC_ERR_ARGUMENT, std::string(who) + ": bad track");
+  if (!io->x || !io->u_prev || !io->X_ref || !io->U_ref || !io->T_ref || !io->bound_left || !io->bound_right || !io->curvatures ||
+      !io->vel_ref || !io->phase || !io->n_learn || !io->lap_time || !io->lap_kind || !io->counters || !io->x_ic || !io->query)
+    return fail(h, LMPC_ERR_ARGUMENT, std::string(who) + ": a required pointer is NULL");
+  const int n_trk = (io->X_trk != nullptr) + (io->U_trk != nullptr) + (io->status_trk != nullptr);
+  const int n_lrn = (io->X_lrn != nullptr) + (io->U_lrn != nullptr) + (io->status_lrn != nullptr);
+  if ((n_trk != 0 && n_trk != 3) || (n_lrn != 0 && n_lrn != 3))
+    return fail(h, LMPC_ERR_ARGUMENT, std::string(who) + ": a solution is X, U and status, or none of them");
+  if (!(io->dt > 0.0) || !(io->dt_sim > 0.0) || io->n_sub < 1) return fail(h, LMPC_ERR_ARGUMENT, std::string(who) + ": dt, dt_sim must be positive and n_sub >= 1");
+  if (io->warm_laps < 1 || io->learn_laps < 1 || io->n_rec < 1)
+    return fail(h, LMPC_ERR_ARGUMENT, std::string(who) + ": warm_laps, learn_laps and n_rec must be >= 1");
+  if (io->plant && io->plant->model_id != LMPC_MODEL_SINGLE_TRACK_PLANAR)
+    return fail(h, LMPC_ERR_ARGUMENT, std::string(who) + ": plant: only single_track_planar_model is built");
+  if (io->plant && io->plant->integrator != LMPC_INTEGRATOR_RK4 && io->plant->integrator != LMPC_INTEGRATOR_EULER)
+    return fail(h, LMPC_ERR_ARGUMENT, std::string(who) + ": plant: integrator must be LMPC_INTEGRATOR_RK4 or LMPC_INTEGRATOR_EULER");
+  if ((io->X_trk && (io->X_ref == io->X_trk || io->U_ref == io->U_trk)) || (io->X_lrn && (io->X_ref == io->X_lrn || io->U_ref == io->U_lrn)))
+    return fail(h, LMPC_ERR_ARGUMENT, std::string(who) + ": the references must not alias a solution");
+  if (h->out_aos) return fail(h, LMPC_ERR_UNSUPPORTED, std::string(who) + " reads the solutions in the [component][knot][batch] layout");
+  HIP_TRY(h, hipSetDevice(h->device));
+  lmpc_fleet_loop_consts K{};
+  K.N = h->P.N;
+  for (int k = 0; k < 6; ++k) K.x_min[k] = h->P.x_min[k], K.x_max[k] = h->P.x_max[k];
+  K.veh = h->P.veh;
+  K.plant = io->plant ? *io->plant : h->P.veh;
+  lmpc_fleet_loop dev = *io;
+  dev.plant = nullptr;  // (a host pointer: the kernel takes the vehicle by value)
+  dev.restart_failed = io->restart_failed ? 1 : 0;
+  h->fleet_L = track->L;  // what the query unrolls the laps by, as lmpc_fleet_ss_record_batch notes it
+  hipLaunchKernelGGL(lmpc_fleet_loop_kernel, dim3((batch + 63) / 64), dim3(64 * lmpc_loop_waves), 0, h->stream, K, h->fleet, *track, dev);
   HIP_TRY(h, hipGetLastError());
   return LMPC_OK;
 }

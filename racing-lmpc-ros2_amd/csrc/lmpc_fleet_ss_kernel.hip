@@ -19,6 +19,7 @@
 
 #include "lmpc_fleet_ss.h"
 #include "lmpc_knn_select.hip.h"
+#include "lmpc_loop_steps.hip.h"  // lmpc_fleet_record_car: the recorder's step, shared with lmpc_fleet_loop_kernel.hip
 
 // ---- recorder: SafeSetRecorder::step (safe_set.cpp:278-322) + SafeSetManager::add_lap (:144-151), one thread per car ----
 __global__ __launch_bounds__(256) void lmpc_fleet_ss_record_kernel(lmpc_fleet_store st, const double* __restrict__ x,
@@ -27,57 +28,10 @@ __global__ __launch_bounds__(256) void lmpc_fleet_ss_record_kernel(lmpc_fleet_st
   const int b = (int)(blockIdx.x * blockDim.x + threadIdx.x), B = st.B;
   if (b >= B) return;
   if (active && active[b] == 0) return;
-  const double s = x[b];
-  int fl = st.flags[b];
-  if (!(fl & LMPC_FLEET_FLAG_VALID)) {  // the very first sample only seeds the abscissa (:278-282)
-    st.s_prev[b] = s;
-    st.flags[b] = fl | LMPC_FLEET_FLAG_VALID;
-    return;
-  }
-  const double sp = st.s_prev[b];
-  st.s_prev[b] = s;
-  const int R1 = st.R + 1, C = st.C;
-  int head = st.head[b], at = -1;
-  if (sp - s > 0.5 * Lt) {  // crossed the start line
-    if (fl & LMPC_FLEET_FLAG_INIT) {
-      const size_t slot = (size_t)b * R1 + head;
-      const int dn = st.dur_n[b];
-      st.dur[(size_t)b * LMPC_FLEET_DUR + dn % LMPC_FLEET_DUR] = t - st.aux[slot * C * 4 + 3];  // t at the crossing - t of the lap's first sample
-      st.dur_n[b] = dn + 1;
-      if (fl & LMPC_FLEET_FLAG_OVERFLOW) {  // longer than a slot: not added, nothing evicted; the slot is reused for the next lap
-        st.n_dropped[b] += 1;
-      } else {  // the open lap becomes the newest of the ring where it stands; the next slot (unused, or the oldest lap) opens
-        st.npts[slot] = st.open_n[b];
-        head = head + 1 == R1 ? 0 : head + 1;
-        st.head[b] = head;
-        const int c = st.cnt[b];
-        if (c < st.R) st.cnt[b] = c + 1;
-      }
-    }  // else: the first, partial lap is discarded (:296-300)
-    st.flags[b] = (fl | LMPC_FLEET_FLAG_INIT) & ~LMPC_FLEET_FLAG_OVERFLOW;
-    st.lap_count[b] += 1;
-    st.open_n[b] = 1;  // the closing sample starts the next lap
-    at = 0;
-  } else if (fl & LMPC_FLEET_FLAG_INIT) {
-    const int n = st.open_n[b];
-    if (n < C) {
-      at = n;
-      st.open_n[b] = n + 1;
-    } else if (!(fl & LMPC_FLEET_FLAG_OVERFLOW)) {  // the slot is full: the lap stops storing and will be dropped at its close
-      st.flags[b] = fl | LMPC_FLEET_FLAG_OVERFLOW;
-    }
-  }
-  if (at < 0) return;
-  const size_t row = ((size_t)b * R1 + head) * C + at;  // at < C, head <= R: inside car b's slots
-  st.key[row] = make_double2(s, x[(size_t)B + b]);
-  double* xr = st.xr + row * 4;
-  double* ax = st.aux + row * 4;
+  double xs[6];
 #pragma unroll
-  for (int c = 0; c < 4; ++c) xr[c] = x[(size_t)(2 + c) * B + b];
-  ax[0] = u[b];
-  ax[1] = u[(size_t)B + b];
-  ax[2] = k[b];
-  ax[3] = t;
+  for (int c = 0; c < 6; ++c) xs[c] = x[(size_t)c * B + b];
+  lmpc_fleet_record_car(st, b, xs, u[b], u[(size_t)B + b], k[b], t, Lt);
 }
 
 // ---- SafeSetRecorder::load (safe_set.cpp:260-276) for one car (grid 1) or every car (grid B): one workgroup per car pushes

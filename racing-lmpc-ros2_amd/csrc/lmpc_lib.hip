@@ -4,6 +4,7 @@
 #include "lmpc_solve_kernel.hip"
 #include "lmpc_ss_kernel.hip"
 #include "lmpc_fleet_ss_kernel.hip"
+#include "lmpc_fleet_loop_kernel.hip"
 #include "lmpc_reg_kernel.hip"
 #include "lmpc_sqp_kernel.hip"
 #include "lmpc_track_kernel.hip"

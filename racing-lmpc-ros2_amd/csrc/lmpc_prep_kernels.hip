@@ -10,6 +10,7 @@
 #include "lmpc_device.h"
 #include "lmpc_dynamics.hip.h"
 #include "lmpc_track.hip.h"  // track_lookup: the periodic linear lookup into an lmpc_track's tables
+#include "lmpc_loop_steps.hip.h"  // sample_refs, and the per-car steps lmpc_loop_advance_kernel shares with lmpc_fleet_loop_kernel.hip
 
 // One thread per (problem b, stage i).  blockIdx.y = stage, so a wave covers 64 consecutive
 // problems of one stage.  Forward-mode chain rule through the four RK4 stages:
@@ -120,18 +121,6 @@ template __global__ void lmpc_linearize_kernel<true, double, 2>(lmpc_params, int
                                                              const double*, double*, double*, double*);
 template __global__ void lmpc_linearize_kernel<true, float, 2>(lmpc_params, int, const float*, const float*, const float*, const float*,
                                                             float*, float*, float*);
-
-// Reference sampling at one knot (racing_mpc_node.cpp:261-292): bounds, curvature, clamped velocity reference.
-__device__ __forceinline__ void sample_refs(const lmpc_track& trk, double s, double cur, double d, double speed_scale,
-                                            double speed_limit, double& bl, double& br, double& kap, double& vr_out) {
-  kap = track_lookup(trk.curvature, trk.M, trk.L, s);
-  bl = track_lookup(trk.bound_left, trk.M, trk.L, s);
-  br = track_lookup(trk.bound_right, trk.M, trk.L, s);
-  const double vr = track_lookup(trk.vel, trk.M, trk.L, s) * speed_scale;
-  const double lim = fmin(fmax(speed_limit, cur - d), cur + d);       // :273-275
-  const double clipped = fmin(fmax(vr, cur - d), cur + d);
-  vr_out = (vr > 0.0) ? fmin(clipped, lim) : lim;                     // :276-285
-}
 
 // Warm-start shift of RacingMPCNode::on_step_timer (racing_mpc_node.cpp:245-254): the previous solution moves
 // one knot forward, the last input is repeated, the last state is rolled out with the model, and the references
@@ -261,7 +250,7 @@ __global__ __launch_bounds__(256) void lmpc_prepare_kernel(lmpc_params P, int B,
 // (wave w: knots w, w + W, ...; reads from the solution only, writes the references: no hazard, no barrier).  A car whose solve
 // failed is wave 0's alone, knot after knot: the cold restart is a rollout, and the shift of the OLD plan is done in place (a
 // thread reads knot i + 1 before it writes knot i + 1) -- which is why the reference arrays carry no __restrict__.
-constexpr int lmpc_loop_waves = 8;  // (measured on the closed loop at 4 / 8 / 16, profiles/r05_tail_ab.txt: 6.49 / 6.53 / 6.36 M car-steps/s at 4096 cars warm)
+// (lmpc_loop_waves = 8: lmpc_loop_steps.hip.h)
 __global__ __launch_bounds__(64 * lmpc_loop_waves) void lmpc_loop_advance_kernel(
     lmpc_params P, int B, lmpc_track trk, const int* __restrict__ status, const int* __restrict__ iters, const double* __restrict__ X_sol,
     const double* __restrict__ U_sol, double* __restrict__ x_io, double* __restrict__ u_prev, double dt, double dt_sim, int nsub,
@@ -282,6 +271,7 @@ __global__ __launch_bounds__(64 * lmpc_loop_waves) void lmpc_loop_advance_kernel
   }
   if (!live) return;
   const double d = P.max_vel_ref_diff;
+  const lmpc_ref_arrays refs{X_ref, U_ref, T_ref, bl, br, curv, vref};
   double x[6], xn[6], u[2];
   if (w == 0) {
     // ---- the input applied, the plant ----
@@ -290,17 +280,7 @@ __global__ __launch_bounds__(64 * lmpc_loop_waves) void lmpc_loop_advance_kernel
 #pragma unroll
     for (int k = 0; k < 6; ++k) x[k] = x_io[(size_t)k * B + b];
     const double s_before = x[0];
-    for (int j = 0; j < nsub; ++j) {
-      if (fabs(x[3]) < 1e-6) x[3] = copysign(1e-6, x[3]);
-      const double kap = track_lookup(trk.curvature, trk.M, trk.L, x[0]);
-      lmpc_fd(P.veh, x, u, kap, dt_sim, xn);
-      const double s1 = xn[0], s2 = trk.L / 2.0;
-      const double kk = fabs(s2 - s1) + trk.L / 2.0;
-      const double ll = kk - fmod(kk, trk.L);
-      xn[0] = s1 + ll * ((s2 > s1) - (s2 < s1));
-#pragma unroll
-      for (int k = 0; k < 6; ++k) x[k] = xn[k];
-    }
+    LMPC_PLANT_SUBSTEPS(P.veh, trk, x, u, dt_sim, nsub, xn)
 #pragma unroll
     for (int k = 0; k < 6; ++k) x_io[(size_t)k * B + b] = x[k];
 #pragma unroll
@@ -317,90 +297,20 @@ __global__ __launch_bounds__(64 * lmpc_loop_waves) void lmpc_loop_advance_kernel
     }
     if (n_fail && !ok) n_fail[b] += 1;
   }
-  // ---- the next period's inputs ----
+  // ---- the next period's inputs (lmpc_loop_steps.hip.h) ----
   if (!ok) {
     if (w != 0) return;
     if (restart_failed) {  // cold start at the new state (lmpc_prepare_kernel)
-      const double u0[2] = {1e-9, 1e-9};
-      for (int i = 0; i < N; ++i) {
-#pragma unroll
-        for (int k = 0; k < 6; ++k) X_ref[(size_t)(k * N + i) * B + b] = x[k];
-        double b_l, b_r, kap, vr;
-        sample_refs(trk, x[0], x[3], d, speed_scale, speed_limit, b_l, b_r, kap, vr);
-        bl[(size_t)i * B + b] = b_l;
-        br[(size_t)i * B + b] = b_r;
-        curv[(size_t)i * B + b] = kap;
-        vref[(size_t)i * B + b] = vr;
-        if (i < NS) {
-          U_ref[(size_t)(0 * NS + i) * B + b] = u0[0];
-          U_ref[(size_t)(1 * NS + i) * B + b] = u0[1];
-          T_ref[(size_t)i * B + b] = dt;
-          lmpc_fd(P.veh, x, u0, kap, dt, xn);
-#pragma unroll
-          for (int k = 0; k < 6; ++k) x[k] = xn[k];
-        }
-      }
+      LMPC_CAR_COLD_RESTART(P.veh, trk, refs, b, B, N, x, xn, dt, d, speed_scale, speed_limit)
       return;
     }
-    for (int i = 0; i < N; ++i) {  // the plan the failed solve started from, shifted in place (lmpc_shift_kernel with X_old = X_ref)
-      if (i < NS) {
-#pragma unroll
-        for (int k = 0; k < 6; ++k) x[k] = X_ref[(size_t)(k * N + i + 1) * B + b];
-      } else {
-#pragma unroll
-        for (int k = 0; k < 6; ++k) x[k] = xn[k];
-      }
-#pragma unroll
-      for (int k = 0; k < 6; ++k) X_ref[(size_t)(k * N + i) * B + b] = x[k];
-      double b_l, b_r, kap, vr;
-      sample_refs(trk, x[0], x[3], d, speed_scale, speed_limit, b_l, b_r, kap, vr);
-      bl[(size_t)i * B + b] = b_l;
-      br[(size_t)i * B + b] = b_r;
-      curv[(size_t)i * B + b] = kap;
-      vref[(size_t)i * B + b] = vr;
-      if (i < NS) {
-        const int src = (i < NS - 1) ? i + 1 : NS - 1;
-#pragma unroll
-        for (int k = 0; k < 2; ++k) {
-          u[k] = U_ref[(size_t)(k * NS + src) * B + b];
-          U_ref[(size_t)(k * NS + i) * B + b] = u[k];
-        }
-        T_ref[(size_t)i * B + b] = dt;
-        if (i == NS - 1) lmpc_fd(P.veh, x, u, kap, dt, xn);
-      }
-    }
+    // the plan the failed solve started from, shifted in place (lmpc_shift_kernel with X_old = X_ref)
+    LMPC_CAR_SHIFT_IN_PLACE(P.veh, trk, refs, b, B, N, x, xn, u, dt, d, speed_scale, speed_limit)
     return;
   }
   // the solution, shifted: knot i of the new reference is knot i + 1 of the solution; the last one is rolled out from the
   // new knot N - 2 with the repeated last input (racing_mpc_node.cpp:247-249)
-  for (int i = w; i < N; i += lmpc_loop_waves) {
-    if (i < NS) {
-#pragma unroll
-      for (int k = 0; k < 6; ++k) x[k] = X_sol[(size_t)(k * N + i + 1) * B + b];
-    } else {
-      double xm[6];
-#pragma unroll
-      for (int k = 0; k < 6; ++k) xm[k] = X_sol[(size_t)(k * N + NS) * B + b];
-#pragma unroll
-      for (int k = 0; k < 2; ++k) u[k] = U_sol[(size_t)(k * NS + NS - 1) * B + b];
-      const double kap_m = track_lookup(trk.curvature, trk.M, trk.L, xm[0]);
-      lmpc_fd(P.veh, xm, u, kap_m, dt, x);
-    }
-#pragma unroll
-    for (int k = 0; k < 6; ++k) X_ref[(size_t)(k * N + i) * B + b] = x[k];
-    double b_l, b_r, kap, vr;
-    sample_refs(trk, x[0], x[3], d, speed_scale, speed_limit, b_l, b_r, kap, vr);
-    bl[(size_t)i * B + b] = b_l;
-    br[(size_t)i * B + b] = b_r;
-    curv[(size_t)i * B + b] = kap;
-    vref[(size_t)i * B + b] = vr;
-    if (i < NS) {
-      const int src = (i < NS - 1) ? i + 1 : NS - 1;
-#pragma unroll
-      for (int k = 0; k < 2; ++k) U_ref[(size_t)(k * NS + i) * B + b] = U_sol[(size_t)(k * NS + src) * B + b];
-      T_ref[(size_t)i * B + b] = dt;
-    }
-  }
+  for (int i = w; i < N; i += lmpc_loop_waves) lmpc_car_shift_knot(P.veh, trk, refs, b, B, N, i, X_sol, U_sol, x, dt, d, speed_scale, speed_limit);
 }
 
 // Launch order for the next solve of a closed-loop batch: problems sorted by the iteration count of their last solve,
