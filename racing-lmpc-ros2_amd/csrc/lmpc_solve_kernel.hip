@@ -634,7 +634,12 @@ __device__ __forceinline__ void riccati_solve(const Lds<real>& L, int lane, Prof
 // WARM (lmpc_solve_batch_warm): the rollout TRACKS a plan -- v_i = v_i^plan - K_i (z_i - z_i^plan) -- whose knots sit in the rhs0
 // cells of the knot records ([z^plan (8) | v^plan (2)] at KN_R0: free between the factorisation that has read its weights
 // there and the first gradient): the plan made dynamically exact about this linearisation, a few 1e-3 from where it was.
-template <bool WARM = false, typename real>
+// CHAIN_ADDR (lmpc_chain_addr, lmpc_solve_layout.hip.h): the forward sweep's form.  Component r of z_i stays in one register per lane and
+// reaches the other lanes by row_newbcast; M(r, :), g, dt -- and the plan's knot of a WARM rollout -- of stage i + 1 are fetched during
+// stage i through addresses that advance once per stage (stride 0 once the fetch ahead has reached the last stage); z_{i+1} and v_i are
+// stored off the chain (a dead cell: stride 0), so nothing a stage reads was written by the loop and the one wave_sync() is at the end.
+// The arithmetic is the loop's below, operation for operation.
+template <bool WARM = false, bool CHAIN_ADDR = false, typename real>
 __device__ __forceinline__ void feedback_rollout(const Lds<real>& L, int lane) {
   FRESH_LANE(lane);
   const int N = L.N, r = lane & 7;
@@ -642,6 +647,80 @@ __device__ __forceinline__ void feedback_rollout(const Lds<real>& L, int lane) {
   real* T = L.tail();
   real* const junk0 = T + TL_W + lane;
   real* const junk1 = T + TL_W + 80 + lane;
+  if constexpr (CHAIN_ADDR) {
+    const unsigned sb = L.stride * sizeof(real);
+    constexpr unsigned kb = LMPC_KNOT_STRIDE * sizeof(real);
+    const int o_g = ST_G + (r < 6 ? r : 0);
+    real d = L.kn(0)[r];  // component r of z_i
+    real col[8], t, g;    // M(r, :), dt and g of the stage: fetched one stage ahead
+    real pl[8], pv = 0.0; // WARM: the plan's knot, z^plan (wave-uniform) and this lane's v^plan
+    {
+      const real* st = L.st(0);
+#pragma unroll
+      for (int k = 0; k < 8; ++k) col[k] = st[ST_ROW(k) + r];
+      t = st[ST_DT];
+      g = st[o_g];
+      if constexpr (WARM) {
+        const real* kn = L.kn(0);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) pl[k] = kn[KN_R0 + k];
+        pv = kn[KN_R0 + 8 + (r & 1)];
+      }
+    }
+    const int in = N > 2 ? 1 : 0;
+    unsigned a_nxt = lds_addr(L.st(in) + r);                                 // column-indexed: M(r, :) of the stage fetched ahead
+    unsigned a_ng = lds_addr(L.st(in) + o_g);                                // ... its g
+    unsigned a_uni = lds_addr(L.st(in));                                     // ... and, wave-uniform, its dt
+    unsigned a_pl = lds_addr(L.kn(in) + KN_R0);                              // WARM: the plan's knot of that stage (wave-uniform)
+    unsigned a_pv = lds_addr(L.kn(in) + KN_R0 + 8 + (r & 1));
+    unsigned a_z = lds_addr(own ? L.kn(1) + r : junk0);                      // store targets (a dead cell: stride 0)
+    unsigned a_v = lds_addr((own && r >= 6) ? L.kn(0) + 2 + r : junk1);
+    const unsigned s_z = own ? kb : 0u, s_v = (own && r >= 6) ? kb : 0u;
+    for (int i = 0; i < N - 1; ++i) {
+      CHAIN_ADDR_PIN(a_nxt); CHAIN_ADDR_PIN(a_ng); CHAIN_ADDR_PIN(a_uni); CHAIN_ADDR_PIN(a_z); CHAIN_ADDR_PIN(a_v);
+      if constexpr (WARM) { CHAIN_ADDR_PIN16(a_pl); CHAIN_ADDR_PIN(a_pv); }
+      const LMPC_LDS real* const p_nxt = lds_at<real>(a_nxt);
+      real dz[8];
+      row_bcast8(d, dz);
+      real acc = 0.0;
+#pragma unroll
+      for (int k = 0; k < 6; ++k) acc = rfma(col[k], dz[k], acc);
+      const real ax = acc;
+      acc = rfma(col[6], dz[6], acc);
+      acc = rfma(col[7], dz[7], acc);
+      real v = -acc;
+      if constexpr (WARM) {  // (lanes 6, 7: col = a row of K)  v = v^plan + K z^plan - K z
+        real kz = pv;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) kz = rfma(col[k], pl[k], kz);
+        v += kz;
+      }
+      const real u = rfma(t, v, d);  // (lanes 6, 7: their own component of z is u_{i-1})
+      real u0, u1;
+      row_bcast67(u, u0, u1);
+      const real b0 = col[6], b1 = col[7], gi = g;
+#pragma unroll
+      for (int k = 0; k < 8; ++k) col[k] = p_nxt[ST_ROW(k)];
+      t = lds_at<real>(a_uni)[ST_DT];
+      g = *lds_at<real>(a_ng);
+      if constexpr (WARM) {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) pl[k] = lds_at<real>(a_pl)[k];
+        pv = *lds_at<real>(a_pv);
+      }
+      const real nx = gi + rfma(b1, u1, rfma(b0, u0, ax));
+      d = (r < 6) ? nx : u;
+      *lds_at<real>(a_z) = d;
+      *lds_at<real>(a_v) = v;
+      const unsigned s_nxt = i < N - 3 ? sb : 0u;  // (the fetch ahead stops at the last stage)
+      a_nxt += s_nxt; a_ng += s_nxt; a_uni += s_nxt; a_z += s_z; a_v += s_v;
+      if constexpr (WARM) {
+        const unsigned s_pl = i < N - 3 ? kb : 0u;
+        a_pl += s_pl; a_pv += s_pl;
+      }
+    }
+    wave_sync();
+  } else
   for (int i = 0; i < N - 1; ++i) {
     const real* st = L.st(i);
     real* kn = L.kn(i);
@@ -1096,6 +1175,9 @@ struct PolishResult {
   int noise;  // refused, and the last round failed on nothing but the multiplier steps / the held rows' residual (see the exit of lmpc_solve_problem)
   real sigma, mu, rdmax, last_step;
   double lm[KS > 0 ? KS : 1];  // the simplex weights of an accepted polish
+#ifdef LMPC_PHASE_TIMING
+  long long prof[4];  // the attempt's own clocks: factorisations, backward sweeps, forward sweeps, everything else
+#endif
 };
 
 template <typename real, int KQ, int KS, typename io, bool SECOND = false>  // (SECOND: see lmpc_solve_problem)
@@ -1108,6 +1190,7 @@ __device__ __forceinline__ PolishResult<real, KS> lmpc_polish(const PolishArgs<r
   const int lane = threadIdx.x;
   const int N = uni(a.N), NS = N - 1;
   constexpr bool LEAN = lmpc_lean(sizeof(real), KQ);
+  constexpr bool CHAINA = lmpc_chain_addr(sizeof(real), KQ, KS);  // the stage chains on explicit LDS addresses, as in the iteration
   Lds<real> L{lds, N, LEAN ? LMPC_LEAN_STAGE_STRIDE : LMPC_STAGE_STRIDE, !SECOND && lmpc_waves_per_simd(sizeof(real), KQ, KS) >= 2};
   real* const T = L.tail();
   treal* const TT = reinterpret_cast<treal*>(T + LMPC_TAIL_DOUBLES);
@@ -1124,7 +1207,7 @@ __device__ __forceinline__ PolishResult<real, KS> lmpc_polish(const PolishArgs<r
   real sigma = uni(a.sigma);
   real hsig = 0.0, ce = 0.0, mu = 0.0, rdmax = 0.0, last_step = 0.0;
   int pol_rounds = uni(a.pol_rounds);
-  Prof pf;
+  PT_DECL
   (void)pf;
   (void)tinf;
   const int KNB = NS * L.stride;
@@ -1331,10 +1414,12 @@ __device__ __forceinline__ PolishResult<real, KS> lmpc_polish(const PolishArgs<r
     hsig = uni(qsig + wave_sum(eysum));
     ++pol_rounds;
     wave_sync();
+    PT_MARK(0)
     if constexpr (LEAN)
       riccati_factor_lean<(KS > 0), true>(L, MS, lane, TT + TL_PT);
     else
-      riccati_factor<(KS > 0), true>(L, lane, TT + TL_PT);
+      riccati_factor<(KS > 0), true, false, CHAINA>(L, lane, TT + TL_PT);
+    PT_MARK(3)
     bool nan_step = false;
     // ---- pol::steps multiplier steps on that factor, each from the point the one before has reached ----
     for (int k = 0; k < pol::steps; ++k) {
@@ -1406,6 +1491,7 @@ __device__ __forceinline__ PolishResult<real, KS> lmpc_polish(const PolishArgs<r
         if (lane < 6) L.kn(N - 1)[KN_R0 + lane] += real(TT[TL_TG + lane]);
       }
       wave_sync();
+      PT_MARK(0)
       if constexpr (LEAN) {
         if (k == 0 && has_sigma)
           riccati_solve_lean_dpp<2>(L, MS, lane, pf);
@@ -1413,9 +1499,9 @@ __device__ __forceinline__ PolishResult<real, KS> lmpc_polish(const PolishArgs<r
           riccati_solve_lean_dpp<1>(L, MS, lane, pf);
       } else {
         if (k == 0 && has_sigma)
-          riccati_solve<2>(L, lane, pf);
+          riccati_solve<2, false, CHAINA>(L, lane, pf);
         else
-          riccati_solve<1>(L, lane, pf);
+          riccati_solve<1, false, CHAINA>(L, lane, pf);
       }
       real dz0[KQ], dz1[KQ], val[KQ];
       real2 hl[KQ];
@@ -1650,6 +1736,13 @@ __device__ __forceinline__ PolishResult<real, KS> lmpc_polish(const PolishArgs<r
 #pragma unroll
     for (int q = 0; q < KS; ++q) res.lm[q] = sx.lm[q];
   }
+#ifdef LMPC_PHASE_TIMING
+  PT_MARK(0)
+  res.prof[0] = pf.acc[3];
+  res.prof[1] = pf.acc[8] + pf.acc[9];
+  res.prof[2] = pf.acc[10] + pf.acc[11];
+  res.prof[3] = pf.acc[0];
+#endif
   return res;
 }
 
@@ -2014,6 +2107,15 @@ __device__ __forceinline__ void lmpc_solve_problem(
     else
       pr = lmpc_polish<real, KQ, KS, io, SECOND>(pa);
     pol_rounds = uni(pr.pol_rounds);
+#ifdef LMPC_PHASE_TIMING
+    if constexpr (KS == 0) {  // (the learning kernels use buckets 13 .. 15 for their terminal block)
+      pf.acc[13] += pr.prof[0];
+      pf.acc[14] += pr.prof[1];
+      pf.acc[15] += pr.prof[2];
+      pf.acc[18] += pr.prof[3];
+      pf.acc[19] += 1;
+    }
+#endif
     // what the interior point recomputes before it reads it again (predictor products -- multiplied by zero in the next
     // predictor pass --, the explicit-point bookkeeping, the Schur scalars) does not live across the polish
 #pragma unroll
@@ -2079,10 +2181,12 @@ __device__ __forceinline__ void lmpc_solve_problem(
       if (lane < 36) TT[TL_PT + lane] = (lane % 7 == 0) ? TT[TL_E + lane / 7] : treal(0);
     }
     wave_sync();
+    PT_MARK(1)
     if constexpr (LEAN)
       riccati_factor_lean<(KS > 0), false>(L, MS, lane, TT + TL_PT);
     else
-      riccati_factor<(KS > 0), false>(L, lane, TT + TL_PT);
+      riccati_factor<(KS > 0), false, false, CHAINA>(L, lane, TT + TL_PT);
+    PT_MARK(16)
     if constexpr (WARM_BUILT) {
       if (attempt == 0) {
         // the plan in the solver's variables into the rhs0 cells: z_i = [x_i; u_{i-1}] (knot 0: the measured state and the applied
@@ -2106,7 +2210,7 @@ __device__ __forceinline__ void lmpc_solve_problem(
         if constexpr (LEAN)
           feedback_rollout_lean<true>(L, MS, lane);
         else
-          feedback_rollout<true>(L, lane);
+          feedback_rollout<true, CHAINA>(L, lane);
         // the plan's boundary slack, then its working set (the interior point's row state is what the polish classifies by:
         // a held row gets lam = 1 > t = 0, every other row lam = 0 <= t = its slack)
         real vw[KQ];
@@ -2188,7 +2292,8 @@ __device__ __forceinline__ void lmpc_solve_problem(
     if constexpr (LEAN)
       feedback_rollout_lean(L, MS, lane);
     else
-      feedback_rollout(L, lane);
+      feedback_rollout<false, CHAINA>(L, lane);
+    PT_MARK(17)
   }
   if constexpr (KS > 0) {
     treal ul[6] = {0, 0, 0, 0, 0, 0};
@@ -2974,6 +3079,7 @@ __device__ __forceinline__ void lmpc_solve_problem(
       asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
       kkt_out[18 * (size_t)B + b] = (io)hwid;
       kkt_out[19 * (size_t)B + b] = (io)(xcc & 0xf);
+      for (int k = 16; k < 20; ++k) kkt_out[(k + 4) * (size_t)B + b] = (io)pf.acc[k];
     }
 #else
     if (kkt_out) {

@@ -182,6 +182,11 @@ __host__ __device__ constexpr bool lmpc_fuse_bwd(int real_bytes, int kq, int ks)
 // `own ? cell : junk` selects become strides of 0.  Same cells, same values, same order: only how an address is formed changes.
 // On for the fp64 tracking classes of N <= 23 (KQ <= 4, KS = 0: the one-wave cold, warm and second-pass instances), whose two waves
 // per SIMD share the VALU with the chain's integer work; off elsewhere (not measured there).  profiles/chain_addresses.md.
+// What takes it there: the iteration's factorisation and vector solves; the active-set polish's (lmpc_polish: the plain JOSEPH
+// factorisation and riccati_solve<2 | 1>); the start point's factorisation and feedback_rollout, which under the policy has the forward
+// sweep's form (profiles/polish_chains.md: +1.6 % on the headline, every output bit equal).  NOT taken: the polish's first backward sweep
+// fused into its factorisation -- bit equal as well, but the FUSE + JOSEPH body inside the polish's call frame costs 284 B of scratch
+// per lane (672 -> 956 B in the headline kernel) and the headline 17 % (same document, section 8).
 __host__ __device__ constexpr bool lmpc_chain_addr(int real_bytes, int kq, int ks) { return real_bytes == 8 && kq <= 4 && ks == 0; }
 
 #endif

@@ -7,13 +7,16 @@
 #define LMPC_WAVE_HIP_H_
 
 // Optional per-phase cycle accounting (make prof -> -DLMPC_PHASE_TIMING): one s_memtime read per
-// phase boundary, per-wave totals written over kkt_out as [16][B] doubles (caller allocates 20 rows).
+// phase boundary, per-wave totals written over kkt_out as [16][B] doubles, four words of bookkeeping behind them and buckets 16 .. 19
+// behind those (the caller allocates 24 rows).  Buckets 13 .. 15, 18 and 19 of a KS = 0 kernel are the active-set polish's own clocks
+// (factorisation, backward sweeps, forward sweeps, row work with the save-area traffic, calls), which the callee hands back in its
+// result and which are ALSO inside the caller's bucket 7; 16 and 17 are the start point's factorisation and rollout.
 #ifdef LMPC_PHASE_TIMING
 struct Prof {
-  long long acc[16];
+  long long acc[20];
   long long t, w0;
 };
-#define PT_DECL Prof pf; { for (int k = 0; k < 16; ++k) pf.acc[k] = 0; pf.t = __builtin_readcyclecounter(); pf.w0 = wall_clock64(); }
+#define PT_DECL Prof pf; { for (int k = 0; k < 20; ++k) pf.acc[k] = 0; pf.t = __builtin_readcyclecounter(); pf.w0 = wall_clock64(); }
 #define PT_MARK(k) { const long long pt_n = __builtin_readcyclecounter(); pf.acc[k] += pt_n - pf.t; pf.t = pt_n; }
 #else
 struct Prof {};

@@ -37,7 +37,7 @@ if "w1" in sys.argv:
 if "w2" in sys.argv:
     solver.set_waves_per_problem(2)   # (round 6: the two-wave kernels; the clock is the chain wave's)
 out = solver.alloc_outputs(B)
-out["kkt"] = torch.zeros((20, B), dtype=torch.float64, device="cuda")
+out["kkt"] = torch.zeros((24, B), dtype=torch.float64, device="cuda")
 for _ in range(3):
     solver.solve(inp, out, mixed=MIXED, **kw)
 torch.cuda.synchronize()
@@ -45,10 +45,19 @@ k = out["kkt"].cpu().numpy()
 it = out["iters"].cpu().numpy()
 names = ["load", "init(factor+rollout)", "rows+reduce(+terminal block)", "factor", "riccati_solve (all)", "(ModelStream::wait, inside the sweeps)", "schur+steps", "update/exit",
          "  bwd sweep nrhs1", "  bwd sweep nrhs2", "  fwd sweep nrhs1", "  fwd sweep nrhs2", "gradient", "x13", "x14", "x15"]
-tot = k[:16].sum(0)
+tot = k[:13].sum(0) if not LMPC else k[:16].sum(0)   # (KS = 0: buckets 13 .. 15 are the polish's own clocks, already inside update/exit)
 print("mean iters %.2f; mean cycles/wave %.0f" % (it.mean(), tot.mean()))
 for n, v in zip(names, k[:16]):
     print("%-22s %10.0f cycles  %5.1f %%   per-iter %8.0f" % (n, v.mean(), 100 * v.mean() / tot.mean(), v.mean() / it.mean()))
+
+# the start point's two chains and the polish's own clocks (KS = 0 kernels; the polish's are also inside update/exit)
+ex = {"start factorisation": k[20], "start rollout": k[21], "polish factor": k[13], "polish bwd sweeps": k[14], "polish fwd sweeps": k[15],
+      "polish rows + save area": k[22], "polish calls": k[23]}
+tot = tot + k[20] + k[21]
+print("with the start point's chains: mean cycles/wave %.0f" % tot.mean())
+for n, v in ex.items():
+    print("%-26s %10.1f   %5.2f %%" % (n, v.mean(), 100 * v.mean() / tot.mean()))
+print("polish rounds per solve (iters - counted interior-point iterations are not separable here): calls %.3f" % k[23].mean())
 
 w0, w1, hw, xcc = k[16], k[17], k[18].astype(np.int64), k[19].astype(np.int64)
 span = (w1.max() - w0.min()) / 100e6
