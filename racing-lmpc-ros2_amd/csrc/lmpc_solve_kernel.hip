@@ -30,9 +30,10 @@
 // predictor-corrector interior point; Newton systems by Riccati recursion on (z, v = dU); the
 // shared boundary slack sigma (one scalar coupling all knots) by a Schur complement.
 //
-// This file: the Riccati sweeps of both layouts, the active-set polish, lmpc_solve_problem, the kernels and the lists of what each
-// translation unit instantiates.  What they are written in -- layout and policies, wave primitives, limits, the safe-set terminal
-// block -- is in the four headers included below (DESIGN.md section 4 has the file map); lmpc_solve_w2.hip.h holds the two-wave kernel.
+// This file: the stage chains (Riccati factorisation and feedback rollout: one body each for the indexed, pinned and lean form; the
+// vector solve: still a fat and a lean function behind one call), the lean model stream, the active-set polish, lmpc_solve_problem,
+// the kernels and the lists of what each translation unit instantiates.  What they are written in -- layouts, policies and the
+// description of the chain forms, wave primitives, limits, the safe-set terminal block -- is in the four headers included below (DESIGN.md section 4 has the file map); lmpc_solve_w2.hip.h holds the two-wave kernel.
 #include <hip/hip_runtime.h>
 
 #include <type_traits>
@@ -40,31 +41,20 @@
 
 #include "lmpc_device.h"
 
-#include "lmpc_solve_layout.hip.h"   // LDS layout, Lds / SimplexRows, per-instantiation policies
+#include "lmpc_solve_layout.hip.h"   // LDS layouts, Lds / SimplexRows, per-instantiation policies, the forms of a stage chain
 #include "lmpc_wave.hip.h"           // fences, broadcasts, reductions, scheduling pins
 #include "lmpc_limits.hip.h"         // ipm_limits, polish_limits
 #include "lmpc_terminal.hip.h"       // safe-set terminal block
 
-// ---- the LEAN layout (fp64, N > 40) -----------------------------------------------------------------------------------
-// At long horizons the stage records are what limits residency: 78 doubles per stage, 48 of them the stage model [A B],
-// which the iteration only reads.  The lean layout keeps the model OUT of the records: every sweep streams it from the
-// linearisation workspace (L2 / MALL resident, written by lmpc_linearize_kernel just before) through two chunk buffers of
-// LN_CHUNK stages each, filled by asynchronous global -> LDS copies (global_load_lds_dwordx4: no registers, no ds_write)
-// one chunk ahead of the sweep.  A stage record shrinks to what the factorisation produces:
-//     K_j[c] @ 2 c + j (c < 8) | Hinv (h00, h01) @16, h11 @18 | dt @19 | kff rhs0 [2] @20 | kff rhs1 [2] @22        (24)
-// and a chunk slot holds the workspace record as it is: ABt[8][6] (row c of it = column c of [A B]: the rows the backward
-// sweeps read are contiguous 48-byte runs on distinct banks, the columns the forward sweep reads are stride-6) | g [6].
-// N = 60: 57 KB -> 38 KB per problem, 2 -> 4 resident problems per CU (the register file allows no more); N = 80: 2 -> 3.
-#define LN_CHUNK LMPC_LEAN_CHUNK  // (lmpc_device.h: the host sizes the two chunk buffers with the same constants)
-#define LN_REC LMPC_LIN_RECORD
-#define LN_HI 16
-#define LN_HI11 18
-#define LN_DT 19
-#define LN_KFF(s) ((s) ? 22 : 20)
-// Which kernels take it: lmpc_lean (lmpc_solve_layout.hip.h), the fp64 kernels from LMPC_LEAN_MIN_KQ = 11 slots per lane on.
+// (the lean layout and its LN_* offsets: lmpc_solve_layout.hip.h)
+#include "lmpc_solve_setup.hip.h"    // the load phase of both layouts
 
-#include "lmpc_solve_setup.hip.h"    // the load phase of both layouts (needs LN_DT above)
-
+// The lean layout's stage model on its way from the linearisation workspace to the two chunk buffers in LDS.
+// Streaming discipline of a sweep that walks the stages downwards (factor, backward vector sweep): the chunk it starts in
+// is fetched and waited for, the one below it is fetched at once; the stage that reads ahead into the next chunk waits for
+// it first and, the chunk just left being dead by then, fetches the one after into its buffer.  Upwards (forward sweep,
+// rollout) the mirror image.  One fetch is in flight at a time; a chunk is 8 stages of work ahead of its first use.
+// In the chain bodies these steps stand under `if constexpr (SC::lean)`.
 template <typename real>
 struct ModelStream {
   const real* ws;  // this problem's [N - 1][LN_REC] in the workspace (HBM / L2)
@@ -130,6 +120,16 @@ __device__ __forceinline__ real qz_entry(const real* ct, bool terminal, int r, i
   return (r < 6 || c < 6) ? ((r == c) ? dx : 0.0) : uu;
 }
 
+// ======== the stage chains: factorisation, vector solve, rollout ========
+// The factorisation and the LDS-exchange rollout are ONE body each for the three forms an instantiation can take (ChainForm,
+// lmpc_solve_layout.hip.h: indexed fat records, fat records on pinned LDS addresses, lean records with the model streamed).  The body
+// states the stage arithmetic once; `SC` (StageCells<FORM>) says where the cells of a stage are; CHAIN_GET / CHAIN_PUT reach a cell as
+// record(i) + offset or, under CHAIN_PINNED, through an LDS byte address that is set up, pinned and advanced in three blocks under
+// `SC::pinned` -- the same cells in the same order --; what the lean form adds (when the chunks of the model are fetched and waited
+// for) stands under `SC::lean`.  Every call site passes the form of its instantiation, lmpc_chain_form(LEAN, lmpc_chain_addr(..)).
+// The bodies are held to the device code of the separate functions they replace (scratch/isa_diff.py): they avoid lambdas and helper
+// functions around their arrays and around control flow on the stage index, which change what the optimiser emits.
+
 // Backward Riccati sweep for the barrier weights currently in the knots' rhs0 region
 // (Thz @ +10..17, Thv @ +18,19, boundary weight @ KN_EY).  Leaves K (columns 6,7 of M) and Hinv in
 // the stage records.
@@ -155,15 +155,16 @@ __device__ __forceinline__ real qz_entry(const real* ct, bool terminal, int r, i
 // predictor's gradient first (it depends on the iterate only) into the rhs0 cells, and the barrier weights the factor reads move
 // to the rhs1 cells (`th_off` = KN_R1, the boundary row's weight to `tey_off` = KN_TEY) -- the Schur vector that used to sit there
 // is one number per knot (c_sigma on e_y: KN_CSIG), generated on the fly.  The arithmetic of either recursion is the unfused one's,
-// operation for operation.  riccati_solve<2, true> then runs the forward half only.
+// operation for operation.  riccati_solve<.., 2, true> then runs the forward half only.
 #define KN_TEY 35  // (the knot record's spare cell)
-// CHAIN_ADDR (lmpc_chain_addr, lmpc_solve_layout.hip.h): what the loop reads and writes in the stage and knot records -- the cells that
+// CHAIN_PINNED (lmpc_chain_addr, lmpc_solve_layout.hip.h): what the loop reads and writes in the stage and knot records -- the cells that
 // move from stage to stage; P, W, Y in the tail stay where they are -- goes through LDS byte addresses, one per lane pattern, each
 // advanced once per stage, every access at a compile-time offset from one of them: the same cells in the same order.
-template <bool HAS_PT, bool JOSEPH, bool FUSE = false, bool CHAIN_ADDR = false, typename real, typename ptreal>
-__device__ __forceinline__ void riccati_factor(const Lds<real>& L, int lane, const ptreal* PT, const int th_off = KN_R0, const int tey_off = KN_EY) {
+template <ChainForm FORM, bool HAS_PT, bool JOSEPH, bool FUSE = false, typename real, typename ptreal>
+__device__ __forceinline__ void riccati_factor(const Lds<real>& L, ModelStream<real>& MS, int lane, const ptreal* PT, const int th_off = KN_R0, const int tey_off = KN_EY) {
+  typedef StageCells<FORM> SC;
   FRESH_LANE(lane);
-  CHAIN_PRIO_ENTER();
+  if constexpr (SC::prio) CHAIN_PRIO_ENTER();
   const int N = L.N, r = lane >> 3, c = lane & 7;
   real* T = L.tail();
   real* MP = T + TL_P;
@@ -177,6 +178,11 @@ __device__ __forceinline__ void riccati_factor(const Lds<real>& L, int lane, con
   const real qmid = qz_entry(ct, false, r, c);
   real pown;
   {
+    int ch = 0;
+    if constexpr (SC::lean) {  // (the chunk the sweep starts in is requested ...)
+      ch = (N - 2) / LN_CHUNK;
+      MS.ensure(ch);
+    }
     const real* kn = L.kn(N - 1);
     real e = qz_entry(ct, true, r, c);
     const real th = kn[th_off + r] + (r == 1 ? kn[tey_off] : real(0));
@@ -185,6 +191,10 @@ __device__ __forceinline__ void riccati_factor(const Lds<real>& L, int lane, con
     if (HAS_PT && r < 6 && c < 6) e += real(PT[r <= c ? r * 6 + c : c * 6 + r]);
     pown = e;
     MP[MROWS(r) + c] = e;
+    if constexpr (SC::lean) {  // (... and there; the one below it is requested at once)
+      MS.wait();
+      if (ch > 0) MS.ensure(ch - 1);
+    }
   }
   // fused backward sweep: lane (s, c), s = parity of the DPP row; rhs0 = the knots' rhs0 cells, rhs1 = c_sigma e_y (knots >= 1)
   const int fs = (lane >> 4) & 1;
@@ -204,17 +214,17 @@ __device__ __forceinline__ void riccati_factor(const Lds<real>& L, int lane, con
   real* const p_dst1 = upper ? MP + MROWS(c) + r : MW + MROWS(r) + c;
   // where this lane's share of the stage results goes: lanes 0..15 K_j[c] (j = r), 16..18 Hinv, the
   // rest to their own (dead) W cell
-  const int res_off = lane < 16 ? ST_ROW(c) + 6 + r : (lane == 18 ? ST_HI11 : ST_HI + (lane - 16));
+  const int res_off = lane < 16 ? SC::krow(c) + SC::kidx + r : (lane == 18 ? SC::hi11 : SC::hi + (lane - 16));
   const bool res_on = lane < 19;
   real* const res_junk = MW + MROWS(r) + c;
   // phase-1/2 operands of stage N-2 (later stages: fetched during phase 3 of the stage before)
   real ar[6], ac[6];
   {
-    const real* st = L.st(N - 2);
+    const real* ab = SC::model(L, MS, N - 2);
 #pragma unroll
     for (int k = 0; k < 6; ++k) {
-      ar[k] = st[ST_ROW(r) + k];
-      ac[k] = st[ST_ROW(c) + k];
+      ar[k] = ab[SC::row(r) + k];
+      ac[k] = ab[SC::row(c) + k];
     }
   }
   // the input-rate weights are the same at every stage: scalar registers, not an LDS read per stage
@@ -227,12 +237,12 @@ __device__ __forceinline__ void riccati_factor(const Lds<real>& L, int lane, con
     pown = MP[MROWS(r) + c];
     ISSUE_ORDER();
   }
-  // CHAIN_ADDR: wave-uniform cells of the stage and of the knot, the knot's weight by row, the sweep's q_z, the rows r and c of the
+  // CHAIN_PINNED: wave-uniform cells of the stage and of the knot, the knot's weight by row, the sweep's q_z, the rows r and c of the
   // stage fetched ahead (stride 0 once it is stage 0), and the two store targets (a dead cell: stride 0)
   unsigned a_stu = 0, a_knu = 0, a_thr = 0, a_foq = 0, a_nr = 0, a_nc = 0, a_res = 0, a_kff = 0, s_res = 0, s_kff = 0;
   constexpr unsigned ca_kb = LMPC_KNOT_STRIDE * sizeof(real);
   const unsigned ca_sb = L.stride * sizeof(real);
-  if constexpr (CHAIN_ADDR) {
+  if constexpr (SC::pinned) {
     const int in = N > 2 ? N - 3 : 0;
     a_stu = lds_addr(L.st(N - 2));
     a_knu = lds_addr(L.kn(N - 2));
@@ -248,7 +258,9 @@ __device__ __forceinline__ void riccati_factor(const Lds<real>& L, int lane, con
   for (int i = N - 2; i >= 0; --i) {
     real* st = L.st(i);
     const real* kn = L.kn(i);
-    if constexpr (CHAIN_ADDR) {
+    const real* ab = SC::model(L, MS, i);
+    const bool cross = SC::lean && (i % LN_CHUNK) == 0 && i > 0;  // the read-ahead of this stage is the first read of the chunk below
+    if constexpr (SC::pinned) {
       CHAIN_ADDR_PIN16(a_stu); CHAIN_ADDR_PIN16(a_knu); CHAIN_ADDR_PIN(a_thr); CHAIN_ADDR_PIN16(a_nr); CHAIN_ADDR_PIN16(a_nc); CHAIN_ADDR_PIN(a_res);
       if constexpr (FUSE) { CHAIN_ADDR_PIN(a_foq); CHAIN_ADDR_PIN(a_kff); }
     }
@@ -260,22 +272,11 @@ __device__ __forceinline__ void riccati_factor(const Lds<real>& L, int lane, con
       ISSUE_ORDER();
     }
     // phase-3 operands of this stage, queued behind the P row
-    real t, thr, ey, thv0, thv1;
-    if constexpr (CHAIN_ADDR) {
-      const LMPC_LDS real* const knu = lds_at<real>(a_knu);
-      t = lds_at<real>(a_stu)[ST_DT], thr = *lds_at<real>(a_thr), ey = knu[tey_off], thv0 = knu[th_off + 8], thv1 = knu[th_off + 9];
-      if constexpr (FUSE) {
-        fqz = *lds_at<real>(a_foq);
-        fqv0 = knu[KN_R0 + 8];
-        fqv1 = knu[KN_R0 + 9];
-      }
-    } else {
-      t = st[ST_DT], thr = kn[th_off + r], ey = kn[tey_off], thv0 = kn[th_off + 8], thv1 = kn[th_off + 9];
-      if constexpr (FUSE) {
-        fqz = kn[f_oq];
-        fqv0 = kn[KN_R0 + 8];
-        fqv1 = kn[KN_R0 + 9];
-      }
+    const real t = CHAIN_GET(a_stu, st, 0, SC::dt), thr = CHAIN_GET(a_thr, kn, th_off + r, 0), ey = CHAIN_GET(a_knu, kn, 0, tey_off), thv0 = CHAIN_GET(a_knu, kn, 0, th_off + 8), thv1 = CHAIN_GET(a_knu, kn, 0, th_off + 9);
+    if constexpr (FUSE) {
+      fqz = CHAIN_GET(a_foq, kn, f_oq, 0);
+      fqv0 = CHAIN_GET(a_knu, kn, 0, KN_R0 + 8);
+      fqv1 = CHAIN_GET(a_knu, kn, 0, KN_R0 + 9);
     }
     ISSUE_ORDER();
     real w = m_r6 * pown;
@@ -305,20 +306,18 @@ __device__ __forceinline__ void riccati_factor(const Lds<real>& L, int lane, con
     const real y6r = MY[MROWS(6) + r], y7r = MY[MROWS(7) + r];
     const real y6c = MY[MROWS(6) + c], y7c = MY[MROWS(7) + c];
     AFTER_VALUE(y);
-    if constexpr (!JOSEPH) {  // phase-1/2 operands of the next stage (their registers are dead by now), queued behind the Y rows
-      if constexpr (CHAIN_ADDR) {
+    // phase-1/2 operands of the next stage (their registers are dead by now), queued behind the Y rows
+    if constexpr (!JOSEPH) {
+      if constexpr (SC::lean) if (cross) MS.wait();
+      const real* abn = SC::pinned ? nullptr : SC::model(L, MS, i > 0 ? i - 1 : 0);  // (pinned: the addresses are there already)
 #pragma unroll
-        for (int k = 0; k < 6; ++k) {
-          ar[k] = lds_at<real>(a_nr)[k];
-          ac[k] = lds_at<real>(a_nc)[k];
-        }
-      } else {
-        const real* stn = L.st(i > 0 ? i - 1 : 0);
-#pragma unroll
-        for (int k = 0; k < 6; ++k) {
-          ar[k] = stn[ST_ROW(r) + k];
-          ac[k] = stn[ST_ROW(c) + k];
-        }
+      for (int k = 0; k < 6; ++k) {
+        ar[k] = CHAIN_GET(a_nr, abn, SC::row(r), k);
+        ac[k] = CHAIN_GET(a_nc, abn, SC::row(c), k);
+      }
+      if constexpr (SC::lean) if (cross && i / LN_CHUNK >= 2) {  // (the chunk just left is dead: the one after into its buffer)
+        wave_fence();
+        MS.fetch(i / LN_CHUNK - 2);
       }
     }
     ISSUE_ORDER();
@@ -351,13 +350,8 @@ __device__ __forceinline__ void riccati_factor(const Lds<real>& L, int lane, con
         real b0[6], b1[6];
 #pragma unroll
         for (int k = 0; k < 6; ++k) {
-          if constexpr (CHAIN_ADDR) {
-            b0[k] = lds_at<real>(a_stu)[ST_ROW(6) + k];
-            b1[k] = lds_at<real>(a_stu)[ST_ROW(7) + k];
-          } else {
-            b0[k] = st[ST_ROW(6) + k];
-            b1[k] = st[ST_ROW(7) + k];
-          }
+          b0[k] = CHAIN_GET(a_stu, ab, 0, SC::row(6) + k);
+          b1[k] = CHAIN_GET(a_stu, ab, 0, SC::row(7) + k);
         }
 #pragma unroll
         for (int k = 0; k < 6; ++k) {
@@ -388,19 +382,18 @@ __device__ __forceinline__ void riccati_factor(const Lds<real>& L, int lane, con
         for (int k = 0; k < 6; ++k) y2 += w2r[k] * ac[k];
         y2 += w2r[6] * fc6 + w2r[7] * fc7;
       }
-      if constexpr (CHAIN_ADDR) {  // operands of the next stage
-#pragma unroll
+      {
+        if constexpr (SC::lean) if (cross) MS.wait();
+        const real* abn = SC::pinned ? nullptr : SC::model(L, MS, i > 0 ? i - 1 : 0);  // (pinned: the addresses are there already)
+  #pragma unroll
         for (int k = 0; k < 6; ++k) {
-          ar[k] = lds_at<real>(a_nr)[k];
-          ac[k] = lds_at<real>(a_nc)[k];
+          ar[k] = CHAIN_GET(a_nr, abn, SC::row(r), k);
+          ac[k] = CHAIN_GET(a_nc, abn, SC::row(c), k);
         }
-      } else {
-        const real* stn = L.st(i > 0 ? i - 1 : 0);
-#pragma unroll
-        for (int k = 0; k < 6; ++k) {
-          ar[k] = stn[ST_ROW(r) + k];
-          ac[k] = stn[ST_ROW(c) + k];
-        }
+        if constexpr (SC::lean) if (cross && i / LN_CHUNK >= 2) {  // (the chunk just left is dead: the one after into its buffer)
+        wave_fence();
+        MS.fetch(i / LN_CHUNK - 2);
+      }
       }
       const real v00 = sv00 + thv0, v11 = sv11 + thv1;
       pn = qmid + y2 + k0r * (v00 * k0c + sv01 * k1c) + k1r * (sv01 * k0c + v11 * k1c);
@@ -412,10 +405,7 @@ __device__ __forceinline__ void riccati_factor(const Lds<real>& L, int lane, con
     *p_dst0 = pn;  // (not used after stage 0)
     *p_dst1 = pn;
     const real res = lane < 8 ? k0c : (lane < 16 ? k1c : (lane == 16 ? hi00 : (lane == 17 ? hi01 : hi11)));
-    if constexpr (CHAIN_ADDR)
-      *lds_at<real>(a_res) = res;
-    else
-      *(res_on ? st + res_off : res_junk) = res;
+    CHAIN_PUT(a_res, res_on ? st + res_off : res_junk, res);
     wave_sync();
     if constexpr (FUSE) {
       if (i > 0) {  // the next stage's P row, behind the stores above
@@ -431,19 +421,25 @@ __device__ __forceinline__ void riccati_factor(const Lds<real>& L, int lane, con
       fp = f_mq * fqz + fws - (k0c * hv0 + k1c * hv1);
       const real ha = c == 0 ? hi00 : hi01, hb = c == 0 ? hi01 : hi11;
       const real kff = ha * hv0 + hb * hv1;
-      if constexpr (CHAIN_ADDR)
-        *lds_at<real>(a_kff) = kff;
-      else
-        *(f_own ? st + ST_KFF(fs) + c : res_junk) = kff;
+      CHAIN_PUT(a_kff, f_own ? st + SC::kff(fs) + c : res_junk, kff);
     }
-    if constexpr (CHAIN_ADDR) {
+    if constexpr (SC::pinned) {
       const unsigned s_nxt = i >= 2 ? ca_sb : 0u;  // (the fetch ahead stops at stage 0)
       a_stu -= ca_sb; a_knu -= ca_kb; a_thr -= ca_kb; a_res -= s_res; a_nr -= s_nxt; a_nc -= s_nxt;
       if constexpr (FUSE) { a_foq -= ca_kb; a_kff -= s_kff; }
     }
   }
-  if constexpr (FUSE) wave_sync();
-  CHAIN_PRIO_LEAVE();
+  if constexpr (FUSE)
+    wave_sync();  // (what follows is the forward half of the solve: lean, chunks 0 and 1 are what the factor ended on)
+  else if constexpr (SC::lean) {
+    if ((N - 2) / LN_CHUNK >= 2) {
+      // what follows is a vector solve, whose backward sweep starts at the top again: its first chunks are on their way while
+      // the gradient is assembled (both buffers are free: the factor is done with them)
+      MS.fetch((N - 2) / LN_CHUNK);
+      MS.fetch((N - 2) / LN_CHUNK - 1);
+    }
+  }
+  if constexpr (SC::prio) CHAIN_PRIO_LEAVE();
 }
 
 // Riccati vector solve for NRHS (1 or 2) right-hand sides held in the knots' rhs regions
@@ -459,7 +455,7 @@ __device__ __forceinline__ void riccati_factor(const Lds<real>& L, int lane, con
 // CHAIN_ADDR (lmpc_chain_addr, lmpc_solve_layout.hip.h): the stage loops walk LDS byte addresses, one per lane pattern, each advanced
 // once per stage, and every access of a stage is a compile-time offset from one of them -- the same cells in the same order.
 template <int NRHS, bool FWD_ONLY = false, bool CHAIN_ADDR = false, typename real>  // (FWD_ONLY: the backward half ran inside the factorisation, riccati_factor<.., FUSE>)
-__device__ __forceinline__ void riccati_solve(const Lds<real>& L, int lane, Prof& pf) {
+__device__ __forceinline__ void riccati_solve_fat(const Lds<real>& L, int lane, Prof& pf) {
   FRESH_LANE(lane);
   CHAIN_PRIO_ENTER();
   const int N = L.N;
@@ -627,362 +623,12 @@ __device__ __forceinline__ void riccati_solve(const Lds<real>& L, int lane, Prof
   PT_MARK(10 + NRHS - 1)
 }
 
-// Closed-loop rollout z_{i+1} = Abar z_i + Bbar v_i + gbar, v_i = -K_i z_i (absolute variables).
-// The linearised model can be open-loop unstable (|eig A| > 1 at low speed with dt = 25 ms), so
-// the start trajectory is generated under the stabilising Riccati feedback.  Same lane roles as the
-// forward sweep of riccati_solve.
-// WARM (lmpc_solve_batch_warm): the rollout TRACKS a plan -- v_i = v_i^plan - K_i (z_i - z_i^plan) -- whose knots sit in the rhs0
-// cells of the knot records ([z^plan (8) | v^plan (2)] at KN_R0: free between the factorisation that has read its weights
-// there and the first gradient): the plan made dynamically exact about this linearisation, a few 1e-3 from where it was.
-// CHAIN_ADDR (lmpc_chain_addr, lmpc_solve_layout.hip.h): the forward sweep's form.  Component r of z_i stays in one register per lane and
-// reaches the other lanes by row_newbcast; M(r, :), g, dt -- and the plan's knot of a WARM rollout -- of stage i + 1 are fetched during
-// stage i through addresses that advance once per stage (stride 0 once the fetch ahead has reached the last stage); z_{i+1} and v_i are
-// stored off the chain (a dead cell: stride 0), so nothing a stage reads was written by the loop and the one wave_sync() is at the end.
-// The arithmetic is the loop's below, operation for operation.
-template <bool WARM = false, bool CHAIN_ADDR = false, typename real>
-__device__ __forceinline__ void feedback_rollout(const Lds<real>& L, int lane) {
-  FRESH_LANE(lane);
-  const int N = L.N, r = lane & 7;
-  const bool own = lane < 8;
-  real* T = L.tail();
-  real* const junk0 = T + TL_W + lane;
-  real* const junk1 = T + TL_W + 80 + lane;
-  if constexpr (CHAIN_ADDR) {
-    const unsigned sb = L.stride * sizeof(real);
-    constexpr unsigned kb = LMPC_KNOT_STRIDE * sizeof(real);
-    const int o_g = ST_G + (r < 6 ? r : 0);
-    real d = L.kn(0)[r];  // component r of z_i
-    real col[8], t, g;    // M(r, :), dt and g of the stage: fetched one stage ahead
-    real pl[8], pv = 0.0; // WARM: the plan's knot, z^plan (wave-uniform) and this lane's v^plan
-    {
-      const real* st = L.st(0);
-#pragma unroll
-      for (int k = 0; k < 8; ++k) col[k] = st[ST_ROW(k) + r];
-      t = st[ST_DT];
-      g = st[o_g];
-      if constexpr (WARM) {
-        const real* kn = L.kn(0);
-#pragma unroll
-        for (int k = 0; k < 8; ++k) pl[k] = kn[KN_R0 + k];
-        pv = kn[KN_R0 + 8 + (r & 1)];
-      }
-    }
-    const int in = N > 2 ? 1 : 0;
-    unsigned a_nxt = lds_addr(L.st(in) + r);                                 // column-indexed: M(r, :) of the stage fetched ahead
-    unsigned a_ng = lds_addr(L.st(in) + o_g);                                // ... its g
-    unsigned a_uni = lds_addr(L.st(in));                                     // ... and, wave-uniform, its dt
-    unsigned a_pl = lds_addr(L.kn(in) + KN_R0);                              // WARM: the plan's knot of that stage (wave-uniform)
-    unsigned a_pv = lds_addr(L.kn(in) + KN_R0 + 8 + (r & 1));
-    unsigned a_z = lds_addr(own ? L.kn(1) + r : junk0);                      // store targets (a dead cell: stride 0)
-    unsigned a_v = lds_addr((own && r >= 6) ? L.kn(0) + 2 + r : junk1);
-    const unsigned s_z = own ? kb : 0u, s_v = (own && r >= 6) ? kb : 0u;
-    for (int i = 0; i < N - 1; ++i) {
-      CHAIN_ADDR_PIN(a_nxt); CHAIN_ADDR_PIN(a_ng); CHAIN_ADDR_PIN(a_uni); CHAIN_ADDR_PIN(a_z); CHAIN_ADDR_PIN(a_v);
-      if constexpr (WARM) { CHAIN_ADDR_PIN16(a_pl); CHAIN_ADDR_PIN(a_pv); }
-      const LMPC_LDS real* const p_nxt = lds_at<real>(a_nxt);
-      real dz[8];
-      row_bcast8(d, dz);
-      real acc = 0.0;
-#pragma unroll
-      for (int k = 0; k < 6; ++k) acc = rfma(col[k], dz[k], acc);
-      const real ax = acc;
-      acc = rfma(col[6], dz[6], acc);
-      acc = rfma(col[7], dz[7], acc);
-      real v = -acc;
-      if constexpr (WARM) {  // (lanes 6, 7: col = a row of K)  v = v^plan + K z^plan - K z
-        real kz = pv;
-#pragma unroll
-        for (int k = 0; k < 8; ++k) kz = rfma(col[k], pl[k], kz);
-        v += kz;
-      }
-      const real u = rfma(t, v, d);  // (lanes 6, 7: their own component of z is u_{i-1})
-      real u0, u1;
-      row_bcast67(u, u0, u1);
-      const real b0 = col[6], b1 = col[7], gi = g;
-#pragma unroll
-      for (int k = 0; k < 8; ++k) col[k] = p_nxt[ST_ROW(k)];
-      t = lds_at<real>(a_uni)[ST_DT];
-      g = *lds_at<real>(a_ng);
-      if constexpr (WARM) {
-#pragma unroll
-        for (int k = 0; k < 8; ++k) pl[k] = lds_at<real>(a_pl)[k];
-        pv = *lds_at<real>(a_pv);
-      }
-      const real nx = gi + rfma(b1, u1, rfma(b0, u0, ax));
-      d = (r < 6) ? nx : u;
-      *lds_at<real>(a_z) = d;
-      *lds_at<real>(a_v) = v;
-      const unsigned s_nxt = i < N - 3 ? sb : 0u;  // (the fetch ahead stops at the last stage)
-      a_nxt += s_nxt; a_ng += s_nxt; a_uni += s_nxt; a_z += s_z; a_v += s_v;
-      if constexpr (WARM) {
-        const unsigned s_pl = i < N - 3 ? kb : 0u;
-        a_pl += s_pl; a_pv += s_pl;
-      }
-    }
-    wave_sync();
-  } else
-  for (int i = 0; i < N - 1; ++i) {
-    const real* st = L.st(i);
-    real* kn = L.kn(i);
-    real dz[8], col[8];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) dz[k] = kn[k];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) col[k] = st[ST_ROW(k) + r];
-    const real t = st[ST_DT];
-    const real g = st[ST_G + (r < 6 ? r : 0)];
-    real acc = 0.0;
-#pragma unroll
-    for (int k = 0; k < 6; ++k) acc = rfma(col[k], dz[k], acc);
-    const real ax = acc;
-    acc = rfma(col[6], dz[6], acc);
-    acc = rfma(col[7], dz[7], acc);
-    real v = -acc;
-    if constexpr (WARM) {  // (lanes 6, 7: col = a row of K)  v = v^plan + K z^plan - K z
-      real kz = kn[KN_R0 + 8 + (r & 1)];
-#pragma unroll
-      for (int k = 0; k < 8; ++k) kz = rfma(col[k], kn[KN_R0 + k], kz);
-      v += kz;
-    }
-    const real u = rfma(t, v, (r == 6) ? dz[6] : dz[7]);
-    const real u0 = lane_bcast(u, 6), u1 = lane_bcast(u, 7);
-    const real nx = g + rfma(col[7], u1, rfma(col[6], u0, ax));
-    *(own ? kn + LMPC_KNOT_STRIDE + r : junk0) = (r < 6) ? nx : u;
-    *((own && r >= 6) ? kn + 2 + r : junk1) = v;
-    wave_sync();
-  }
-}
-
-// ---- the sweeps of the lean layout: the same arithmetic, stage by stage, with the stage model read from the chunk slots
-// ---- of a ModelStream and K / Hinv / kff in the 24-cell records -------------------------------------------------------
-// Streaming discipline of a sweep that walks the stages downwards (factor, backward vector sweep): the chunk it starts in
-// is fetched and waited for, the one below it is fetched at once; the stage that reads ahead into the next chunk waits for
-// it first and, the chunk just left being dead by then, fetches the one after into its buffer.  Upwards (forward sweep,
-// rollout) the mirror image.  One fetch is in flight at a time; a chunk is 8 stages of work ahead of its first use.
-template <bool HAS_PT, bool JOSEPH, bool FUSE = false, typename real, typename ptreal>
-__device__ __forceinline__ void riccati_factor_lean(const Lds<real>& L, ModelStream<real>& M, int lane, const ptreal* PT, const int th_off = KN_R0,
-                                                    const int tey_off = KN_EY) {
-  FRESH_LANE(lane);
-  const int N = L.N, r = lane >> 3, c = lane & 7;
-  real* T = L.tail();
-  real* MP = T + TL_P;
-  real* MW = T + TL_W;
-  real* MY = T + TL_Y;
-  const real* ct = T + TL_CT;
-  const bool diag = r == c;
-  const real m_diag = diag ? real(1) : real(0), m_r1 = r == 1 ? real(1) : real(0);
-  const real m_r6 = r >= 6 ? real(1) : real(0), m_c6 = c >= 6 ? real(1) : real(0);
-  const real qmid = qz_entry(ct, false, r, c);
-  real pown;
-  {
-    const int ch = (N - 2) / LN_CHUNK;
-    M.ensure(ch);
-    const real* kn = L.kn(N - 1);
-    real e = qz_entry(ct, true, r, c);
-    const real th = kn[th_off + r] + (r == 1 ? kn[tey_off] : real(0));
-    if (diag) e += th;
-    if (HAS_PT && r < 6 && c < 6) e += real(PT[r <= c ? r * 6 + c : c * 6 + r]);
-    pown = e;
-    MP[MROWS(r) + c] = e;
-    M.wait();
-    if (ch > 0) M.ensure(ch - 1);
-  }
-  // fused backward sweep of the predictor's right-hand sides (see riccati_factor)
-  const int fs = (lane >> 4) & 1;
-  const bool f_own = FUSE && (lane & 8) == 0 && lane < 32 && c < 2;
-  const int f_oq = fs == 0 ? KN_R0 + c : KN_CSIG;
-  const real f_mq = (fs == 0 || c == 1) ? real(1) : real(0);
-  const real f_m6 = (c >= 6) ? real(1) : real(0);
-  real fp = 0.0, fws = 0.0, fw6 = 0.0, fw7 = 0.0, fqz = 0.0, fqv0 = 0.0, fqv1 = 0.0;
-  if constexpr (FUSE) fp = f_mq * L.kn(N - 1)[f_oq];
-  const bool upper = r <= c;
-  real* const p_dst0 = upper ? MP + MROWS(r) + c : MW + MROWS(r) + c;
-  real* const p_dst1 = upper ? MP + MROWS(c) + r : MW + MROWS(r) + c;
-  const int res_off = lane < 16 ? 2 * c + r : (lane == 18 ? LN_HI11 : LN_HI + (lane - 16));
-  const bool res_on = lane < 19;
-  real* const res_junk = MW + MROWS(r) + c;
-  real ar[6], ac[6];
-  {
-    const real* ab = M.stage(N - 2);
-#pragma unroll
-    for (int k = 0; k < 6; ++k) {
-      ar[k] = ab[6 * r + k];
-      ac[k] = ab[6 * c + k];
-    }
-  }
-  const real sv00 = uni(ct[CT_SV + 0]), sv01 = uni(ct[CT_SV + 1]), sv11 = uni(ct[CT_SV + 3]);
-  wave_sync();
-  real pr[6];
-  if constexpr (FUSE) {
-#pragma unroll
-    for (int k = 0; k < 6; ++k) pr[k] = MP[MROWS(c) + k];
-    pown = MP[MROWS(r) + c];
-    ISSUE_ORDER();
-  }
-  for (int i = N - 2; i >= 0; --i) {
-    real* st = L.st(i);
-    const real* kn = L.kn(i);
-    const real* ab = M.stage(i);
-    const bool cross = (i % LN_CHUNK) == 0 && i > 0;  // the read-ahead of this stage is the first read of the chunk below
-    if constexpr (!FUSE) {
-#pragma unroll
-      for (int k = 0; k < 6; ++k) pr[k] = MP[MROWS(c) + k];
-      pown = MP[MROWS(r) + c];
-      ISSUE_ORDER();
-    }
-    const real t = st[LN_DT], thr = kn[th_off + r], ey = kn[tey_off], thv0 = kn[th_off + 8], thv1 = kn[th_off + 9];
-    if constexpr (FUSE) {
-      fqz = kn[f_oq];
-      fqv0 = kn[KN_R0 + 8];
-      fqv1 = kn[KN_R0 + 9];
-    }
-    ISSUE_ORDER();
-    real w = m_r6 * pown;
-#pragma unroll
-    for (int k = 0; k < 6; ++k) w += ar[k] * pr[k];
-    MW[MROWS(r) + c] = w;
-    wave_sync();
-    real wr[6];
-#pragma unroll
-    for (int k = 0; k < 6; ++k) wr[k] = MW[MROWS(r) + k];
-    if constexpr (FUSE) {
-      ISSUE_ORDER();
-      real pb[6];
-      row_bcast6(fp, pb);
-      fws = f_m6 * fp;
-#pragma unroll
-      for (int k = 0; k < 6; ++k) fws = rfma(ac[k], pb[k], fws);
-      row_bcast67(fws, fw6, fw7);
-    }
-    real y = m_c6 * w;
-#pragma unroll
-    for (int k = 0; k < 6; ++k) y += wr[k] * ac[k];
-    MY[MROWS(r) + c] = y;
-    wave_sync();
-    const real y6r = MY[MROWS(6) + r], y7r = MY[MROWS(7) + r];
-    const real y6c = MY[MROWS(6) + c], y7c = MY[MROWS(7) + c];
-    AFTER_VALUE(y);
-    if constexpr (!JOSEPH) {
-      if (cross) M.wait();
-      const real* abn = M.stage(i > 0 ? i - 1 : 0);
-#pragma unroll
-      for (int k = 0; k < 6; ++k) {
-        ar[k] = abn[6 * r + k];
-        ac[k] = abn[6 * c + k];
-      }
-      if (cross && i / LN_CHUNK >= 2) {
-        wave_fence();
-        M.fetch(i / LN_CHUNK - 2);
-      }
-    }
-    ISSUE_ORDER();
-    const real y66 = lane_bcast(y, 54), y67 = lane_bcast(y, 55), y77 = lane_bcast(y, 63);
-    const real tt = t * t;
-    const real h00 = sv00 + thv0 + tt * y66;
-    const real h01 = sv01 + tt * y67;
-    const real h11 = sv11 + thv1 + tt * y77;
-    const real idet = frcp(h00 * h11 - h01 * h01);
-    const real hi00 = h11 * idet, hi01 = -h01 * idet, hi11 = h00 * idet;
-    const real g0 = t * y6c, g1 = t * y7c;
-    const real k0c = hi00 * g0 + hi01 * g1;
-    const real k1c = hi01 * g0 + hi11 * g1;
-    real pn;
-    if constexpr (JOSEPH) {
-      const real g0r = t * y6r, g1r = t * y7r;
-      const real k0r = hi00 * g0r + hi01 * g1r;
-      const real k1r = hi01 * g0r + hi11 * g1r;
-      {
-        real b0[6], b1[6];
-#pragma unroll
-        for (int k = 0; k < 6; ++k) {
-          b0[k] = ab[36 + k];
-          b1[k] = ab[42 + k];
-        }
-#pragma unroll
-        for (int k = 0; k < 6; ++k) {
-          ar[k] -= t * (b0[k] * k0r + b1[k] * k1r);
-          ac[k] -= t * (b0[k] * k0c + b1[k] * k1c);
-        }
-      }
-      const real fr6 = (r == 6 ? real(1) : real(0)) - t * k0r, fr7 = (r == 7 ? real(1) : real(0)) - t * k1r;
-      const real fc6 = (c == 6 ? real(1) : real(0)) - t * k0c, fc7 = (c == 7 ? real(1) : real(0)) - t * k1c;
-      real w2 = 0.0;
-      {
-        real pc[8];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) pc[k] = MP[MROWS(c) + k];
-#pragma unroll
-        for (int k = 0; k < 6; ++k) w2 += ar[k] * pc[k];
-        w2 += fr6 * pc[6] + fr7 * pc[7];
-      }
-      MW[MROWS(r) + c] = w2;
-      wave_sync();
-      real y2 = 0.0;
-      {
-        real w2r[8];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) w2r[k] = MW[MROWS(r) + k];
-#pragma unroll
-        for (int k = 0; k < 6; ++k) y2 += w2r[k] * ac[k];
-        y2 += w2r[6] * fc6 + w2r[7] * fc7;
-      }
-      {
-        if (cross) M.wait();
-        const real* abn = M.stage(i > 0 ? i - 1 : 0);
-#pragma unroll
-        for (int k = 0; k < 6; ++k) {
-          ar[k] = abn[6 * r + k];
-          ac[k] = abn[6 * c + k];
-        }
-        if (cross && i / LN_CHUNK >= 2) {
-          wave_fence();
-          M.fetch(i / LN_CHUNK - 2);
-        }
-      }
-      const real v00 = sv00 + thv0, v11 = sv11 + thv1;
-      pn = qmid + y2 + k0r * (v00 * k0c + sv01 * k1c) + k1r * (sv01 * k0c + v11 * k1c);
-    } else {
-      pn = qmid + y - t * (y6r * k0c + y7r * k1c);
-    }
-    const real th = rfma(m_r1, ey, thr);
-    pn = rfma(m_diag, th, pn);
-    *p_dst0 = pn;
-    *p_dst1 = pn;
-    const real res = lane < 8 ? k0c : (lane < 16 ? k1c : (lane == 16 ? hi00 : (lane == 17 ? hi01 : hi11)));
-    *(res_on ? st + res_off : res_junk) = res;
-    wave_sync();
-    if constexpr (FUSE) {
-      if (i > 0) {
-#pragma unroll
-        for (int k = 0; k < 6; ++k) pr[k] = MP[MROWS(c) + k];
-        pown = MP[MROWS(r) + c];
-      }
-      ISSUE_ORDER();
-      const real qv0 = fs == 0 ? fqv0 : real(0), qv1 = fs == 0 ? fqv1 : real(0);
-      const real hv0 = rfma(t, fw6, qv0);
-      const real hv1 = rfma(t, fw7, qv1);
-      fp = f_mq * fqz + fws - (k0c * hv0 + k1c * hv1);
-      const real ha = c == 0 ? hi00 : hi01, hb = c == 0 ? hi01 : hi11;
-      const real kff = ha * hv0 + hb * hv1;
-      *(f_own ? st + LN_KFF(fs) + c : res_junk) = kff;
-    }
-  }
-  if constexpr (FUSE) {
-    wave_sync();  // (what follows is the forward half of the solve: chunks 0 and 1 are what the factor ended on)
-  } else if ((N - 2) / LN_CHUNK >= 2) {
-    // what follows is a vector solve, whose backward sweep starts at the top again: its first chunks are on their way while
-    // the gradient is assembled (both buffers are free: the factor is done with them)
-    M.fetch((N - 2) / LN_CHUNK);
-    M.fetch((N - 2) / LN_CHUNK - 1);
-  }
-}
-
-// The lean vector solve with the running vector in registers (DPP row broadcasts, as riccati_solve) instead of one LDS round
+// The lean vector solve with the running vector in registers (DPP row broadcasts, as riccati_solve_fat) instead of one LDS round
 // trip per stage: at one wave per SIMD a sweep stage costs what its instruction count costs (~4.5 cycles each, nothing to
 // overlap with), and the exchange through LDS was a third of the lean stage's instructions (the LDS-exchange form of rounds 2-3,
 // bit for bit the same results, is scratch/r5/experiment_switches.patch); lane (s, r) = ((lane >> 4) % NRHS, lane & 7), lanes 8..15 of a row mirror 0..7.
 template <int NRHS, bool FWD_ONLY = false, typename real>
-__device__ __forceinline__ void riccati_solve_lean_dpp(const Lds<real>& L, ModelStream<real>& M, int lane, Prof& pf) {
+__device__ __forceinline__ void riccati_solve_lean(const Lds<real>& L, ModelStream<real>& M, int lane, Prof& pf) {
   FRESH_LANE(lane);
   const int N = L.N;
   const int r = lane & 7, s = (lane >> 4) & (NRHS - 1);
@@ -1091,52 +737,161 @@ __device__ __forceinline__ void riccati_solve_lean_dpp(const Lds<real>& L, Model
   PT_MARK(10 + NRHS - 1)
 }
 
-template <bool WARM = false, typename real>
-__device__ __forceinline__ void feedback_rollout_lean(const Lds<real>& L, ModelStream<real>& M, int lane) {
+// The vector solve in the form of the instantiation.  NOT one body yet, unlike the factorisation and the rollout: merged with the
+// accessors of lmpc_solve_layout.hip.h the indexed form compiles to the separate function's code, but the pinned and the lean form do
+// not (the lean forward sweep's fetch of a stage is a lambda that captures its arrays, the fat one's is written out, and the optimiser
+// treats the two differently), so the two functions above stay as they were and this only picks one.
+template <ChainForm FORM, int NRHS, bool FWD_ONLY = false, typename real>
+__device__ __forceinline__ void riccati_solve(const Lds<real>& L, ModelStream<real>& MS, int lane, Prof& pf) {
+  if constexpr (FORM == CHAIN_LEAN)
+    riccati_solve_lean<NRHS, FWD_ONLY>(L, MS, lane, pf);
+  else
+    riccati_solve_fat<NRHS, FWD_ONLY, FORM == CHAIN_PINNED>(L, lane, pf);
+}
+
+// Closed-loop rollout z_{i+1} = Abar z_i + Bbar v_i + gbar, v_i = -K_i z_i (absolute variables).
+// The linearised model can be open-loop unstable (|eig A| > 1 at low speed with dt = 25 ms), so
+// the start trajectory is generated under the stabilising Riccati feedback.  Same lane roles as the
+// forward sweep of riccati_solve.
+// WARM (lmpc_solve_batch_warm): the rollout TRACKS a plan -- v_i = v_i^plan - K_i (z_i - z_i^plan) -- whose knots sit in the rhs0
+// cells of the knot records ([z^plan (8) | v^plan (2)] at KN_R0: free between the factorisation that has read its weights
+// there and the first gradient): the plan made dynamically exact about this linearisation, a few 1e-3 from where it was.
+// Two algorithms.  CHAIN_INDEXED and CHAIN_LEAN share the LDS-exchange loop at the bottom: z_i is read back from the knot record
+// every stage, one wave_sync() per stage.  CHAIN_PINNED is a body of its own, the forward sweep's form: component r of z_i stays in
+// one register per lane and reaches the other lanes by row_newbcast; M(r, :), g, dt -- and the plan's knot of a WARM rollout -- of
+// stage i + 1 are fetched during stage i through addresses that advance once per stage (stride 0 once the fetch ahead has reached
+// the last stage); z_{i+1} and v_i are stored off the chain (a dead cell: stride 0), so nothing a stage reads was written by the
+// loop and the one wave_sync() is at the end.  The arithmetic is the loop's below, operation for operation.
+template <ChainForm FORM, bool WARM = false, typename real>
+__device__ __forceinline__ void feedback_rollout(const Lds<real>& L, ModelStream<real>& MS, int lane) {
+  typedef StageCells<FORM> SC;
   FRESH_LANE(lane);
   const int N = L.N, r = lane & 7;
   const bool own = lane < 8;
   real* T = L.tail();
   real* const junk0 = T + TL_W + lane;
   real* const junk1 = T + TL_W + 80 + lane;
-  const int nch = (N - 2) / LN_CHUNK + 1;
-  const int cb = r < 6 ? r : 0;
-  M.ensure(0);
-  M.wait();
-  if (nch > 1) M.ensure(1);
-  for (int i = 0; i < N - 1; ++i) {
-    const real* st = L.st(i);
-    const real* ab = M.stage(i);
-    real* kn = L.kn(i);
-    real dz[8], col[8];
+  if constexpr (SC::pinned) {
+    const unsigned sb = L.stride * sizeof(real);
+    constexpr unsigned kb = LMPC_KNOT_STRIDE * sizeof(real);
+    const int o_g = ST_G + (r < 6 ? r : 0);
+    real d = L.kn(0)[r];  // component r of z_i
+    real col[8], t, g;    // M(r, :), dt and g of the stage: fetched one stage ahead
+    real pl[8], pv = 0.0; // WARM: the plan's knot, z^plan (wave-uniform) and this lane's v^plan
+    {
+      const real* st = L.st(0);
 #pragma unroll
-    for (int k = 0; k < 8; ++k) dz[k] = kn[k];
+      for (int k = 0; k < 8; ++k) col[k] = st[ST_ROW(k) + r];
+      t = st[ST_DT];
+      g = st[o_g];
+      if constexpr (WARM) {
+        const real* kn = L.kn(0);
 #pragma unroll
-    for (int k = 0; k < 8; ++k) col[k] = r < 6 ? ab[6 * k + cb] : st[2 * k + (r - 6)];
-    const real t = st[LN_DT];
-    const real g = ab[48 + cb];
-    real acc = 0.0;
-#pragma unroll
-    for (int k = 0; k < 6; ++k) acc = rfma(col[k], dz[k], acc);
-    const real ax = acc;
-    acc = rfma(col[6], dz[6], acc);
-    acc = rfma(col[7], dz[7], acc);
-    real v = -acc;
-    if constexpr (WARM) {  // (lanes 6, 7: col = a row of K)  v = v^plan + K z^plan - K z
-      real kz = kn[KN_R0 + 8 + (r & 1)];
-#pragma unroll
-      for (int k = 0; k < 8; ++k) kz = rfma(col[k], kn[KN_R0 + k], kz);
-      v += kz;
+        for (int k = 0; k < 8; ++k) pl[k] = kn[KN_R0 + k];
+        pv = kn[KN_R0 + 8 + (r & 1)];
+      }
     }
-    const real u = rfma(t, v, (r == 6) ? dz[6] : dz[7]);
-    const real u0 = lane_bcast(u, 6), u1 = lane_bcast(u, 7);
-    const real nx = g + rfma(col[7], u1, rfma(col[6], u0, ax));
-    *(own ? kn + LMPC_KNOT_STRIDE + r : junk0) = (r < 6) ? nx : u;
-    *((own && r >= 6) ? kn + 2 + r : junk1) = v;
+    const int in = N > 2 ? 1 : 0;
+    unsigned a_nxt = lds_addr(L.st(in) + r);                                 // column-indexed: M(r, :) of the stage fetched ahead
+    unsigned a_ng = lds_addr(L.st(in) + o_g);                                // ... its g
+    unsigned a_uni = lds_addr(L.st(in));                                     // ... and, wave-uniform, its dt
+    unsigned a_pl = lds_addr(L.kn(in) + KN_R0);                              // WARM: the plan's knot of that stage (wave-uniform)
+    unsigned a_pv = lds_addr(L.kn(in) + KN_R0 + 8 + (r & 1));
+    unsigned a_z = lds_addr(own ? L.kn(1) + r : junk0);                      // store targets (a dead cell: stride 0)
+    unsigned a_v = lds_addr((own && r >= 6) ? L.kn(0) + 2 + r : junk1);
+    const unsigned s_z = own ? kb : 0u, s_v = (own && r >= 6) ? kb : 0u;
+    for (int i = 0; i < N - 1; ++i) {
+      CHAIN_ADDR_PIN(a_nxt); CHAIN_ADDR_PIN(a_ng); CHAIN_ADDR_PIN(a_uni); CHAIN_ADDR_PIN(a_z); CHAIN_ADDR_PIN(a_v);
+      if constexpr (WARM) { CHAIN_ADDR_PIN16(a_pl); CHAIN_ADDR_PIN(a_pv); }
+      const LMPC_LDS real* const p_nxt = lds_at<real>(a_nxt);
+      real dz[8];
+      row_bcast8(d, dz);
+      real acc = 0.0;
+#pragma unroll
+      for (int k = 0; k < 6; ++k) acc = rfma(col[k], dz[k], acc);
+      const real ax = acc;
+      acc = rfma(col[6], dz[6], acc);
+      acc = rfma(col[7], dz[7], acc);
+      real v = -acc;
+      if constexpr (WARM) {  // (lanes 6, 7: col = a row of K)  v = v^plan + K z^plan - K z
+        real kz = pv;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) kz = rfma(col[k], pl[k], kz);
+        v += kz;
+      }
+      const real u = rfma(t, v, d);  // (lanes 6, 7: their own component of z is u_{i-1})
+      real u0, u1;
+      row_bcast67(u, u0, u1);
+      const real b0 = col[6], b1 = col[7], gi = g;
+#pragma unroll
+      for (int k = 0; k < 8; ++k) col[k] = p_nxt[ST_ROW(k)];
+      t = lds_at<real>(a_uni)[ST_DT];
+      g = *lds_at<real>(a_ng);
+      if constexpr (WARM) {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) pl[k] = lds_at<real>(a_pl)[k];
+        pv = *lds_at<real>(a_pv);
+      }
+      const real nx = gi + rfma(b1, u1, rfma(b0, u0, ax));
+      d = (r < 6) ? nx : u;
+      *lds_at<real>(a_z) = d;
+      *lds_at<real>(a_v) = v;
+      const unsigned s_nxt = i < N - 3 ? sb : 0u;  // (the fetch ahead stops at the last stage)
+      a_nxt += s_nxt; a_ng += s_nxt; a_uni += s_nxt; a_z += s_z; a_v += s_v;
+      if constexpr (WARM) {
+        const unsigned s_pl = i < N - 3 ? kb : 0u;
+        a_pl += s_pl; a_pv += s_pl;
+      }
+    }
     wave_sync();
-    if ((i % LN_CHUNK) == LN_CHUNK - 1 && i < N - 2) {  // the next stage is the first of the chunk above
-      M.wait();
-      if (i / LN_CHUNK + 2 < nch) M.fetch(i / LN_CHUNK + 2);
+  } else {
+    int nch = 0, cb = 0;
+    if constexpr (SC::lean) {
+      nch = (N - 2) / LN_CHUNK + 1;  // chunks of the model
+      cb = r < 6 ? r : 0;
+      MS.ensure(0);
+      MS.wait();
+      if (nch > 1) MS.ensure(1);
+    }
+    for (int i = 0; i < N - 1; ++i) {
+      const real* st = L.st(i);
+      const real* ab = SC::model(L, MS, i);
+      real* kn = L.kn(i);
+      real dz[8], col[8];
+#pragma unroll
+      for (int k = 0; k < 8; ++k) dz[k] = kn[k];
+      if constexpr (SC::lean) {  // (lanes r < 6: their row of [A B], stride 6 in the model record; lanes 6, 7: their row of K, stride 2 in the stage record)
+#pragma unroll
+        for (int k = 0; k < 8; ++k) col[k] = r < 6 ? ab[6 * k + cb] : st[2 * k + (r - 6)];
+      } else {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) col[k] = st[SC::row(k) + r];
+      }
+      const real t = st[SC::dt];
+      const real g = ab[SC::g + (SC::lean ? cb : (r < 6 ? r : 0))];
+      real acc = 0.0;
+#pragma unroll
+      for (int k = 0; k < 6; ++k) acc = rfma(col[k], dz[k], acc);
+      const real ax = acc;
+      acc = rfma(col[6], dz[6], acc);
+      acc = rfma(col[7], dz[7], acc);
+      real v = -acc;
+      if constexpr (WARM) {  // (lanes 6, 7: col = a row of K)  v = v^plan + K z^plan - K z
+        real kz = kn[KN_R0 + 8 + (r & 1)];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) kz = rfma(col[k], kn[KN_R0 + k], kz);
+        v += kz;
+      }
+      const real u = rfma(t, v, (r == 6) ? dz[6] : dz[7]);
+      const real u0 = lane_bcast(u, 6), u1 = lane_bcast(u, 7);
+      const real nx = g + rfma(col[7], u1, rfma(col[6], u0, ax));
+      *(own ? kn + LMPC_KNOT_STRIDE + r : junk0) = (r < 6) ? nx : u;
+      *((own && r >= 6) ? kn + 2 + r : junk1) = v;
+      wave_sync();
+      if constexpr (SC::lean) if ((i % LN_CHUNK) == LN_CHUNK - 1 && i < N - 2) {  // the next stage is the first of the chunk above
+        MS.wait();
+        if (i / LN_CHUNK + 2 < nch) MS.fetch(i / LN_CHUNK + 2);
+      }
     }
   }
 }
@@ -1152,7 +907,7 @@ __device__ __forceinline__ void feedback_rollout_lean(const Lds<real>& L, ModelS
 // (its accesses stay DS instructions).  Slacks and multipliers of the interior point are not touched; the iterate is put
 // aside in the handle's save area and comes back unless the attempt is accepted.  Wave-uniform values arrive in vector
 // registers (the calling convention has no scalar arguments) and go back to scalar registers first thing.
-// Every instantiation runs the DPP form of the vector solves (riccati_solve, riccati_solve_lean_dpp) since round 4: bit for bit the
+// Every instantiation runs the DPP form of the vector solves (riccati_solve_fat, riccati_solve_lean) since round 4: bit for bit the
 // LDS-exchange forms of rounds 2-3, -3 % at N = 40 tracking / IAC, -8 % at N = 60, -4 % at N = 80, -4 / -12 % for the learning
 // problem at N = 60 / 80.  (Rounds 2-3 kept DPP out of the one-wave-per-SIMD kernels after a non-reproducible KQ = 14 / KS = 3
 // build; with the polish behind a call that family has been bit-stable in every build since.  The LDS-exchange functions and
@@ -1190,7 +945,7 @@ __device__ __forceinline__ PolishResult<real, KS> lmpc_polish(const PolishArgs<r
   const int lane = threadIdx.x;
   const int N = uni(a.N), NS = N - 1;
   constexpr bool LEAN = lmpc_lean(sizeof(real), KQ);
-  constexpr bool CHAINA = lmpc_chain_addr(sizeof(real), KQ, KS);  // the stage chains on explicit LDS addresses, as in the iteration
+  constexpr ChainForm FORM = lmpc_chain_form(LEAN, lmpc_chain_addr(sizeof(real), KQ, KS));  // of the stage chains, as in the iteration
   Lds<real> L{lds, N, LEAN ? LMPC_LEAN_STAGE_STRIDE : LMPC_STAGE_STRIDE, !SECOND && lmpc_waves_per_simd(sizeof(real), KQ, KS) >= 2};
   real* const T = L.tail();
   treal* const TT = reinterpret_cast<treal*>(T + LMPC_TAIL_DOUBLES);
@@ -1415,10 +1170,7 @@ __device__ __forceinline__ PolishResult<real, KS> lmpc_polish(const PolishArgs<r
     ++pol_rounds;
     wave_sync();
     PT_MARK(0)
-    if constexpr (LEAN)
-      riccati_factor_lean<(KS > 0), true>(L, MS, lane, TT + TL_PT);
-    else
-      riccati_factor<(KS > 0), true, false, CHAINA>(L, lane, TT + TL_PT);
+    riccati_factor<FORM, (KS > 0), true>(L, MS, lane, TT + TL_PT);
     PT_MARK(3)
     bool nan_step = false;
     // ---- pol::steps multiplier steps on that factor, each from the point the one before has reached ----
@@ -1492,17 +1244,10 @@ __device__ __forceinline__ PolishResult<real, KS> lmpc_polish(const PolishArgs<r
       }
       wave_sync();
       PT_MARK(0)
-      if constexpr (LEAN) {
-        if (k == 0 && has_sigma)
-          riccati_solve_lean_dpp<2>(L, MS, lane, pf);
-        else
-          riccati_solve_lean_dpp<1>(L, MS, lane, pf);
-      } else {
-        if (k == 0 && has_sigma)
-          riccati_solve<2, false, CHAINA>(L, lane, pf);
-        else
-          riccati_solve<1, false, CHAINA>(L, lane, pf);
-      }
+      if (k == 0 && has_sigma)
+        riccati_solve<FORM, 2>(L, MS, lane, pf);
+      else
+        riccati_solve<FORM, 1>(L, MS, lane, pf);
       real dz0[KQ], dz1[KQ], val[KQ];
       real2 hl[KQ];
 #pragma unroll
@@ -1787,7 +1532,7 @@ __device__ __forceinline__ void lmpc_solve_problem(
   // (the warm-start kernels too: their cold path is this iteration -- except at two waves per SIMD, where the fused iteration is only
   //  trusted with the polish behind a call, lmpc_fuse_bwd's comment, and the warm kernels keep theirs inline)
   constexpr bool FUSEK = lmpc_fuse_bwd(sizeof(real), KQ, KS) && !(WARMK && lmpc_waves_per_simd(sizeof(real), KQ, KS) >= 2);
-  constexpr bool CHAINA = lmpc_chain_addr(sizeof(real), KQ, KS);  // the stage chains on explicit LDS addresses
+  constexpr ChainForm FORM = lmpc_chain_form(LEAN, lmpc_chain_addr(sizeof(real), KQ, KS));  // of the stage chains (lmpc_solve_layout.hip.h)
   const bool fuse = FUSEK && P.has_sigma != 0;
   Lds<real> L{lds, N, LEAN ? LMPC_LEAN_STAGE_STRIDE : LMPC_STAGE_STRIDE, !SECOND && lmpc_waves_per_simd(sizeof(real), KQ, KS) >= 2};
   if constexpr (SECOND && LMPC_CHAIN_PRIO) __builtin_amdgcn_s_setprio(3);
@@ -2182,10 +1927,7 @@ __device__ __forceinline__ void lmpc_solve_problem(
     }
     wave_sync();
     PT_MARK(1)
-    if constexpr (LEAN)
-      riccati_factor_lean<(KS > 0), false>(L, MS, lane, TT + TL_PT);
-    else
-      riccati_factor<(KS > 0), false, false, CHAINA>(L, lane, TT + TL_PT);
+    riccati_factor<FORM, (KS > 0), false>(L, MS, lane, TT + TL_PT);
     PT_MARK(16)
     if constexpr (WARM_BUILT) {
       if (attempt == 0) {
@@ -2207,10 +1949,7 @@ __device__ __forceinline__ void lmpc_solve_problem(
           L.kn(i)[KN_R0 + o] = val;
         }
         wave_sync();
-        if constexpr (LEAN)
-          feedback_rollout_lean<true>(L, MS, lane);
-        else
-          feedback_rollout<true, CHAINA>(L, lane);
+        feedback_rollout<FORM, true>(L, MS, lane);
         // the plan's boundary slack, then its working set (the interior point's row state is what the polish classifies by:
         // a held row gets lam = 1 > t = 0, every other row lam = 0 <= t = its slack)
         real vw[KQ];
@@ -2289,10 +2028,7 @@ __device__ __forceinline__ void lmpc_solve_problem(
         continue;
       }
     }
-    if constexpr (LEAN)
-      feedback_rollout_lean(L, MS, lane);
-    else
-      feedback_rollout<false, CHAINA>(L, lane);
+    feedback_rollout<FORM>(L, MS, lane);
     PT_MARK(17)
   }
   if constexpr (KS > 0) {
@@ -2633,28 +2369,16 @@ __device__ __forceinline__ void lmpc_solve_problem(
           PT_MARK(4)
         }
       }
-      if constexpr (LEAN) {
-        if (mu <= real(JOSEPH_MU)) {
-          if (FUSEK && fuse)
-            riccati_factor_lean<(KS > 0), true, FUSEK>(L, MS, lane, TT + TL_PT, KN_R1, KN_TEY);
-          else
-            riccati_factor_lean<(KS > 0), true>(L, MS, lane, TT + TL_PT);
-        } else {
-          if (FUSEK && fuse)
-            riccati_factor_lean<(KS > 0), false, FUSEK>(L, MS, lane, TT + TL_PT, KN_R1, KN_TEY);
-          else
-            riccati_factor_lean<(KS > 0), false>(L, MS, lane, TT + TL_PT);
-        }
-      } else if (sizeof(real) == 8 && mu <= real(JOSEPH_MU)) {  // (single precision stops at mu ~ 2e-6)
+      if (sizeof(real) == 8 && mu <= real(JOSEPH_MU)) {  // (single precision stops at mu ~ 2e-6)
         if (FUSEK && fuse)
-          riccati_factor<(KS > 0), (sizeof(real) == 8), FUSEK, CHAINA>(L, lane, TT + TL_PT, KN_R1, KN_TEY);
+          riccati_factor<FORM, (KS > 0), (sizeof(real) == 8), FUSEK>(L, MS, lane, TT + TL_PT, KN_R1, KN_TEY);
         else
-          riccati_factor<(KS > 0), (sizeof(real) == 8), false, CHAINA>(L, lane, TT + TL_PT);
+          riccati_factor<FORM, (KS > 0), (sizeof(real) == 8)>(L, MS, lane, TT + TL_PT);
       } else {
         if (FUSEK && fuse)
-          riccati_factor<(KS > 0), false, FUSEK, CHAINA>(L, lane, TT + TL_PT, KN_R1, KN_TEY);
+          riccati_factor<FORM, (KS > 0), false, FUSEK>(L, MS, lane, TT + TL_PT, KN_R1, KN_TEY);
         else
-          riccati_factor<(KS > 0), false, false, CHAINA>(L, lane, TT + TL_PT);
+          riccati_factor<FORM, (KS > 0), false>(L, MS, lane, TT + TL_PT);
       }
       PT_MARK(3)
     }
@@ -2672,23 +2396,13 @@ __device__ __forceinline__ void lmpc_solve_problem(
         PT_MARK(4)
       }
       // ======== Newton step: predictor together with the Schur vector, then the corrector ========
-      if constexpr (LEAN) {
-        if (pass == 0 && ipm && has_sigma) {
-          if (FUSEK && fuse)
-            riccati_solve_lean_dpp<2, FUSEK>(L, MS, lane, pf);
-          else
-            riccati_solve_lean_dpp<2>(L, MS, lane, pf);
-        } else
-          riccati_solve_lean_dpp<1>(L, MS, lane, pf);
-      } else {
-        if (pass == 0 && ipm && has_sigma) {
-          if (FUSEK && fuse)
-            riccati_solve<2, FUSEK, CHAINA>(L, lane, pf);
-          else
-            riccati_solve<2, false, CHAINA>(L, lane, pf);
-        } else
-          riccati_solve<1, false, CHAINA>(L, lane, pf);
-      }
+      if (pass == 0 && ipm && has_sigma) {
+        if (FUSEK && fuse)
+          riccati_solve<FORM, 2, FUSEK>(L, MS, lane, pf);
+        else
+          riccati_solve<FORM, 2>(L, MS, lane, pf);
+      } else
+        riccati_solve<FORM, 1>(L, MS, lane, pf);
       PT_MARK(5)
       // ======== step of every constrained value; boundary slack by Schur complement ========
       // (QC == KQ: the steps and values are loaded once, here, and stay in registers across the reduction; otherwise chunk-wise,

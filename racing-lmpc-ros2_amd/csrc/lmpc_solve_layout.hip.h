@@ -1,12 +1,15 @@
 // lmpc_solve_layout.hip.h -- what a solve kernel's LDS block looks like and which form of the code each instantiation takes.
-// Holds: the LDS record layout (stage / knot / tail offsets, slot kinds and flags, MROWS), the handles onto it (Lds, SimplexRows),
-// and the per-instantiation constexpr policy functions (waves per SIMD, lean layout, polish call, row chunks, opaque slot tables,
-// fused backward sweep), each with the measurement that decided it.  Needs: lmpc_device.h (record strides) only.
+// Holds: the LDS record layout of both layouts (stage / knot / tail offsets, the lean records, slot kinds and flags, MROWS), the handles
+// onto it (Lds, SimplexRows), the per-instantiation constexpr policy functions (waves per SIMD, lean layout, polish call, row chunks,
+// opaque slot tables, fused backward sweep, chain addresses), each with the measurement that decided it, and the description of the
+// three forms of a stage chain (ChainForm, StageCells, CHAIN_GET / CHAIN_PUT) that the one body per chain in lmpc_solve_kernel.hip is
+// written against.  Needs: lmpc_device.h (record strides) and lmpc_wave.hip.h (LDS addresses, fences).
 // Included by lmpc_solve_kernel.hip, i.e. by all three translation units (lmpc_lib.hip, lmpc_lib_minreg.hip, lmpc_lib_w2.hip).
 #ifndef LMPC_SOLVE_LAYOUT_HIP_H_
 #define LMPC_SOLVE_LAYOUT_HIP_H_
 
 #include "lmpc_device.h"
+#include "lmpc_wave.hip.h"
 
 #define NSLOT 11
 // resident waves per SIMD the register allocation is sized for: the fp64 tracking kernels up to N = 23 and every fp32
@@ -105,15 +108,31 @@ template <typename real>
 struct Lds {
   real* base;
   int N;
-  int stride;  // of a stage record: LMPC_STAGE_STRIDE, or LMPC_LEAN_STAGE_STRIDE in the lean layout (lmpc_solve_kernel.hip)
+  int stride;  // of a stage record: LMPC_STAGE_STRIDE, or LMPC_LEAN_STAGE_STRIDE in the lean layout (below)
   bool chain_prio;  // CHAIN_PRIO around the serial stage chains (a compile-time constant where the sweeps are inlined)
   __device__ __forceinline__ real* st(int i) const { return base + i * stride; }
   __device__ __forceinline__ real* kn(int i) const { return base + (N - 1) * stride + i * LMPC_KNOT_STRIDE; }
   __device__ __forceinline__ real* tail() const { return base + (N - 1) * stride + N * LMPC_KNOT_STRIDE; }
 };
 
-// the lean layout (lmpc_solve_kernel.hip): the fp64 kernels from LMPC_LEAN_MIN_KQ slots per lane on (lmpc_device.h; the host's
-// lmpc_is_lean is the same test)
+// ---- the LEAN layout (fp64, N > 40) -----------------------------------------------------------------------------------
+// At long horizons the stage records are what limits residency: 78 doubles per stage, 48 of them the stage model [A B],
+// which the iteration only reads.  The lean layout keeps the model OUT of the records: every sweep streams it from the
+// linearisation workspace (L2 / MALL resident, written by lmpc_linearize_kernel just before) through two chunk buffers of
+// LN_CHUNK stages each, filled by asynchronous global -> LDS copies (global_load_lds_dwordx4: no registers, no ds_write)
+// one chunk ahead of the sweep (ModelStream, lmpc_solve_kernel.hip).  A stage record shrinks to what the factorisation produces:
+//     K_j[c] @ 2 c + j (c < 8) | Hinv (h00, h01) @16, h11 @18 | dt @19 | kff rhs0 [2] @20 | kff rhs1 [2] @22        (24)
+// and a chunk slot holds the workspace record as it is: ABt[8][6] (row c of it = column c of [A B]: the rows the backward
+// sweeps read are contiguous 48-byte runs on distinct banks, the columns the forward sweep reads are stride-6) | g [6].
+// N = 60: 57 KB -> 38 KB per problem, 2 -> 4 resident problems per CU (the register file allows no more); N = 80: 2 -> 3.
+#define LN_CHUNK LMPC_LEAN_CHUNK  // (lmpc_device.h: the host sizes the two chunk buffers with the same constants)
+#define LN_REC LMPC_LIN_RECORD
+#define LN_HI 16
+#define LN_HI11 18
+#define LN_DT 19
+#define LN_KFF(s) ((s) ? 22 : 20)
+// Which kernels take it: the fp64 kernels from LMPC_LEAN_MIN_KQ = 11 slots per lane on (lmpc_device.h; the host's lmpc_is_lean is
+// the same test)
 constexpr bool lmpc_lean(int real_bytes, int kq) { return real_bytes == 8 && kq >= LMPC_LEAN_MIN_KQ; }
 
 // Where the polish is a call: every fp64 kernel calls it (lmpc_polish_call), the fp32 kernels inline it.  The sweeps take a fresh
@@ -177,7 +196,7 @@ __host__ __device__ constexpr bool lmpc_fuse_bwd(int real_bytes, int kq, int ks)
   return false;                 // fp32 / mixed learning -- measured: -4 %, but 5 instead of 3 of 32768 answers past 1e-3 of the fp64 ones
 }
 
-// The stage chains on explicit LDS byte addresses (CHAIN_ADDR, lmpc_solve_kernel.hip): one address per lane pattern, advanced once
+// The stage chains on explicit LDS byte addresses (the CHAIN_PINNED form below; lmpc_solve_kernel.hip): one address per lane pattern, advanced once
 // per stage, every access of the stage at a compile-time offset from one of them; the clamp of the one-stage-ahead fetch and the
 // `own ? cell : junk` selects become strides of 0.  Same cells, same values, same order: only how an address is formed changes.
 // On for the fp64 tracking classes of N <= 23 (KQ <= 4, KS = 0: the one-wave cold, warm and second-pass instances), whose two waves
@@ -188,5 +207,54 @@ __host__ __device__ constexpr bool lmpc_fuse_bwd(int real_bytes, int kq, int ks)
 // fused into its factorisation -- bit equal as well, but the FUSE + JOSEPH body inside the polish's call frame costs 284 B of scratch
 // per lane (672 -> 956 B in the headline kernel) and the headline 17 % (same document, section 8).
 __host__ __device__ constexpr bool lmpc_chain_addr(int real_bytes, int kq, int ks) { return real_bytes == 8 && kq <= 4 && ks == 0; }
+
+// ---- the three forms of a stage chain ----------------------------------------------------------------------------------------------
+// The Riccati factorisation and the LDS-exchange rollout (lmpc_solve_kernel.hip) each state their stage arithmetic ONCE; the vector
+// solve is one call over a fat and a lean function.  What an instantiation's form decides -- where a stage's operands are and how the
+// cursor moves from stage to stage -- is described here, next to the records it walks:
+//   CHAIN_INDEXED  fat records; every operand is record(i) + offset, formed at its use
+//   CHAIN_PINNED   fat records; lmpc_chain_addr: one LDS byte address per lane pattern, advanced once per stage
+//   CHAIN_LEAN     lean records (lmpc_lean); the stage model comes from the chunk slots of a ModelStream
+// StageCells<FORM> is where the cells are and whether CHAIN_PRIO applies, CHAIN_GET / CHAIN_PUT how a cell is reached.  What the
+// lean form adds to a chain -- when the chunks of the model are fetched and waited for -- stands in the bodies, under SC::lean.
+enum ChainForm { CHAIN_INDEXED, CHAIN_PINNED, CHAIN_LEAN };
+constexpr ChainForm lmpc_chain_form(bool lean, bool chain_addr) { return lean ? CHAIN_LEAN : (chain_addr ? CHAIN_PINNED : CHAIN_INDEXED); }
+
+template <typename real>
+struct ModelStream;  // lmpc_solve_kernel.hip
+template <ChainForm FORM>
+struct StageCells {
+  static constexpr bool pinned = FORM == CHAIN_PINNED, lean = FORM == CHAIN_LEAN;
+  // CHAIN_PRIO_* around the chain: the fat forms (where Lds::chain_prio says so); the lean chains never raise their priority
+  static constexpr bool prio = !lean;
+  // in the stage record L.st(i): dt, H^-1 (h00, h01 | h11), kff of right-hand side s, and K_j[c] at krow(c) + kidx + j
+  static constexpr int dt = lean ? LN_DT : ST_DT, hi = lean ? LN_HI : ST_HI, hi11 = lean ? LN_HI11 : ST_HI11;
+  __device__ static __forceinline__ constexpr int kff(int s) { return lean ? LN_KFF(s) : ST_KFF(s); }
+  __device__ static __forceinline__ constexpr int krow(int c) { return lean ? 2 * c : ST_ROW(c); }
+  static constexpr int kidx = lean ? 0 : 6;
+  // in the model record of the stage (model(): the stage record itself, or the lean chunk slot): column c of [A B] as
+  // six contiguous cells (c = 6, 7: the rows of B'), and g
+  __device__ static __forceinline__ constexpr int row(int c) { return lean ? 6 * c : ST_ROW(c); }
+  template <typename real>
+  __device__ static __forceinline__ const real* model(const Lds<real>& L, const ModelStream<real>& M, int i) {
+    if constexpr (lean) return M.stage(i);
+    else return L.st(i);
+  }
+  static constexpr int g = lean ? 48 : ST_G;
+};
+
+// How a chain reaches a cell (or run of cells) that it visits in every stage.  Every access in a chain body names the cell twice over:
+// as the indexed forms reach it -- record(i) + offset, formed at its use -- and by the LDS byte address `a` that the pinned form keeps
+// for the lane pattern: set to the cell of the first stage, kept a register of its own from stage to stage (CHAIN_ADDR_PIN*,
+// lmpc_wave.hip.h) and advanced once per stage by the record's stride, in the three blocks under SC::pinned that each chain has around
+// its stage.  A store target of lanes that own nothing (a dead cell) and the clamp of the one-stage-ahead fetch are strides of 0 there.
+//   CHAIN_GET(a, rec, o, k)  cell k of the run at offset o of the record: rec[o + k], or pinned lds_at(a)[k] -- a constant k is the DS
+//                            instruction's immediate offset in either form
+//   CHAIN_PUT(a, p, v)       *p = v (p: `own ? cell : dead cell`), or pinned *lds_at(a) = v
+// What a form does not use is never evaluated.  Same cells, same values, same order in either form.  Macros (they expect the body's
+// `SC` and `real`), not functions: a function boundary around an operand changes when the optimiser sees its address arithmetic, and
+// with it the schedule -- the bodies are held to the device code of the separate ones they replace, instruction for instruction.
+#define CHAIN_GET(a, rec, o, k) (SC::pinned ? lds_at<real>(a)[k] : (rec)[(o) + (k)])
+#define CHAIN_PUT(a, p, v) do { if constexpr (SC::pinned) *lds_at<real>(a) = (v); else *(p) = (v); } while (0)
 
 #endif

@@ -1,6 +1,7 @@
 // lmpc_solve_w2.hip.h -- TWO wavefronts per problem on one LDS record: the fp64 tracking kernels for N >= 24 (round 6).
-// (Included by lmpc_solve_kernel.hip behind everything it uses as it is: that file's Riccati factorisation and sweeps, its lean
-//  model stream and the polish's argument structs; the reductions and pins of lmpc_wave.hip.h, the layout and policies of
+// (Included by lmpc_solve_kernel.hip behind everything it uses as it is: that file's stage chains -- riccati_factor, riccati_solve and
+//  feedback_rollout, each ONE call here in the form lmpc_chain_form(LEAN, false) of the instantiation --, its lean model stream and the
+//  polish's argument structs; the reductions and pins of lmpc_wave.hip.h, the layout and policies of
 //  lmpc_solve_layout.hip.h, the limits of lmpc_limits.hip.h.  A translation unit of its own, lmpc_lib_w2.hip: its object compiles
 //  in twenty seconds.)
 //
@@ -98,6 +99,7 @@ __device__ __attribute__((noinline)) PolishResult<double, 0> lmpc_polish_w2(cons
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const int N = uni(a.N), NS = N - 1;
   constexpr bool LEAN = lmpc_lean(8, KQ);
+  constexpr ChainForm FORM = lmpc_chain_form(LEAN, false);  // of the stage chains (lmpc_solve_layout.hip.h); pinned addresses: not taken here
   Lds<real> L{lds, N, LEAN ? LMPC_LEAN_STAGE_STRIDE : LMPC_STAGE_STRIDE, true};
   real* const T = L.tail();
   Wg2 g{T + TL_Y, wv, 0};
@@ -179,12 +181,7 @@ __device__ __attribute__((noinline)) PolishResult<double, 0> lmpc_polish_w2(cons
     }
     hsig = qsig + wg_sum(g, eysum);  // (its barrier also publishes the weights)
     ++pol_rounds;
-    if constexpr (CHAIN) {
-      if constexpr (LEAN)
-        riccati_factor_lean<false, true>(L, MS, lane, (const double*)nullptr);
-      else
-        riccati_factor<false, true>(L, lane, (const double*)nullptr);
-    }
+    if constexpr (CHAIN) riccati_factor<FORM, false, true>(L, MS, lane, (const double*)nullptr);
     wg_sync();
     bool nan_step = false;
     for (int k = 0; k < pol::steps; ++k) {
@@ -223,17 +220,10 @@ __device__ __attribute__((noinline)) PolishResult<double, 0> lmpc_polish_w2(cons
       }
       wg_sync();
       if constexpr (CHAIN) {
-        if constexpr (LEAN) {
-          if (k == 0 && has_sigma)
-            riccati_solve_lean_dpp<2>(L, MS, lane, pf);
-          else
-            riccati_solve_lean_dpp<1>(L, MS, lane, pf);
-        } else {
-          if (k == 0 && has_sigma)
-            riccati_solve<2>(L, lane, pf);
-          else
-            riccati_solve<1>(L, lane, pf);
-        }
+        if (k == 0 && has_sigma)
+          riccati_solve<FORM, 2>(L, MS, lane, pf);
+        else
+          riccati_solve<FORM, 1>(L, MS, lane, pf);
       }
       wg_sync();
       real dz0[KL], dz1[KL], val[KL];
@@ -379,6 +369,7 @@ __device__ __forceinline__ void lmpc_solve_problem_w2(const lmpc_params& P, cons
   const int N = P.N, NS = N - 1;
   const real inf = real(INFINITY), marg = real(P.marg), qsig = real(P.qsig), tol = lim::tol(P.tol);
   constexpr bool LEAN = lmpc_lean(8, KQ);
+  constexpr ChainForm FORM = lmpc_chain_form(LEAN, false);  // of the stage chains (lmpc_solve_layout.hip.h); pinned addresses: not taken here
   Lds<real> L{lds, N, LEAN ? LMPC_LEAN_STAGE_STRIDE : LMPC_STAGE_STRIDE, true};
   real* T = L.tail();
   real* ct = T + TL_CT;
@@ -555,13 +546,8 @@ __device__ __forceinline__ void lmpc_solve_problem_w2(const lmpc_params& P, cons
   }
   wg_sync();
   if constexpr (CHAIN) {
-    if constexpr (LEAN) {
-      riccati_factor_lean<false, false>(L, MS, lane, (const double*)nullptr);
-      feedback_rollout_lean(L, MS, lane);
-    } else {
-      riccati_factor<false, false>(L, lane, (const double*)nullptr);
-      feedback_rollout(L, lane);
-    }
+    riccati_factor<FORM, false, false>(L, MS, lane, (const double*)nullptr);
+    feedback_rollout<FORM>(L, MS, lane);
   }
   wg_sync();
   PT_MARK(1)
@@ -677,28 +663,16 @@ __device__ __forceinline__ void lmpc_solve_problem_w2(const lmpc_params& P, cons
           PT_MARK(12)
         }
         if constexpr (CHAIN) {
-          if constexpr (LEAN) {
-            if (mu <= real(JOSEPH_MU)) {
-              if (fuse)
-                riccati_factor_lean<false, true, true>(L, MS, lane, (const double*)nullptr, KN_R1, KN_TEY);
-              else
-                riccati_factor_lean<false, true>(L, MS, lane, (const double*)nullptr);
-            } else {
-              if (fuse)
-                riccati_factor_lean<false, false, true>(L, MS, lane, (const double*)nullptr, KN_R1, KN_TEY);
-              else
-                riccati_factor_lean<false, false>(L, MS, lane, (const double*)nullptr);
-            }
-          } else if (mu <= real(JOSEPH_MU)) {
+          if (mu <= real(JOSEPH_MU)) {
             if (fuse)
-              riccati_factor<false, true, true>(L, lane, (const double*)nullptr, KN_R1, KN_TEY);
+              riccati_factor<FORM, false, true, true>(L, MS, lane, (const double*)nullptr, KN_R1, KN_TEY);
             else
-              riccati_factor<false, true>(L, lane, (const double*)nullptr);
+              riccati_factor<FORM, false, true>(L, MS, lane, (const double*)nullptr);
           } else {
             if (fuse)
-              riccati_factor<false, false, true>(L, lane, (const double*)nullptr, KN_R1, KN_TEY);
+              riccati_factor<FORM, false, false, true>(L, MS, lane, (const double*)nullptr, KN_R1, KN_TEY);
             else
-              riccati_factor<false, false>(L, lane, (const double*)nullptr);
+              riccati_factor<FORM, false, false>(L, MS, lane, (const double*)nullptr);
           }
         }
         wg_sync();
@@ -716,23 +690,13 @@ __device__ __forceinline__ void lmpc_solve_problem_w2(const lmpc_params& P, cons
         PT_MARK(12)
         // ======== Newton step (wave 0) ========
         if constexpr (CHAIN) {
-          if constexpr (LEAN) {
-            if (pass == 0 && ipm && has_sigma) {
-              if (fuse)
-                riccati_solve_lean_dpp<2, true>(L, MS, lane, pf);
-              else
-                riccati_solve_lean_dpp<2>(L, MS, lane, pf);
-            } else
-              riccati_solve_lean_dpp<1>(L, MS, lane, pf);
-          } else {
-            if (pass == 0 && ipm && has_sigma) {
-              if (fuse)
-                riccati_solve<2, true>(L, lane, pf);
-              else
-                riccati_solve<2>(L, lane, pf);
-            } else
-              riccati_solve<1>(L, lane, pf);
-          }
+          if (pass == 0 && ipm && has_sigma) {
+            if (fuse)
+              riccati_solve<FORM, 2, true>(L, MS, lane, pf);
+            else
+              riccati_solve<FORM, 2>(L, MS, lane, pf);
+          } else
+            riccati_solve<FORM, 1>(L, MS, lane, pf);
         }
         wg_sync();
         PT_MARK(4)

@@ -269,7 +269,7 @@ __device__ __forceinline__ void row_bcast67(real v, real& a, real& b) {  // lane
   b = row_bcast<7>(v);
 }
 
-// LDS byte addresses for the stage chains that walk them (CHAIN_ADDR, lmpc_solve_kernel.hip): the address of a cell of the workgroup's
+// LDS byte addresses for the stage chains that walk them (the CHAIN_PINNED form, lmpc_solve_layout.hip.h): the address of a cell of the workgroup's
 // block as a 32-bit number, a typed LDS pointer back from it (its constant indices become the DS instructions' immediate offsets), and
 // the pin that keeps an address a register of its own from stage to stage -- left to itself the optimiser rewrites the walk as
 // base + index * stride and forms every address again at its use.
