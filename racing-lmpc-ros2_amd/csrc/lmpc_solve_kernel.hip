@@ -897,6 +897,11 @@ __device__ __forceinline__ void feedback_rollout(const Lds<real>& L, ModelStream
 }
 
 // ======== the active-set polish (polish_limits, lmpc_limits.hip.h; the twin's polish() runs the same rounds) ========
+// ONE body on the device, lmpc_polish<real, KQ, KS, io, TEAM>, for every kernel that polishes: the one-wave kernels (fp64, mixed, fp32,
+// warm, second pass, tracking and learning: TEAM = Wave1, below) and the two-wave fp64 tracking kernels (TEAM = Wave2,
+// lmpc_solve_w2.hip.h: KS = 0, real = io = double).  The twin is the only mirror of its rules.  In the profiling build
+// (LMPC_PHASE_TIMING) the two-wave instances now keep the polish's own clocks as well and hand them back in PolishResult::prof; their
+// caller does not add them to its buckets.  LMPC_POLISH_TRACE prints from thread 0 of workgroup 0 under either team.
 // A CALL in the fp64 kernels (lmpc_polish_is_call, lmpc_solve_layout.hip.h), not part of the interior point's body (round 4; until then a lambda inlined into the solve): the polish keeps
 // ~190 B more state per lane alive than an iteration does, and inlined -- even in an outer loop of its own -- it weighed on
 // the register allocation of the iteration: 292 B of scratch per lane in the N = 20 fp64 kernel (824 B in the mixed learning
@@ -935,19 +940,88 @@ struct PolishResult {
 #endif
 };
 
-template <typename real, int KQ, int KS, typename io, bool SECOND = false>  // (SECOND: see lmpc_solve_problem)
+// ---- the team that runs the polish's row phases ----
+// lmpc_polish below is ONE body for one wave per problem and for two (lmpc_solve_w2.hip.h).  A team states what differs between the
+// two, and nothing else -- none of it is arithmetic on a row:
+//   THREADS, tid, lane    who owns the rows: a row loop is `for (e = tid; e < n; e += THREADS)`; lane is the lane within the wave, which
+//                         deals the slots and is what the stage chains are written in
+//   CHAIN                 whether this wave runs the stage chains; after_chain() is what shows the team a chain's results
+//   OPAQUE                whether a slot's table integers are read through an empty asm (table(); lmpc_solve_problem_w2 has the account)
+//   LEAN, FORM, PRIO      the layout, the form of its stage chains and Lds::chain_prio: of the kernel's class (the one-wave KQ), not of
+//                         the slots per lane the polish is instantiated with
+//   attach(tail)          where the team exchanges, once the LDS block is known (the team itself is made first: the lane is read first)
+//   sync()                the exchange of LDS content inside the team (the simplex blocks, one wave's, keep their wave_fence)
+//   published()           behind an exchange that has to have published the LDS writes before it: two waves' exchange had a barrier
+//   and one operation per exchange point of the body, each of them what the body did there before it had a team:
+//   weights_sum(q, x)     q + the team's sum of x (the weights' eysum)
+//   sum3(v)               three sums at once (the Schur step)
+//   step_end(step, nan)   the end of a multiplier step: the largest step, and whether any lane's step was not finite
+//   kkt(..)               the KKT exchange: four votes, the most negative multiplier, the worst row
+//   any_of / min_of / max_of (slot, x)   what step_end and kkt agreed on, read at the point of use by its PolishSlot and with the lane's
+//                         own value: one wave reduces THERE and step_end / kkt do nothing (a DPP reduction is not sunk by the compiler:
+//                         the minimum is taken only after the acceptance test, the maximum only inside it; the ballots are behind the
+//                         short-circuits they were behind), two waves have agreed on all of it in the one exchange and answer from it
+//   mean(x, inv_m)        inv_m * the team's sum of x (the complementarity of an accepted point)
+//   changed(p)            whether p holds on any lane (did a repair change the held set)
+//   sum(x)                the team's sum (LMPC_POLISH_TRACE only)
+// Every result is the same bits in every lane of the team, so the team takes every branch together.
+// The operations pass plain values and return plain values: an aggregate returned or a result written through a reference changed the
+// one-wave kernels' device code (the order of two scalar moves in <double, 4, 0, double>, more in the fp32 kernels), and so did reading
+// the lane after N (scratch/isa_diff.py).
+enum PolishSlot { PS_STEP = 0, PS_NAN = 1, PK_BAD = 0, PK_NEG = 1, PK_WEAK = 2, PK_VIOL = 3, PK_YMIN = 4, PK_WORST = 5 };
+
+template <int REAL_BYTES, int KQ, int KS, bool SECOND>
+struct Wave1 {
+  static constexpr int THREADS = 64;
+  static constexpr bool CHAIN = true, OPAQUE = false;
+  static constexpr bool LEAN = lmpc_lean(REAL_BYTES, KQ);
+  static constexpr ChainForm FORM = lmpc_chain_form(LEAN, lmpc_chain_addr(REAL_BYTES, KQ, KS));  // as in the iteration
+  static constexpr bool PRIO = !SECOND && lmpc_waves_per_simd(REAL_BYTES, KQ, KS) >= 2;
+  const int tid, lane;
+  __device__ __forceinline__ Wave1() : tid(threadIdx.x), lane(threadIdx.x) {}
+  template <typename real>
+  __device__ static __forceinline__ void attach(real*) {}  // (tail of the LDS block: where two waves exchange)
+  __device__ static __forceinline__ int table(int v) { return v; }
+  __device__ static __forceinline__ void sync() { wave_sync(); }
+  __device__ static __forceinline__ void published() { wave_sync(); }
+  __device__ static __forceinline__ void after_chain() {}
+  template <typename real>
+  __device__ static __forceinline__ real weights_sum(real q, real x) { return uni(q + wave_sum(x)); }
+  template <typename real>
+  __device__ static __forceinline__ void sum3(real (&v)[3]) { wave_sum_n<3>(v); }
+  template <typename real>
+  __device__ static __forceinline__ void step_end(real, bool) {}  // (nothing yet: every value is reduced where it is read)
+  template <typename real>
+  __device__ static __forceinline__ void kkt(bool, bool, bool, bool, real, real) {}
+  __device__ static __forceinline__ bool any_of(int, bool p) { return __ballot(p) != 0; }
+  template <typename real>
+  __device__ static __forceinline__ real min_of(int, real x) { return wave_min(x); }
+  template <typename real>
+  __device__ static __forceinline__ real max_of(int, real x) { return wave_max(x); }
+  template <typename real>
+  __device__ static __forceinline__ real mean(real x, real inv_m) { return uni(wave_sum(x) * inv_m); }
+  __device__ static __forceinline__ bool changed(bool p) { return __ballot(p) != 0; }
+  template <typename real>
+  __device__ static __forceinline__ real sum(real x) { return wave_sum(x); }
+};
+
+// KQ: slots per lane (one wave: the class's; two waves: lmpc_w2_slots of it, and the class is the team's)
+template <typename real, int KQ, int KS, typename io, class TEAM>
 __device__ __forceinline__ PolishResult<real, KS> lmpc_polish(const PolishArgs<real, KQ, KS>& a) {
+  static_assert(KS == 0 || TEAM::THREADS == 64, "the simplex rows and the terminal block are one wave's");
   extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
   real* const lds = reinterpret_cast<real*>(lds_raw);
   typedef typename vec2<real>::type real2;
   typedef double treal;
   typedef polish_limits<real> pol;
-  const int lane = threadIdx.x;
+  TEAM tm;
+  const int tid = tm.tid, lane = tm.lane;
   const int N = uni(a.N), NS = N - 1;
-  constexpr bool LEAN = lmpc_lean(sizeof(real), KQ);
-  constexpr ChainForm FORM = lmpc_chain_form(LEAN, lmpc_chain_addr(sizeof(real), KQ, KS));  // of the stage chains, as in the iteration
-  Lds<real> L{lds, N, LEAN ? LMPC_LEAN_STAGE_STRIDE : LMPC_STAGE_STRIDE, !SECOND && lmpc_waves_per_simd(sizeof(real), KQ, KS) >= 2};
+  constexpr bool LEAN = TEAM::LEAN;
+  constexpr ChainForm FORM = TEAM::FORM;
+  Lds<real> L{lds, N, LEAN ? LMPC_LEAN_STAGE_STRIDE : LMPC_STAGE_STRIDE, TEAM::PRIO};
   real* const T = L.tail();
+  tm.attach(T);
   treal* const TT = reinterpret_cast<treal*>(T + LMPC_TAIL_DOUBLES);
   ModelStream<real> MS{nullptr, nullptr, NS, lane, uni(a.have0), uni(a.have1)};
   if constexpr (LEAN) {
@@ -988,22 +1062,25 @@ __device__ __forceinline__ PolishResult<real, KS> lmpc_polish(const PolishArgs<r
 #pragma unroll
     for (int k = 0; k < 6; ++k) sx.ss0[k] = uni(sx.ss0[k]);
   }
-  auto flags = [&](int q) { return s_gf[q] >> 20; };
-  auto o_w = [&](int q) { return o_val[q] + ((flags(q) & F_EY) ? KN_EY - 1 : KN_R0); };
-  auto o_csig = [&](int q) { return (flags(q) & F_EY) ? o_val[q] + (KN_CSIG - 1) : JB + KN_CSIG; };
-  auto bounds = [&](int q) { return *reinterpret_cast<const real2*>(&lds[o_hl[q]]); };
+  auto ovq = [&](int q) { return TEAM::table(o_val[q]); };  // (the slot's table integers as the row phases read them)
+  auto ohq = [&](int q) { return TEAM::table(o_hl[q]); };
+  auto gfq = [&](int q) { return TEAM::table(s_gf[q]); };
+  auto flags = [&](int q) { return gfq(q) >> 20; };
+  auto o_w = [&](int q) { return ovq(q) + ((flags(q) & F_EY) ? KN_EY - 1 : KN_R0); };
+  auto o_csig = [&](int q) { return (flags(q) & F_EY) ? ovq(q) + (KN_CSIG - 1) : JB + KN_CSIG; };
+  auto bounds = [&](int q) { return *reinterpret_cast<const real2*>(&lds[ohq(q)]); };
   // The iterate is put aside in the handle's save area -- one contiguous block of 10 N - 4 values per problem (full-line
   // writes), values as they stand in LDS, so that they read back exactly -- and taken back from there at the start of every
   // round and when the attempt is refused: every lane reads back what it wrote itself.
   io* const keep = uni_ptr(reinterpret_cast<io*>(a.keep));
   auto put_keep = [&]() {
-    for (int e = lane; e < 10 * N - 4; e += 64) {  // knot i: z [8] (x_i, u_{i-1}) at 10 i - 2 .. (knot 0: x_0 only is not kept), v_i [2] behind it
+    for (int e = tid; e < 10 * N - 4; e += TEAM::THREADS) {  // knot i: z [8] (x_i, u_{i-1}) at 10 i - 2 .. (knot 0: x_0 only is not kept), v_i [2] behind it
       const int i = (e + 2) / 10, o = e + 2 - 10 * i;
       keep[e] = io(L.kn(i)[o]);
     }
   };
   auto get_primal = [&]() {
-    for (int e = lane; e < 10 * N - 4; e += 64) {
+    for (int e = tid; e < 10 * N - 4; e += TEAM::THREADS) {
       const int i = (e + 2) / 10, o = e + 2 - 10 * i;
       if (i >= 1 || o >= 8) L.kn(i)[o] = real(keep[e]);
     }
@@ -1029,14 +1106,14 @@ __device__ __forceinline__ PolishResult<real, KS> lmpc_polish(const PolishArgs<r
   const int max_rounds = min((int)pol::rounds, uni(a.max_rounds) & ~POLISH_EXIT);
   for (int round = 0; round < max_rounds; ++round) {
     if (round > 0) {  // every round starts from the interior point's iterate
-      wave_sync();
+      tm.sync();
       get_primal();
       sigma = sigma_keep;
       if constexpr (KS > 0) {
 #pragma unroll
         for (int q = 0; q < KS; ++q) sx.lm[q] = sx.sv[q];
       }
-      wave_sync();
+      tm.sync();
     }
     // ---- weights: theta on the held rows, nothing on the others; multipliers start from the interior point's on the
     // rows it held itself and from zero on rows a repair has added ----
@@ -1166,11 +1243,12 @@ __device__ __forceinline__ PolishResult<real, KS> lmpc_polish(const PolishArgs<r
       }
       wave_fence();
     }
-    hsig = uni(qsig + wave_sum(eysum));
+    hsig = tm.weights_sum(qsig, eysum);
     ++pol_rounds;
-    wave_sync();
+    tm.published();  // (the weights)
     PT_MARK(0)
-    riccati_factor<FORM, (KS > 0), true>(L, MS, lane, TT + TL_PT);
+    if constexpr (TEAM::CHAIN) riccati_factor<FORM, (KS > 0), true>(L, MS, lane, TT + TL_PT);
+    tm.after_chain();
     PT_MARK(3)
     bool nan_step = false;
     // ---- pol::steps multiplier steps on that factor, each from the point the one before has reached ----
@@ -1211,13 +1289,13 @@ __device__ __forceinline__ PolishResult<real, KS> lmpc_polish(const PolishArgs<r
         real2 hl[KQ];
 #pragma unroll
         for (int q = 0; q < KQ; ++q) {
-          const int gr = s_gf[q];
-          val[q] = lds[o_val[q]];
+          const int gr = gfq(q);
+          val[q] = lds[ovq(q)];
           hl[q] = bounds(q);
-          par[q] = lds[o_val[q] + ((gr >> 16) & 3) - 1];
+          par[q] = lds[ovq(q) + ((gr >> 16) & 3) - 1];
           ca[q] = lds[CTB + (gr & 0xff)];
           cb[q] = lds[CTB + ((gr >> 8) & 0xff)];
-          ql[q] = lds[o_val[q] + (KN_QLIN - 3)];
+          ql[q] = lds[ovq(q) + (KN_QLIN - 3)];
         }
 #pragma unroll
         for (int q = 0; q < KQ; ++q) {
@@ -1226,14 +1304,14 @@ __device__ __forceinline__ PolishResult<real, KS> lmpc_polish(const PolishArgs<r
           const bool hu = (held >> (2 * q)) & 1, hd = (held >> (2 * q + 1)) & 1;
           const real cu = hu ? rfma(real(pol::theta), val[q] - sg - hl[q].x, s_pu[q]) : real(0);
           const real cd = hd ? rfma(real(pol::theta), -val[q] - sg + hl[q].y, s_pl[q]) : real(0);
-          const real g = ca[q] * val[q] + cb[q] * par[q] + ((f & F_QLIN) ? ql[q] : real(0));
-          lds[o_w(q)] = g + cu - cd;
+          const real gq = ca[q] * val[q] + cb[q] * par[q] + ((f & F_QLIN) ? ql[q] : real(0));
+          lds[o_w(q)] = gq + cu - cd;
           if (k == 0) lds[(f & F_EY) ? JB + KN_EY : o_w(q) + 10] = 0.0;
           sgsum += (f & F_SIG) ? (cu + cd) : real(0);
         }
       }
-      wave_sync();
-      for (int i = lane; i < N; i += 64) {
+      tm.sync();
+      for (int i = tid; i < N; i += TEAM::THREADS) {
         real* kn = L.kn(i);
         kn[KN_R0 + 1] += kn[KN_EY];
         if (k == 0) kn[KN_R1 + 1] = (i >= 1) ? kn[KN_CSIG] : 0.0;
@@ -1242,19 +1320,22 @@ __device__ __forceinline__ PolishResult<real, KS> lmpc_polish(const PolishArgs<r
         wave_sync();
         if (lane < 6) L.kn(N - 1)[KN_R0 + lane] += real(TT[TL_TG + lane]);
       }
-      wave_sync();
+      tm.sync();
       PT_MARK(0)
-      if (k == 0 && has_sigma)
-        riccati_solve<FORM, 2>(L, MS, lane, pf);
-      else
-        riccati_solve<FORM, 1>(L, MS, lane, pf);
+      if constexpr (TEAM::CHAIN) {
+        if (k == 0 && has_sigma)
+          riccati_solve<FORM, 2>(L, MS, lane, pf);
+        else
+          riccati_solve<FORM, 1>(L, MS, lane, pf);
+      }
+      tm.after_chain();
       real dz0[KQ], dz1[KQ], val[KQ];
       real2 hl[KQ];
 #pragma unroll
       for (int q = 0; q < KQ; ++q) {
-        dz0[q] = lds[o_val[q] + 10];
-        dz1[q] = lds[o_val[q] + 20];
-        val[q] = lds[o_val[q]];
+        dz0[q] = lds[ovq(q) + 10];
+        dz1[q] = lds[ovq(q) + 20];
+        val[q] = lds[ovq(q)];
         hl[q] = bounds(q);
       }
       real dsigma = 0.0;
@@ -1271,7 +1352,7 @@ __device__ __forceinline__ PolishResult<real, KS> lmpc_polish(const PolishArgs<r
             red[1] += sch ? cs[q] * dz1[q] : real(0);
           }
         }
-        wave_sum_n<3>(red);
+        tm.sum3(red);
         if (k == 0) ce = red[1];
         const real qsg = qsig * sigma - red[2];
         dsigma = uni(-(qsg + red[0]) / (hsig + ce));
@@ -1324,13 +1405,13 @@ __device__ __forceinline__ PolishResult<real, KS> lmpc_polish(const PolishArgs<r
         const int f = flags(q);
         const real dval = dz0[q] + dsigma * dz1[q];
         finite_step = finite_step && (fabs(dval) < inf);
-        stepmax = fmax(stepmax, (f & F_MOVE) ? fabs(dval) * real(slot_inv_scale((s_gf[q] >> 27) & 15)) : real(0));
+        stepmax = fmax(stepmax, (f & F_MOVE) ? fabs(dval) * real(slot_inv_scale((gfq(q) >> 27) & 15)) : real(0));
         const real sg = (f & F_SIG) ? sigma : 0.0, dsg = (f & F_SIG) ? dsigma : 0.0;
         const bool hu = (held >> (2 * q)) & 1, hd = (held >> (2 * q + 1)) & 1;
         s_pu[q] = hu ? rfma(real(pol::theta), (val[q] - sg - hl[q].x) + (dval - dsg), s_pu[q]) : real(0);
         s_pl[q] = hd ? rfma(real(pol::theta), (-val[q] - sg + hl[q].y) + (-dval - dsg), s_pl[q]) : real(0);
         const bool mv = (f & F_MOVE) != 0;
-        lds[mv ? o_val[q] : JB + q] += mv ? dval : real(0);
+        lds[mv ? ovq(q) : JB + q] += mv ? dval : real(0);
       }
       if (has_sigma) sigma = uni(sigma + dsigma);
       if constexpr (KS > 0) {
@@ -1342,9 +1423,10 @@ __device__ __forceinline__ PolishResult<real, KS> lmpc_polish(const PolishArgs<r
           finite_step = finite_step && (fabs(sx.dl[q]) < tinf);
         }
       }
-      nan_step = nan_step || (__ballot(!finite_step) != 0);
-      last_step = wave_max(stepmax);  // (scaled: what kkt[0] reports after an accepted polish)
-      wave_sync();
+      tm.step_end(stepmax, !finite_step);
+      nan_step = nan_step || tm.any_of(PS_NAN, !finite_step);
+      last_step = tm.max_of(PS_STEP, stepmax);  // (scaled: what kkt[0] reports after an accepted polish)
+      tm.published();  // (the update)
       if constexpr (KS > 0) {  // the hull residual and the simplex residual at the new point (the next step's gradient)
         treal ul[7] = {0, 0, 0, 0, 0, 0, 0};
 #pragma unroll
@@ -1367,7 +1449,7 @@ __device__ __forceinline__ PolishResult<real, KS> lmpc_polish(const PolishArgs<r
         wave_fence();
       }
 #ifdef LMPC_POLISH_TRACE
-      if (blockIdx.x == 0 && lane == 0) printf("      step %d: %.3e\n", k, (double)last_step);
+      if (blockIdx.x == 0 && tid == 0) printf("      step %d: %.3e\n", k, (double)last_step);
 #endif
       if (k >= 1 && last_step <= real(pol::step_ok)) break;  // (converged: the remaining steps would move nothing)
     }
@@ -1376,7 +1458,7 @@ __device__ __forceinline__ PolishResult<real, KS> lmpc_polish(const PolishArgs<r
     real2 hl[KQ];
 #pragma unroll
     for (int q = 0; q < KQ; ++q) {
-      val[q] = lds[o_val[q]];
+      val[q] = lds[ovq(q)];
       hl[q] = bounds(q);
     }
     bool bad = false, neg = false, weakneg = false, viol = false;
@@ -1411,20 +1493,21 @@ __device__ __forceinline__ PolishResult<real, KS> lmpc_polish(const PolishArgs<r
     }
     // (a last multiplier step that still moved the iterate: the steps have not converged -- held rows that are stiff meet
     // their bounds long before the point is stationary, so the row tests alone would pass)
-    const bool anybad = nan_step || !(last_step <= real(pol::step_tol)) || __ballot(bad) != 0;
-    const bool anyneg = __ballot(neg) != 0, anyweak = __ballot(weakneg) != 0;
-    const bool anyviol = __ballot(viol) != 0;
+    tm.kkt(bad, neg, weakneg, viol, ymin, worst);
+    const bool anybad = nan_step || !(last_step <= real(pol::step_tol)) || tm.any_of(PK_BAD, bad);
+    const bool anyneg = tm.any_of(PK_NEG, neg), anyweak = tm.any_of(PK_WEAK, weakneg);
+    const bool anyviol = tm.any_of(PK_VIOL, viol);
 #ifdef LMPC_POLISH_TRACE  // (diagnostics: workgroup 0 prints what each round's KKT test saw)
     {
-      const real tr_held = wave_sum(real(__popc(held & 0x0fffffff))), tr_ymin = wave_min(ymin), tr_worst = wave_max(worst);
-      if (blockIdx.x == 0 && lane == 0)
+      const real tr_held = tm.sum(real(__popc(held & 0x0fffffff))), tr_ymin = tm.min_of(PK_YMIN, ymin), tr_worst = tm.max_of(PK_WORST, worst);
+      if (blockIdx.x == 0 && tid == 0)
         printf("polish round %d: held %d last_step %.3e bad %d (rows %d nan %d) neg %d weak %d viol %d ymin %.3e worst %.3e\n", pol_rounds, (int)tr_held,
-               (double)last_step, (int)anybad, (int)(__ballot(bad) != 0), (int)nan_step, (int)anyneg, (int)anyweak, (int)anyviol, (double)tr_ymin, (double)tr_worst);
+               (double)last_step, (int)anybad, (int)tm.any_of(PK_BAD, bad), (int)nan_step, (int)anyneg, (int)anyweak, (int)anyviol, (double)tr_ymin, (double)tr_worst);
     }
 #endif
     if (!anybad && !anyneg && !anyviol) {  // the optimum for the held set, and the held set passes the KKT test
-      mu = uni(wave_sum(comp) * inv_m);
-      rdmax = wave_max(worst);
+      mu = tm.mean(comp, inv_m);
+      rdmax = tm.max_of(PK_WORST, worst);
       accepted = true;
       break;
     }
@@ -1432,7 +1515,7 @@ __device__ __forceinline__ PolishResult<real, KS> lmpc_polish(const PolishArgs<r
     // repair: release rows with a negative multiplier -- those the interior point did not hold firmly if there are such,
     // otherwise the most negative ones (a wrong row drags its neighbours' multipliers below zero) -- and only when no
     // multiplier is negative, hold the rows the new point violates
-    const real ycut = real(0.5) * wave_min(ymin);
+    const real ycut = real(0.5) * tm.min_of(PK_YMIN, ymin);
     const int before = held;
 #pragma unroll
     for (int q = 0; q < KQ; ++q) {
@@ -1455,17 +1538,17 @@ __device__ __forceinline__ PolishResult<real, KS> lmpc_polish(const PolishArgs<r
         held = (held & ~((dq ? 1 : 0) << (28 + q))) | ((aq ? 1 : 0) << (28 + q));
       }
     }
-    if (__ballot(held != before) == 0) break;  // (the multiplier steps did not converge on a consistent set: nothing to repair)
+    if (!tm.changed(held != before)) break;  // (the multiplier steps did not converge on a consistent set: nothing to repair)
   }
   if (!accepted) {  // refused: iterate, slack variable and simplex weights as the interior point left them
-    wave_sync();
+    tm.sync();
     get_primal();
     sigma = sigma_keep;
     if constexpr (KS > 0) {
 #pragma unroll
       for (int q = 0; q < KS; ++q) sx.lm[q] = sx.sv[q];
     }
-    wave_sync();
+    tm.sync();
   }
   PolishResult<real, KS> res;
   res.accepted = accepted ? 1 : 0;
@@ -1493,7 +1576,7 @@ __device__ __forceinline__ PolishResult<real, KS> lmpc_polish(const PolishArgs<r
 
 template <typename real, int KQ, int KS, typename io, bool SECOND = false>
 __device__ __attribute__((noinline)) PolishResult<real, KS> lmpc_polish_call(const PolishArgs<real, KQ, KS> a) {
-  return lmpc_polish<real, KQ, KS, io, SECOND>(a);
+  return lmpc_polish<real, KQ, KS, io, Wave1<sizeof(real), KQ, KS, SECOND>>(a);
 }
 
 // `real` is the arithmetic and LDS type, `io` the type of the arrays in HBM: <double, double> is the reference's
@@ -1850,7 +1933,7 @@ __device__ __forceinline__ void lmpc_solve_problem(
     if constexpr (lmpc_polish_is_call(sizeof(real), KQ, KS) && !(WARMK && lmpc_waves_per_simd(sizeof(real), KQ, KS) >= 2))
       pr = lmpc_polish_call<real, KQ, KS, io, SECOND>(pa);
     else
-      pr = lmpc_polish<real, KQ, KS, io, SECOND>(pa);
+      pr = lmpc_polish<real, KQ, KS, io, Wave1<sizeof(real), KQ, KS, SECOND>>(pa);
     pol_rounds = uni(pr.pol_rounds);
 #ifdef LMPC_PHASE_TIMING
     if constexpr (KS == 0) {  // (the learning kernels use buckets 13 .. 15 for their terminal block)

@@ -1,7 +1,8 @@
 // lmpc_solve_w2.hip.h -- TWO wavefronts per problem on one LDS record: the fp64 tracking kernels for N >= 24 (round 6).
 // (Included by lmpc_solve_kernel.hip behind everything it uses as it is: that file's stage chains -- riccati_factor, riccati_solve and
-//  feedback_rollout, each ONE call here in the form lmpc_chain_form(LEAN, false) of the instantiation --, its lean model stream and the
-//  polish's argument structs; the reductions and pins of lmpc_wave.hip.h, the layout and policies of
+//  feedback_rollout, each ONE call here in the form lmpc_chain_form(LEAN, false) of the instantiation --, its lean model stream, and
+//  its active-set polish, lmpc_polish with its argument structs: this file has no polish of its own, it describes the team of two
+//  waves (Wave2) that runs the one there; the reductions and pins of lmpc_wave.hip.h, the layout and policies of
 //  lmpc_solve_layout.hip.h, the limits of lmpc_limits.hip.h.  A translation unit of its own, lmpc_lib_w2.hip: its object compiles
 //  in twenty seconds.)
 //
@@ -88,267 +89,57 @@ __device__ __forceinline__ double wg_min(Wg2& g, double x) {
 }
 __device__ __forceinline__ bool wg_any(Wg2& g, bool p) { return wg_max(g, __ballot(p) != 0 ? 1.0 : 0.0) > 0.5; }
 
-// ---- the active-set polish on two waves: lmpc_polish (lmpc_solve_kernel.hip) for real = io = double, KS = 0, rows on 128 lanes ----
-template <int KQ, int KL, bool CHAIN>
-__device__ __attribute__((noinline)) PolishResult<double, 0> lmpc_polish_w2(const PolishArgs<double, KL, 0> a) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
-  typedef double real;
-  typedef double2 real2;
-  typedef polish_limits<double> pol;
-  real* const lds = reinterpret_cast<real*>(lds_raw);
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  const int N = uni(a.N), NS = N - 1;
-  constexpr bool LEAN = lmpc_lean(8, KQ);
-  constexpr ChainForm FORM = lmpc_chain_form(LEAN, false);  // of the stage chains (lmpc_solve_layout.hip.h); pinned addresses: not taken here
-  Lds<real> L{lds, N, LEAN ? LMPC_LEAN_STAGE_STRIDE : LMPC_STAGE_STRIDE, true};
-  real* const T = L.tail();
-  Wg2 g{T + TL_Y, wv, 0};
-  ModelStream<real> MS{nullptr, nullptr, NS, lane, uni(a.have0), uni(a.have1)};
-  if constexpr (LEAN) {
-    MS.ws = uni_ptr(reinterpret_cast<const real*>(a.ws));
-    MS.buf = T + LMPC_TAIL_DOUBLES;
+// ---- the active-set polish on two waves: lmpc_polish itself (lmpc_solve_kernel.hip), run by this team ----
+// Wave2 is what lmpc_polish asks of a team (the account stands with Wave1, next to the polish): the rows on 128 threads, the stage
+// chains on wave 0 with a barrier behind each, the slot tables read through the empty asm, every exchange one wg_reduce_n -- batched
+// where the body has two results to agree on at one point ({largest step, not finite} at the end of a multiplier step; the four votes,
+// the most negative multiplier as a maximum of its negative, and the worst row in the KKT test) -- whose barrier also publishes the
+// LDS writes before it.  KQ is the class's (the one-wave kernel's slots per lane): it decides the layout; the polish itself is
+// instantiated with KL = lmpc_w2_slots(KQ) slots per lane, KS = 0, real = io = double.
+template <int KQ, bool CHAIN_>
+struct Wave2 {
+  static constexpr int THREADS = W2_THREADS;
+  static constexpr bool CHAIN = CHAIN_, OPAQUE = true;
+  static constexpr bool LEAN = lmpc_lean(8, KQ);
+  static constexpr ChainForm FORM = lmpc_chain_form(LEAN, false);  // (pinned addresses: not taken here)
+  static constexpr bool PRIO = true;
+  const int tid, lane;
+  Wg2 g;
+  double ex[6];  // what the last step_end / kkt exchange agreed on, by PolishSlot
+  __device__ __forceinline__ Wave2() : tid(threadIdx.x), lane(tid & 63), g{nullptr, tid >> 6, 0} {}
+  __device__ __forceinline__ void attach(double* tail) { g.red = tail + TL_Y; }
+  __device__ static __forceinline__ int table(int v) { asm volatile("" : "+v"(v)); return v; }  // (opaque table reads: see lmpc_solve_problem_w2)
+  __device__ static __forceinline__ void sync() { wg_sync(); }
+  __device__ static __forceinline__ void published() {}
+  __device__ static __forceinline__ void after_chain() { wg_sync(); }
+  __device__ __forceinline__ double weights_sum(double q, double x) { return q + wg_sum(g, x); }
+  __device__ __forceinline__ void sum3(double (&v)[3]) { wg_reduce_n<op_sum, 3>(g, v); }
+  __device__ __forceinline__ void step_end(double stepmax, bool bad) {
+    double red[2] = {stepmax, bad ? 1.0 : 0.0};
+    wg_reduce_n<op_max, 2>(g, red);
+    ex[PS_STEP] = red[0];
+    ex[PS_NAN] = red[1];
   }
-  const real inf = real(INFINITY);
-  const bool has_sigma = uni(a.has_sigma) != 0;
-  const real qsig = uni(a.qsig), inv_m = uni(a.inv_m);
-  real sigma = uni(a.sigma);
-  real hsig = 0.0, ce = 0.0, mu = 0.0, rdmax = 0.0, last_step = 0.0;
-  int pol_rounds = uni(a.pol_rounds);
-  Prof pf;
-  (void)pf;
-  const int KNB = NS * L.stride;
-  const int JB = KNB + N * LMPC_KNOT_STRIDE + TL_W;
-  const int CTB = KNB + N * LMPC_KNOT_STRIDE + TL_CT;
-  int o_val[KL], o_hl[KL], s_gf[KL];
-  real s_tu[KL], s_tl[KL], s_lu[KL], s_ll[KL], s_pu[KL], s_pl[KL];
-#pragma unroll
-  for (int q = 0; q < KL; ++q) {
-    o_val[q] = a.o_val[q];
-    o_hl[q] = a.o_hl[q];
-    s_gf[q] = a.s_gf[q];
-    s_tu[q] = a.s_tu[q];
-    s_tl[q] = a.s_tl[q];
-    s_lu[q] = a.s_lu[q];
-    s_ll[q] = a.s_ll[q];
-    s_pu[q] = s_pl[q] = 0.0;
-  }
-  auto ovq = [&](int q) { int v = o_val[q]; asm volatile("" : "+v"(v)); return v; };  // (opaque table reads: see lmpc_solve_problem_w2)
-  auto ohq = [&](int q) { int v = o_hl[q]; asm volatile("" : "+v"(v)); return v; };
-  auto gfq = [&](int q) { int v = s_gf[q]; asm volatile("" : "+v"(v)); return v; };
-  auto flags = [&](int q) { return gfq(q) >> 20; };
-  auto o_w = [&](int q) { return ovq(q) + ((flags(q) & F_EY) ? KN_EY - 1 : KN_R0); };
-  auto o_csig = [&](int q) { return (flags(q) & F_EY) ? ovq(q) + (KN_CSIG - 1) : JB + KN_CSIG; };
-  auto bounds = [&](int q) { return *reinterpret_cast<const real2*>(&lds[ohq(q)]); };
-  double* const keep = uni_ptr(reinterpret_cast<double*>(a.keep));
-  auto put_keep = [&]() {
-    for (int e = tid; e < 10 * N - 4; e += W2_THREADS) {
-      const int i = (e + 2) / 10, o = e + 2 - 10 * i;
-      keep[e] = L.kn(i)[o];
-    }
-  };
-  auto get_primal = [&]() {
-    for (int e = tid; e < 10 * N - 4; e += W2_THREADS) {
-      const int i = (e + 2) / 10, o = e + 2 - 10 * i;
-      if (i >= 1 || o >= 8) L.kn(i)[o] = keep[e];
-    }
-  };
-  const real gam = (uni(a.max_rounds) & POLISH_EXIT) ? real(POLISH_EXIT_GAMMA) : real(1);  // (lmpc_polish: in doubt a row is held at the exit)
-  int held = 0;
-#pragma unroll
-  for (int q = 0; q < KL; ++q) held |= (s_lu[q] > gam * s_tu[q] ? 1 << (2 * q) : 0) | (s_ll[q] > gam * s_tl[q] ? 2 << (2 * q) : 0);
-  const real sigma_keep = sigma;
-  put_keep();
-  bool accepted = false, noise = false;
-  const int max_rounds = min((int)pol::rounds, uni(a.max_rounds) & ~POLISH_EXIT);
-  for (int round = 0; round < max_rounds; ++round) {
-    if (round > 0) {
-      wg_sync();
-      get_primal();
-      sigma = sigma_keep;
-      wg_sync();
-    }
-    real eysum = 0.0;
-#pragma unroll
-    for (int q = 0; q < KL; ++q) {
-      const int f = flags(q);
-      const bool hu = (held >> (2 * q)) & 1, hd = (held >> (2 * q + 1)) & 1;
-      const real thu = hu ? real(pol::theta) : real(0), thd = hd ? real(pol::theta) : real(0);
-      lds[o_w(q)] = thu + thd;
-      lds[o_csig(q)] = (f & F_SIG) ? (thd - thu) : real(0);
-      eysum += (f & F_SIG) ? (thu + thd) : real(0);
-      s_pu[q] = (hu && s_lu[q] > s_tu[q]) ? s_lu[q] : real(0);
-      s_pl[q] = (hd && s_ll[q] > s_tl[q]) ? s_ll[q] : real(0);
-    }
-    hsig = qsig + wg_sum(g, eysum);  // (its barrier also publishes the weights)
-    ++pol_rounds;
-    if constexpr (CHAIN) riccati_factor<FORM, false, true>(L, MS, lane, (const double*)nullptr);
-    wg_sync();
-    bool nan_step = false;
-    for (int k = 0; k < pol::steps; ++k) {
-      real sgsum = 0.0;
-      {
-        real val[KL], par[KL], ca[KL], cb[KL], ql[KL];
-        real2 hl[KL];
-#pragma unroll
-        for (int q = 0; q < KL; ++q) {
-          const int gr = gfq(q);
-          val[q] = lds[ovq(q)];
-          hl[q] = bounds(q);
-          par[q] = lds[ovq(q) + ((gr >> 16) & 3) - 1];
-          ca[q] = lds[CTB + (gr & 0xff)];
-          cb[q] = lds[CTB + ((gr >> 8) & 0xff)];
-          ql[q] = lds[ovq(q) + (KN_QLIN - 3)];
-        }
-#pragma unroll
-        for (int q = 0; q < KL; ++q) {
-          const int f = flags(q);
-          const real sg = (f & F_SIG) ? sigma : 0.0;
-          const bool hu = (held >> (2 * q)) & 1, hd = (held >> (2 * q + 1)) & 1;
-          const real cu = hu ? rfma(real(pol::theta), val[q] - sg - hl[q].x, s_pu[q]) : real(0);
-          const real cd = hd ? rfma(real(pol::theta), -val[q] - sg + hl[q].y, s_pl[q]) : real(0);
-          const real gq = ca[q] * val[q] + cb[q] * par[q] + ((f & F_QLIN) ? ql[q] : real(0));
-          lds[o_w(q)] = gq + cu - cd;
-          if (k == 0) lds[(f & F_EY) ? JB + KN_EY : o_w(q) + 10] = 0.0;
-          sgsum += (f & F_SIG) ? (cu + cd) : real(0);
-        }
-      }
-      wg_sync();
-      for (int i = tid; i < N; i += W2_THREADS) {
-        real* kn = L.kn(i);
-        kn[KN_R0 + 1] += kn[KN_EY];
-        if (k == 0) kn[KN_R1 + 1] = (i >= 1) ? kn[KN_CSIG] : 0.0;
-      }
-      wg_sync();
-      if constexpr (CHAIN) {
-        if (k == 0 && has_sigma)
-          riccati_solve<FORM, 2>(L, MS, lane, pf);
-        else
-          riccati_solve<FORM, 1>(L, MS, lane, pf);
-      }
-      wg_sync();
-      real dz0[KL], dz1[KL], val[KL];
-      real2 hl[KL];
-#pragma unroll
-      for (int q = 0; q < KL; ++q) {
-        dz0[q] = lds[ovq(q) + 10];
-        dz1[q] = lds[ovq(q) + 20];
-        val[q] = lds[ovq(q)];
-        hl[q] = bounds(q);
-      }
-      real dsigma = 0.0;
-      if (has_sigma) {
-        real red[3] = {0.0, 0.0, sgsum};
-        {
-          real cs[KL];
-#pragma unroll
-          for (int q = 0; q < KL; ++q) cs[q] = lds[o_csig(q)];
-#pragma unroll
-          for (int q = 0; q < KL; ++q) {
-            const bool sch = (flags(q) & F_SCH) != 0;
-            red[0] += sch ? cs[q] * dz0[q] : real(0);
-            red[1] += sch ? cs[q] * dz1[q] : real(0);
-          }
-        }
-        wg_reduce_n<op_sum, 3>(g, red);
-        if (k == 0) ce = red[1];
-        const real qsg = qsig * sigma - red[2];
-        dsigma = uni(-(qsg + red[0]) / (hsig + ce));
-      }
-      bool finite_step = dsigma == dsigma;
-      real stepmax = 0.0;
-#pragma unroll
-      for (int q = 0; q < KL; ++q) {
-        const int f = flags(q);
-        const real dval = dz0[q] + dsigma * dz1[q];
-        finite_step = finite_step && (fabs(dval) < inf);
-        stepmax = fmax(stepmax, (f & F_MOVE) ? fabs(dval) * real(slot_inv_scale((gfq(q) >> 27) & 15)) : real(0));
-        const real sg = (f & F_SIG) ? sigma : 0.0, dsg = (f & F_SIG) ? dsigma : 0.0;
-        const bool hu = (held >> (2 * q)) & 1, hd = (held >> (2 * q + 1)) & 1;
-        s_pu[q] = hu ? rfma(real(pol::theta), (val[q] - sg - hl[q].x) + (dval - dsg), s_pu[q]) : real(0);
-        s_pl[q] = hd ? rfma(real(pol::theta), (-val[q] - sg + hl[q].y) + (-dval - dsg), s_pl[q]) : real(0);
-        const bool mv = (f & F_MOVE) != 0;
-        lds[mv ? ovq(q) : JB + q] += mv ? dval : real(0);
-      }
-      if (has_sigma) sigma = uni(sigma + dsigma);
-      {
-        real red[2] = {stepmax, finite_step ? 0.0 : 1.0};
-        wg_reduce_n<op_max, 2>(g, red);  // (its barrier also publishes the update)
-        last_step = red[0];
-        nan_step = nan_step || red[1] > 0.5;
-      }
-      if (k >= 1 && last_step <= real(pol::step_ok)) break;
-    }
-    // ---- KKT test of the point reached; repair of the held set ----
-    real val[KL];
-    real2 hl[KL];
-#pragma unroll
-    for (int q = 0; q < KL; ++q) {
-      val[q] = lds[ovq(q)];
-      hl[q] = bounds(q);
-    }
-    bool bad = false, neg = false, weakneg = false, viol = false;
-    real ymin = 0.0, comp = 0.0, worst = 0.0;
-#pragma unroll
-    for (int q = 0; q < KL; ++q) {
-      const int f = flags(q);
-      const real sg = (f & F_SIG) ? sigma : 0.0;
-      const real ru = val[q] - sg - hl[q].x, rl = -val[q] - sg + hl[q].y;
-      const bool hu = (held >> (2 * q)) & 1, hd = (held >> (2 * q + 1)) & 1;
-      const bool nu_ = hu && s_pu[q] < -real(pol::dual), nd_ = hd && s_pl[q] < -real(pol::dual);
-      bad = bad || (hu && !(fabs(ru) <= real(pol::feas))) || (hd && !(fabs(rl) <= real(pol::feas)));
-      neg = neg || nu_ || nd_;
-      weakneg = weakneg || (nu_ && s_lu[q] < real(POLISH_STRONG) * s_tu[q]) || (nd_ && s_ll[q] < real(POLISH_STRONG) * s_tl[q]);
-      viol = viol || (!hu && (f & F_UP) && !(ru <= real(pol::feas))) || (!hd && (f & F_LO) && !(rl <= real(pol::feas)));
-      ymin = fmin(ymin, fmin(hu ? s_pu[q] : real(0), hd ? s_pl[q] : real(0)));
-      comp += (hu ? fabs(s_pu[q] * ru) : real(0)) + (hd ? fabs(s_pl[q] * rl) : real(0));
-      worst = fmax(worst, fmax((f & F_UP) ? ru : real(0), (f & F_LO) ? rl : real(0)));
-    }
-    // the four votes, the most negative multiplier (as a maximum of its negative) and the worst row in one exchange
-    real vote[6] = {__ballot(bad) != 0 ? 1.0 : 0.0, __ballot(neg) != 0 ? 1.0 : 0.0, __ballot(weakneg) != 0 ? 1.0 : 0.0,
-                    __ballot(viol) != 0 ? 1.0 : 0.0, -ymin, worst};
+  __device__ __forceinline__ void kkt(bool bad, bool neg, bool weak, bool viol, double ymin, double worst) {
+    double vote[6] = {__ballot(bad) != 0 ? 1.0 : 0.0, __ballot(neg) != 0 ? 1.0 : 0.0, __ballot(weak) != 0 ? 1.0 : 0.0,
+                      __ballot(viol) != 0 ? 1.0 : 0.0, -ymin, worst};
     wg_reduce_n<op_max, 6>(g, vote);
-    const bool anybad = nan_step || !(last_step <= real(pol::step_tol)) || vote[0] > 0.5;
-    const bool anyneg = vote[1] > 0.5, anyweak = vote[2] > 0.5, anyviol = vote[3] > 0.5;
-    if (!anybad && !anyneg && !anyviol) {
-      mu = wg_sum(g, comp) * inv_m;
-      rdmax = vote[5];
-      accepted = true;
-      break;
-    }
-    noise = anybad && !anyneg && !anyviol;
-    const real ycut = real(0.5) * (-vote[4]);
-    const int before = held;
 #pragma unroll
-    for (int q = 0; q < KL; ++q) {
-      const int f = flags(q);
-      const real sg = (f & F_SIG) ? sigma : 0.0;
-      const real ru = val[q] - sg - hl[q].x, rl = -val[q] - sg + hl[q].y;
-      const bool hu = (held >> (2 * q)) & 1, hd = (held >> (2 * q + 1)) & 1;
-      const bool du = hu && s_pu[q] < -real(pol::dual) && (anyweak ? s_lu[q] < real(POLISH_STRONG) * s_tu[q] : s_pu[q] <= ycut);
-      const bool dd = hd && s_pl[q] < -real(pol::dual) && (anyweak ? s_ll[q] < real(POLISH_STRONG) * s_tl[q] : s_pl[q] <= ycut);
-      const bool au = !anyneg && !hu && (f & F_UP) && !(ru <= real(pol::feas));
-      const bool ad = !anyneg && !hd && (f & F_LO) && !(rl <= real(pol::feas));
-      held = (held & ~((du ? 1 : 0) << (2 * q)) & ~((dd ? 2 : 0) << (2 * q))) | ((au ? 1 : 0) << (2 * q)) | ((ad ? 2 : 0) << (2 * q));
-    }
-    if (!wg_any(g, held != before)) break;
+    for (int k = 0; k < 6; ++k) ex[k] = vote[k];
   }
-  if (!accepted) {
-    wg_sync();
-    get_primal();
-    sigma = sigma_keep;
-    wg_sync();
-  }
-  PolishResult<double, 0> res;
-  res.accepted = accepted ? 1 : 0;
-  res.noise = (!accepted && noise) ? 1 : 0;
-  res.pol_rounds = pol_rounds;
-  res.have0 = MS.have0;
-  res.have1 = MS.have1;
-  res.sigma = sigma;
-  res.mu = mu;
-  res.rdmax = rdmax;
-  res.last_step = last_step;
-  return res;
+  // (the lane's own value is not looked at: the exchange has the team's)
+  __device__ __forceinline__ bool any_of(int slot, bool) const { return ex[slot] > 0.5; }
+  __device__ __forceinline__ double min_of(int slot, double) const { return -ex[slot]; }  // (exchanged as a maximum of its negative)
+  __device__ __forceinline__ double max_of(int slot, double) const { return ex[slot]; }
+  __device__ __forceinline__ double mean(double x, double inv_m) { return wg_sum(g, x) * inv_m; }
+  __device__ __forceinline__ bool changed(bool p) { return wg_any(g, p); }
+  __device__ __forceinline__ double sum(double x) { return wg_sum(g, x); }
+};
+
+// (a call, as in the one-wave fp64 kernels: lmpc_polish_call; what crosses it stays by value)
+template <int KQ, int KL, bool CHAIN>
+__device__ __attribute__((noinline)) PolishResult<double, 0> lmpc_polish_call_w2(const PolishArgs<double, KL, 0> a) {
+  return lmpc_polish<double, KL, 0, double, Wave2<KQ, CHAIN>>(a);
 }
 
 // ---- one problem on two waves: lmpc_solve_problem (lmpc_solve_kernel.hip) for real = io = double, KS = 0, cold start ----
@@ -515,7 +306,7 @@ __device__ __forceinline__ void lmpc_solve_problem_w2(const lmpc_params& P, cons
       pa.s_lu[q] = s_lu[q];
       pa.s_ll[q] = s_ll[q];
     }
-    const PolishResult<real, 0> pr = lmpc_polish_w2<KQ, KL, CHAIN>(pa);
+    const PolishResult<real, 0> pr = lmpc_polish_call_w2<KQ, KL, CHAIN>(pa);
     g.par = 0;  // (the polish leaves its exchange parity behind; both waves restart from the same one)
     wg_sync();
     pol_rounds = uni(pr.pol_rounds);

@@ -11,8 +11,11 @@ Per function it reports one of
     different               anything else (the two versions are written to <out>/diff/ for a look with diff)
 and exits 1 if any function is different or missing.  Meant for refactors of the solve kernel: the check needs no GPU.
 
-usage: isa_diff.py TREE_A TREE_B [--out DIR] [--jobs N (<= 16)] [--reuse] [--units lmpc_lib_w2,...] [--no-dbg]
+usage: isa_diff.py TREE_A TREE_B [--out DIR] [--jobs N (<= 16)] [--reuse] [--units lmpc_lib_w2,...] [--no-dbg] [--rename OLD=NEW ...]
   --reuse keeps listings already under <out>/a or <out>/b (a parent built once serves many comparisons)
+  --rename OLD=NEW (repeatable) states that tree B calls NEW what tree A calls OLD: every occurrence of OLD in listing A -- mangled
+    names or prefixes of them, e.g. _Z14lmpc_polish_w2=_Z19lmpc_polish_call_w2 -- is replaced before the split, so that a renamed
+    function and the callers that name it are compared by content instead of reported missing
 """
 import argparse
 import concurrent.futures
@@ -42,13 +45,15 @@ def build(tree, out, unit, dbg, reuse):
     return path
 
 
-def split(path):
+def split(path, renames=()):
     """listing -> {name: lines}: one part per function (body and kernel descriptor), one per metadata entry, the rest as '(module)'"""
     parts = {"(module)": []}
     cur = parts["(module)"]
     meta = None
     for line in open(path):
         line = CUID.sub("__hip_cuid_X", line.rstrip("\n"))
+        for old, new in renames:
+            line = line.replace(old, new)
         m = FUNC.match(line)
         if m:
             cur = parts.setdefault(m.group(1), [])
@@ -101,8 +106,10 @@ def main():
     ap.add_argument("--reuse", action="store_true")
     ap.add_argument("--units", default=",".join(UNITS))
     ap.add_argument("--no-dbg", action="store_true")
+    ap.add_argument("--rename", action="append", default=[], metavar="OLD=NEW")
     args = ap.parse_args()
     units = args.units.split(",")
+    renames = [tuple(r.split("=", 1)) for r in args.rename]
     cfgs = [(u, d) for u in units for d in ([False] if args.no_dbg else [False, True])]
     outs = {"a": os.path.join(args.out, "a"), "b": os.path.join(args.out, "b")}
     for d in list(outs.values()) + [os.path.join(args.out, "diff")]:
@@ -116,7 +123,7 @@ def main():
     bad = 0
     for u, d in cfgs:
         tag = u + ("_dbg" if d else "")
-        pa, pb = split(paths[("a", u, d)]), split(paths[("b", u, d)])
+        pa, pb = split(paths[("a", u, d)], renames), split(paths[("b", u, d)])
         print("== %s: %d / %d lines" % (tag, sum(map(len, pa.values())), sum(map(len, pb.values()))))
         for name in list(pa) + [n for n in pb if n not in pa]:
             if name not in pa or name not in pb:
