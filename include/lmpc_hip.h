@@ -25,6 +25,18 @@
  *     N counts knot points: X is 6 x N, U and dU are 2 x (N-1) (racing_mpc.cpp:43-45).
  *   - A handle is not re-entrant (the reference holds traj_mutex_ across solve,
  *     racing_mpc_node.cpp:158,360); distinct handles (one per GPU) are independent.
+ *   - Streams.  Every kernel launch, memset and asynchronous copy of an entry point goes to the handle's stream (lmpc_set_stream),
+ *     never to the null stream.  An entry point whose array arguments are device pointers is ASYNCHRONOUS unless its comment says
+ *     otherwise: it enqueues and returns, and neither waits for the stream nor reads device data on the host.  An entry point that
+ *     takes or returns HOST arrays, or that allocates or frees device memory (the create / destroy calls, lmpc_set_safe_set,
+ *     lmpc_set_regression_laps, lmpc_fleet_ss_set_regression, lmpc_reserve, a first call that grows a workspace), is BLOCKING: it
+ *     waits for the handle's stream where its comment says so, and the runtime's allocator may wait for the whole device.  Four of
+ *     them -- lmpc_set_safe_set, lmpc_set_regression_laps, lmpc_fleet_ss_load, lmpc_fleet_ss_get_laps -- move their host arrays with
+ *     the synchronous hipMemcpy (a copy on the null stream that has finished when it returns), between waits on the handle's
+ *     stream: behind the first wait nothing of the handle is in flight, and what they enqueue afterwards goes to the handle's
+ *     stream again.  The rest only read or set host values of the handle.  The three lists are in INTEGRATION.md;
+ *     tests/stream_cases.py holds one class per prototype and tests/test_gpu_streams.py holds every entry point to it on a stream
+ *     that is held by a timed gate.
  */
 #ifndef LMPC_HIP_H_
 #define LMPC_HIP_H_
@@ -153,14 +165,20 @@ typedef struct lmpc_handle lmpc_handle;
 /* Builds the parametric problem once, as RacingMPC::RacingMPC does
  * (racing_mpc.cpp:31-202).  `device` is the HIP device ordinal. */
 int lmpc_create(const lmpc_config* cfg, const lmpc_vehicle* veh, int device, lmpc_handle** out);
-/* On failure *out may still be non-NULL so that lmpc_last_error(*out) can be read; destroy it. */
+/* On failure *out may still be non-NULL so that lmpc_last_error(*out) can be read; destroy it.  lmpc_create allocates (blocking, no
+ * stream yet); lmpc_destroy waits for the handle's stream before it frees anything. */
 void lmpc_destroy(lmpc_handle* h);
 const char* lmpc_last_error(const lmpc_handle* h);
 
 /* Run subsequent launches on `hip_stream` (a hipStream_t).  A new handle uses the device's
- * default (null) stream; NULL selects it again. */
+ * default (null) stream; NULL selects it again.  Host-only: nothing is enqueued and nothing is waited for.  Work is ordered only
+ * WITHIN the handle's current stream: the handle's workspace, staging buffers and stores (safe set, regression tables, fleet rings,
+ * filter, controllers) are shared by all of its calls, whatever stream each was issued on, so a caller who moves a handle to another
+ * stream while work of the old one may still run orders the two streams itself (an event, or a wait of one stream on the other) --
+ * the handle keeps no state tied to a stream and inserts no dependency of its own.  For streams that run CONCURRENTLY use one handle
+ * per stream, as bench.py does. */
 int lmpc_set_stream(lmpc_handle* h, void* hip_stream);
-/* Block until everything queued on the handle's stream has finished. */
+/* Block until everything queued on the handle's stream has finished (synchronises the handle's stream). */
 int lmpc_synchronize(lmpc_handle* h);
 
 /* discrete_dynamics_jacobian for every stage of every problem
@@ -308,7 +326,8 @@ int lmpc_solve_batch_f32(lmpc_handle* h, int32_t batch, const float* x_ic, const
 /* RacingMPC::solve for ONE problem with HOST pointers in the reference's own (CasADi DM,
  * column-major) layout: X_ref is 6 x N with a knot's state contiguous, U_ref 2 x (N-1), the
  * per-knot rows are plain arrays.  Stages the data through buffers owned by the handle, runs
- * lmpc_solve_batch with batch = 1 and waits.  This is what the C++ facade (RacingMPC class,
+ * lmpc_solve_batch with batch = 1 and waits.  lmpc_solve_host synchronises the handle's stream, as do the other single-problem host
+ * entry points below, lmpc_solve_host_warm, lmpc_solve_host_warm_ss and lmpc_solve_full_dynamics_host.  This is what the C++ facade (RacingMPC class,
  * racing-lmpc-ros2_amd/host/) calls.  ss_x is 6 x S column-major, ss_j has S entries
  * (learning only; NULL otherwise); convex_combi_optm may be NULL. */
 int lmpc_solve_host(lmpc_handle* h, const double* x_ic, const double* u_ic, const double* X_ref,
@@ -349,7 +368,7 @@ int lmpc_solve_host_warm_ss(lmpc_handle* h, const double* x_ic, const double* u_
  * never took a step -- its first QP failed -- returns the start unchanged (dU = 0, lambda = 0) with sqp_iters = 1, that QP's
  * status, sqp_move = +inf (never <= step_tol) and defect = 0: no defect is evaluated for it.  A learning handle needs ss_x and
  * ss_j (LMPC_ERR_ARGUMENT otherwise, before anything is written).  The first call for a batch size allocates a work area (like
- * lmpc_reserve); synchronises the stream once per QP (it has to know whether any problem is still moving). */
+ * lmpc_reserve).  Blocking: it synchronises the handle's stream once per QP (it has to know whether any problem is still moving). */
 int lmpc_solve_full_dynamics_batch(lmpc_handle* h, int32_t batch, const double* x_ic, const double* u_ic, const double* X_ref,
                                    const double* U_ref, const double* T_ref, const double* bound_left,
                                    const double* bound_right, const double* curvatures, const double* vel_ref,
@@ -371,7 +390,8 @@ int lmpc_solve_full_dynamics_host(lmpc_handle* h, const double* x_ic, const doub
 /* Safe set store: SafeSetManager::add_lap / SSTrajectory::process_lap_data
  * (safe_set.cpp:116-151).  HOST pointers: laps oldest first, lap j has n_pts[j] samples,
  * x is the concatenation of the laps' [n_pts[j]][6] row-major state tables.  The library
- * builds the +-L unrolled copies and the cost-to-go J on the device. */
+ * builds the +-L unrolled copies and the cost-to-go J on the device.  Blocking: synchronises the handle's stream (a query may still
+ * read the old store), frees and allocates, and the upload has finished when it returns. */
 int lmpc_set_safe_set(lmpc_handle* h, int32_t n_laps, const int32_t* n_pts, const double* x,
                       double total_length);
 
@@ -409,7 +429,8 @@ typedef struct lmpc_regression_spec {
 /* HOST pointers, laps concatenated as in lmpc_set_safe_set: x [n][6], u [n][2], k [n] (curvature), t [n] (time
  * stamps) -- the lap_.x/u/k/t of SSTrajectory.  n_laps = 0 or spec = NULL switches the regression off.  While it is
  * on, lmpc_solve_batch applies it between its linearisation and its QP kernel.  With laps it is refused (LMPC_ERR_ARGUMENT)
- * while lmpc_fleet_ss_set_regression is in effect. */
+ * while lmpc_fleet_ss_set_regression is in effect.  Blocking: synchronises the handle's stream before the old tables are freed and
+ * again behind the kernels that build the new ones. */
 int lmpc_set_regression_laps(lmpc_handle* h, int32_t n_laps, const int32_t* n_pts, const double* x, const double* u,
                              const double* k, const double* t, const lmpc_regression_spec* spec);
 
@@ -522,7 +543,8 @@ int lmpc_set_output_layout(lmpc_handle* h, int32_t layout);
 /* Grow the handle's device workspace (stage linearisations, 432 B per stage per problem; the list of a mixed solve's
  * unverified problems; the polish's save area, 10 N - 4 values per problem) so that no later *_batch call with
  * batch <= max_batch allocates.  lmpc_solve_batch_f32 needs none of the fp64 workspace: it grows its own fp32 workspace and
- * the save area on the first call for a batch size. */
+ * the save area on the first call for a batch size.  Blocking when it grows anything: the stream is drained before a buffer it may
+ * still read is released (the same holds for the first *_batch call of a larger batch on a handle that was not reserved). */
 int lmpc_reserve(lmpc_handle* h, int32_t max_batch);
 
 /* Launch order of the QP kernel's workgroups (no counterpart upstream: a scheduling aid for closed-loop batches).  The
@@ -567,7 +589,8 @@ int lmpc_last_solve_precision(const lmpc_handle* h, int32_t* precision);
 
 /* Per-kernel timing for benchmarks: when enabled, lmpc_solve_batch brackets its two launches
  * with HIP events on the handle's stream; lmpc_last_kernel_ms waits for them and returns the
- * durations of the linearisation kernel and of the QP kernel of the most recent call. */
+ * durations of the linearisation kernel and of the QP kernel of the most recent call (blocking: it waits for those events, that is,
+ * for the solve they bracket; lmpc_enable_timing itself is host-only). */
 int lmpc_enable_timing(lmpc_handle* h, int32_t on);
 int lmpc_last_kernel_ms(lmpc_handle* h, float* linearize_ms, float* solve_ms);
 
@@ -587,7 +610,10 @@ int lmpc_last_kernel_ms(lmpc_handle* h, float* linearize_ms, float* solve_ms);
  * Every call names the store's own batch (LMPC_ERR_ARGUMENT otherwise, and without a store).  The store serves the array form of the
  * safe set only: the by-reference codes (lmpc_ss_query_idx_batch, lmpc_solve_batch_ss_idx, lmpc_solve_batch_warm_ss with ss_idx,
  * lmpc_shift_lambda_batch) name rows of the shared store and have no fleet form.  The error-dynamics regression has one:
- * lmpc_fleet_ss_set_regression / lmpc_fleet_ss_regress_batch below (lmpc_set_regression_laps stays one store per handle). */
+ * lmpc_fleet_ss_set_regression / lmpc_fleet_ss_regress_batch below (lmpc_set_regression_laps stays one store per handle).
+ * lmpc_fleet_ss_create and lmpc_fleet_ss_destroy are blocking: an existing store is released only after the handle's stream has been
+ * waited for (destroy synchronises the handle's stream), and they allocate / free; the zero-fill of a new store is enqueued on the
+ * handle's stream.  lmpc_fleet_ss_bytes is host-only. */
 int lmpc_fleet_ss_create(lmpc_handle* h, int32_t batch, int32_t max_pts_per_lap);
 int lmpc_fleet_ss_destroy(lmpc_handle* h);
 int lmpc_fleet_ss_reset(lmpc_handle* h);
@@ -824,10 +850,10 @@ typedef struct lmpc_ekf_config {
 #define LMPC_EKF_FLAG_FALLBACK 1   /* NaN / Inf in this car's z or R: it took the pure prediction */
 #define LMPC_EKF_FLAG_R_REPAIRED 2 /* check_cov changed the kernel's copy of this car's R         */
 #define LMPC_EKF_FLAG_NOT_FINITE 4 /* this car's new estimate or covariance is not finite         */
-int lmpc_ekf_create(lmpc_handle* h, int32_t batch, const lmpc_ekf_config* cfg); /* replaces an earlier filter */
-int lmpc_ekf_destroy(lmpc_handle* h);                                           /* lmpc_destroy does it too   */
+int lmpc_ekf_create(lmpc_handle* h, int32_t batch, const lmpc_ekf_config* cfg); /* replaces an earlier filter; blocking (allocates) */
+int lmpc_ekf_destroy(lmpc_handle* h);                                           /* waits for the handle's stream.  lmpc_destroy does it too */
 int lmpc_ekf_register_observation(lmpc_handle* h, int32_t nz, const int32_t* rows /* HOST [nz] */, int32_t* obs_id);
-int lmpc_ekf_initialize(lmpc_handle* h, int64_t timestamp_ns);
+int lmpc_ekf_initialize(lmpc_handle* h, int64_t timestamp_ns); /* host-only: the time of the last update is a host value of the handle */
 int lmpc_ekf_set_state(lmpc_handle* h, int32_t batch, const double* x /* [6][B] or NULL */, const double* P /* [36][B] or NULL */);
 int lmpc_ekf_update_control(lmpc_handle* h, int32_t batch, const double* u /* [2][B] */);
 /* z [nz][B], R [nz][nz][B] (both ignored with obs_id = -1); x_out [6][B], P_out [36][B], Kz_out [6][nz][B] (not written with
@@ -869,7 +895,7 @@ typedef struct lmpc_lqr_config {
 } lmpc_lqr_config;
 #define LMPC_LQR_FLAG_NOT_FINITE 1 /* this car's X_optm, U_optm, K or P0 holds a NaN or Inf */
 int lmpc_lqr_create(lmpc_handle* h, int32_t max_batch, const lmpc_lqr_config* cfg); /* allocates the workspace; replaces an earlier one */
-int lmpc_lqr_destroy(lmpc_handle* h);                                               /* lmpc_destroy does it too */
+int lmpc_lqr_destroy(lmpc_handle* h);                                               /* waits for the handle's stream.  lmpc_destroy does it too */
 int lmpc_lqr_solve_batch(lmpc_handle* h, int32_t batch, const double* x_ic /* [6][B] */, const double* X_ref /* [6][N][B] */,
                          const double* U_ref /* [2][N-1][B] */, double* X_optm /* [6][N][B] */, double* U_optm /* [2][N-1][B] */,
                          double* K /* [2][6][N-1][B] or NULL */, double* P0 /* [36][B] or NULL */, int32_t* flags /* [B] or NULL */);
@@ -920,8 +946,8 @@ typedef struct lmpc_vanilla_config {
 #define LMPC_VANILLA_FLAG_NOT_FINITE 1 /* this car's u_out holds a NaN or Inf (rollout: or its state after the plant does) */
 #define LMPC_VANILLA_LAPS_MAX 1e9      /* |s| > LMPC_VANILLA_LAPS_MAX L: u_out is NaN */
 int lmpc_vanilla_create(lmpc_handle* h, int32_t batch, const lmpc_vanilla_config* cfg); /* per-car PID state, zeroed; replaces an earlier one */
-int lmpc_vanilla_destroy(lmpc_handle* h);                                               /* lmpc_destroy does it too */
-int lmpc_vanilla_reset(lmpc_handle* h, int32_t batch, const double* integral /* [B] or NULL: 0 */); /* error and last_error <- 0 */
+int lmpc_vanilla_destroy(lmpc_handle* h);                                               /* waits for the handle's stream.  lmpc_destroy does it too */
+int lmpc_vanilla_reset(lmpc_handle* h, int32_t batch, const double* integral /* [B] or NULL: 0 */); /* error and last_error <- 0; asynchronous */
 int lmpc_vanilla_get(lmpc_handle* h, int32_t batch, double* integral, double* error, double* last_error); /* DEVICE [B], any NULL */
 int lmpc_vanilla_solve_batch(lmpc_handle* h, int32_t batch, const lmpc_spline_track* track, const double* x_ic /* [6][B] */,
                              const double* vel_ref /* [B] or NULL */, double speed_scale, double* u_out /* [3][B] */,
