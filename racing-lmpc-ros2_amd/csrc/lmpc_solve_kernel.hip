@@ -940,19 +940,38 @@ struct PolishResult {
 #endif
 };
 
-// ---- the team that runs the polish's row phases ----
-// lmpc_polish below is ONE body for one wave per problem and for two (lmpc_solve_w2.hip.h).  A team states what differs between the
-// two, and nothing else -- none of it is arithmetic on a row:
+// ---- the team that runs the row phases of the interior point and of the polish ----
+// lmpc_solve_problem and lmpc_polish below are each ONE body for one wave per problem and for two (lmpc_solve_w2.hip.h).  A team states
+// what differs between the two, and nothing else -- none of it is arithmetic on a row:
 //   THREADS, tid, lane    who owns the rows: a row loop is `for (e = tid; e < n; e += THREADS)`; lane is the lane within the wave, which
 //                         deals the slots and is what the stage chains are written in
 //   CHAIN                 whether this wave runs the stage chains; after_chain() is what shows the team a chain's results
-//   OPAQUE                whether a slot's table integers are read through an empty asm (table(); lmpc_solve_problem_w2 has the account)
-//   LEAN, FORM, PRIO      the layout, the form of its stage chains and Lds::chain_prio: of the kernel's class (the one-wave KQ), not of
-//                         the slots per lane the polish is instantiated with
+//   SLOT0                 the first slot of this wave: slot j = SLOT0 + lane + 64 q
+//   OPAQUE                whether a slot's table integers are read through an empty asm wherever a body reads one by itself (table();
+//                         lmpc_solve_problem's SlotRef has the account)
+//   CLASS, LEAN, FORM, PRIO   the kernel's class (the one-wave KQ, which bounds the horizon), its layout, the form of its stage chains and
+//                         Lds::chain_prio: not of the slots per lane a body is instantiated with
 //   attach(tail)          where the team exchanges, once the LDS block is known (the team itself is made first: the lane is read first)
 //   sync()                the exchange of LDS content inside the team (the simplex blocks, one wave's, keep their wave_fence)
 //   published()           behind an exchange that has to have published the LDS writes before it: two waves' exchange had a barrier
-//   and one operation per exchange point of the body, each of them what the body did there before it had a team:
+//   what the interior point alone asks (policies of the class, lmpc_solve_layout.hip.h, that the body once computed from its KQ):
+//   LEARN                 whether the load honours P.learning
+//   ROW_CHUNK             slots a row phase takes in one go (lmpc_row_chunk; two waves: all of a lane's)
+//   OPAQUE_SLOTS, SITES   whether the row phases' SlotRef passes through the empty asm (lmpc_opaque_slots), and where it does otherwise
+//                         (lmpc_opaque_sites)
+//   FUSE                  the predictor's backward sweep inside the factorisation (lmpc_fuse_bwd)
+//   NBHD                  whether the class has the wide-neighbourhood rule (fp64, KQ <= 7 of the CLASS)
+//   POLISH_CALL, polish_call(a)   whether the polish is a call, and the call
+//   uniform(x)            a scalar the team has agreed on, where the iteration carries it on: one wave moves it to scalar registers (uni),
+//                         two waves leave it where it is -- their exchange has already done so, and uni is opaque to the optimiser
+//   publish(next)         after the primal update: publishes it, unless an exchange follows (`next`) whose barrier does
+//   after_polish()        what brings the team together again behind a polish attempt
+//   sum2(v), max(x), min(x), all(p)   the team's sums of two values at once, maximum, minimum, and whether p holds on every lane
+//   exchanged(x), sum_of(x)   the sacc sum in two steps, as step_end / max_of in the polish: two waves exchange once ahead of the pass's two
+//                         arms and sum_of answers from it, one wave does nothing there and reduces in the arm that reads it
+//   ROUNDED_CSIG          whether the rows phase forms the coupling cell's address in o_csig(q), which keeps `thd - thu` a rounded difference
+//                         (the store has the account: it is about the bits the two-wave kernels have always returned, not about tables)
+//   and one operation per exchange point of the bodies, each of them what the body did there before it had a team:
 //   weights_sum(q, x)     q + the team's sum of x (the weights' eysum)
 //   sum3(v)               three sums at once (the Schur step)
 //   step_end(step, nan)   the end of a multiplier step: the largest step, and whether any lane's step was not finite
@@ -970,13 +989,20 @@ struct PolishResult {
 // the lane after N (scratch/isa_diff.py).
 enum PolishSlot { PS_STEP = 0, PS_NAN = 1, PK_BAD = 0, PK_NEG = 1, PK_WEAK = 2, PK_VIOL = 3, PK_YMIN = 4, PK_WORST = 5 };
 
+template <typename real, int KQ, int KS, typename io, bool SECOND = false>
+__device__ PolishResult<real, KS> lmpc_polish_call(const PolishArgs<real, KQ, KS> a);  // (behind the polish)
+
 template <int REAL_BYTES, int KQ, int KS, bool SECOND>
 struct Wave1 {
-  static constexpr int THREADS = 64;
-  static constexpr bool CHAIN = true, OPAQUE = false;
+  static constexpr int THREADS = 64, SLOT0 = 0, CLASS = KQ;
+  static constexpr bool CHAIN = true, OPAQUE = false, ROUNDED_CSIG = false;
   static constexpr bool LEAN = lmpc_lean(REAL_BYTES, KQ);
-  static constexpr ChainForm FORM = lmpc_chain_form(LEAN, lmpc_chain_addr(REAL_BYTES, KQ, KS));  // as in the iteration
+  static constexpr ChainForm FORM = lmpc_chain_form(LEAN, lmpc_chain_addr(REAL_BYTES, KQ, KS));
   static constexpr bool PRIO = !SECOND && lmpc_waves_per_simd(REAL_BYTES, KQ, KS) >= 2;
+  static constexpr bool LEARN = true;
+  static constexpr int ROW_CHUNK = lmpc_row_chunk(REAL_BYTES, KQ, KS), SITES = lmpc_opaque_sites(REAL_BYTES, KQ, KS);
+  static constexpr bool OPAQUE_SLOTS = lmpc_opaque_slots(REAL_BYTES, KQ, KS), FUSE = lmpc_fuse_bwd(REAL_BYTES, KQ, KS);
+  static constexpr bool NBHD = REAL_BYTES == 8 && KQ <= 7, POLISH_CALL = lmpc_polish_is_call(REAL_BYTES, KQ, KS);
   const int tid, lane;
   __device__ __forceinline__ Wave1() : tid(threadIdx.x), lane(threadIdx.x) {}
   template <typename real>
@@ -985,6 +1011,23 @@ struct Wave1 {
   __device__ static __forceinline__ void sync() { wave_sync(); }
   __device__ static __forceinline__ void published() { wave_sync(); }
   __device__ static __forceinline__ void after_chain() {}
+  template <typename real>
+  __device__ static __forceinline__ real uniform(real x) { return uni(x); }
+  template <typename real>
+  __device__ static __forceinline__ real exchanged(real x) { return x; }
+  template <typename real>
+  __device__ static __forceinline__ real sum_of(real x) { return wave_sum(x); }
+  __device__ static __forceinline__ void publish(bool) { wave_sync(); }
+  __device__ static __forceinline__ void after_polish() {}
+  template <typename real, typename io>  // (the function itself, not a wrapper of it: what crosses the call stays by value as the caller wrote it)
+  static constexpr PolishResult<real, KS> (*polish_call)(const PolishArgs<real, KQ, KS>) = &lmpc_polish_call<real, KQ, KS, io, SECOND>;
+  template <typename real>
+  __device__ static __forceinline__ void sum2(real (&v)[2]) { wave_sum_n<2>(v); }
+  template <typename real>
+  __device__ static __forceinline__ real max(real x) { return wave_max(x); }
+  template <typename real>
+  __device__ static __forceinline__ real min(real x) { return wave_min(x); }
+  __device__ static __forceinline__ bool all(bool p) { return wave_min(p ? 1.0 : 0.0) > 0.5; }
   template <typename real>
   __device__ static __forceinline__ real weights_sum(real q, real x) { return uni(q + wave_sum(x)); }
   template <typename real>
@@ -1574,7 +1617,7 @@ __device__ __forceinline__ PolishResult<real, KS> lmpc_polish(const PolishArgs<r
   return res;
 }
 
-template <typename real, int KQ, int KS, typename io, bool SECOND = false>
+template <typename real, int KQ, int KS, typename io, bool SECOND>
 __device__ __attribute__((noinline)) PolishResult<real, KS> lmpc_polish_call(const PolishArgs<real, KQ, KS> a) {
   return lmpc_polish<real, KQ, KS, io, Wave1<sizeof(real), KQ, KS, SECOND>>(a);
 }
@@ -1582,11 +1625,14 @@ __device__ __attribute__((noinline)) PolishResult<real, KS> lmpc_polish_call(con
 // `real` is the arithmetic and LDS type, `io` the type of the arrays in HBM: <double, double> is the reference's
 // precision, <float, float> the single-precision path, <float, double> the mixed path (fp64 linearisation, regression,
 // safe-set centring and results around an fp32 interior-point iteration).
-// One problem, solved by the calling wavefront in the LDS block it is given (the body of both kernels below).
+// One problem, solved by the calling team in the LDS block it is given: the body of every solve kernel, the one-wave kernels below
+// (TEAM = Wave1) and the two-wave kernel of lmpc_solve_w2.hip.h (TEAM = Wave2: each of its waves runs this body on its half of the slots).
+// KQ: slots per lane (one wave: the class's; two waves: lmpc_w2_slots of it, and the class is the team's).
 
 // SECOND: the fp64 second pass of a mixed solve -- a handful of problems a whole batch waits for, sharing the chip with the next batch's
 // first pass: its waves run at the top issue priority throughout (and do not drop it between chains).
-template <typename real, int KQ, int KS, typename io, bool SECOND = false, bool WARMK = false>  // (WARMK: the warm-start kernels, below)
+template <typename real, int KQ, int KS, typename io, bool SECOND = false, bool WARMK = false,  // (WARMK: the warm-start kernels, below)
+          class TEAM = Wave1<sizeof(real), KQ, KS, SECOND>>
 __device__ __forceinline__ void lmpc_solve_problem(
     const lmpc_params& P, const int B, const int b, unsigned char* lds_raw, const io* __restrict__ ws_lin,
     const io* __restrict__ x_ic, const io* __restrict__ u_ic, const io* __restrict__ T_ref, const io* __restrict__ bl,
@@ -1594,8 +1640,11 @@ __device__ __forceinline__ void lmpc_solve_problem(
     const io* __restrict__ ss_j, io* __restrict__ lam_out, io* __restrict__ X_out,
     io* __restrict__ U_out, io* __restrict__ dU_out, int* __restrict__ status_out,
     int* __restrict__ iters_out, io* __restrict__ kkt_out) {
+  static_assert(TEAM::THREADS == 64 || (KS == 0 && !WARMK && !SECOND && std::is_same<real, double>::value && std::is_same<io, double>::value),
+                "the simplex rows, the warm start, the second pass and single precision are one wave's");
   real* const lds = reinterpret_cast<real*>(lds_raw);
-  const int lane = threadIdx.x;
+  TEAM tm;
+  const int tid = tm.tid, lane = tm.lane;
   const int N = P.N, NS = N - 1;
   typedef typename vec2<real>::type real2;
   typedef double treal;  // the safe-set block (simplex rows, terminal elimination) is always carried in fp64
@@ -1603,23 +1652,25 @@ __device__ __forceinline__ void lmpc_solve_problem(
   const real inf = real(INFINITY), marg = real(P.marg), qsig = real(P.qsig), tol = lim::tol(P.tol);
   // single precision carries the abscissa relative to x_ic[0] (the QP is invariant to the shift: A(:, s) = e_s)
   const io s_shift = sizeof(real) == 4 ? x_ic[b] : io(0);
-  constexpr bool LEAN = lmpc_lean(sizeof(real), KQ);
+  constexpr bool LEAN = TEAM::LEAN;
   // slots a row phase loads, computes and stores in one go: all of them where the registers hold the temporaries of all KQ at
   // once; LMPC_ROW_CHUNK at a time in the long-horizon kernels (KQ >= 11: 11-14 slots x 7 operands on top of 12 doubles of row
   // state per slot do not fit 512 registers, and what the allocator spills is the row state)
-  constexpr int QC = lmpc_row_chunk(sizeof(real), KQ, KS);
-  constexpr int SITES = lmpc_opaque_sites(sizeof(real), KQ, KS);
+  constexpr int QC = TEAM::ROW_CHUNK;
+  constexpr int SITES = TEAM::SITES;
   // the predictor's backward sweep inside the factorisation (riccati_factor<.., FUSE>): the barrier weights then go to the rhs1 cells
   // and the predictor's gradient is assembled ahead of the factorisation.  Problems without the shared slack have one right-hand
   // side and keep the five-chain iteration (no shipped configuration: q_boundary > 0 everywhere).
   // (the warm-start kernels too: their cold path is this iteration -- except at two waves per SIMD, where the fused iteration is only
   //  trusted with the polish behind a call, lmpc_fuse_bwd's comment, and the warm kernels keep theirs inline)
-  constexpr bool FUSEK = lmpc_fuse_bwd(sizeof(real), KQ, KS) && !(WARMK && lmpc_waves_per_simd(sizeof(real), KQ, KS) >= 2);
-  constexpr ChainForm FORM = lmpc_chain_form(LEAN, lmpc_chain_addr(sizeof(real), KQ, KS));  // of the stage chains (lmpc_solve_layout.hip.h)
+  constexpr bool WARM_INLINE = WARMK && lmpc_waves_per_simd(sizeof(real), KQ, KS) >= 2;
+  constexpr bool FUSEK = TEAM::FUSE && !WARM_INLINE;
+  constexpr ChainForm FORM = TEAM::FORM;  // of the stage chains (lmpc_solve_layout.hip.h)
   const bool fuse = FUSEK && P.has_sigma != 0;
-  Lds<real> L{lds, N, LEAN ? LMPC_LEAN_STAGE_STRIDE : LMPC_STAGE_STRIDE, !SECOND && lmpc_waves_per_simd(sizeof(real), KQ, KS) >= 2};
+  Lds<real> L{lds, N, LEAN ? LMPC_LEAN_STAGE_STRIDE : LMPC_STAGE_STRIDE, TEAM::PRIO};
   if constexpr (SECOND && LMPC_CHAIN_PRIO) __builtin_amdgcn_s_setprio(3);
   real* T = L.tail();
+  tm.attach(T);
   real* ct = T + TL_CT;
   real* KN0 = L.kn(0);
   // terminal region (learning only): treal cells behind the records; 16-byte aligned because every record size is even
@@ -1636,13 +1687,13 @@ __device__ __forceinline__ void lmpc_solve_problem(
 
   // ---------------- load: linearisation records, per-knot data, constant tables ----------------
   // (lmpc_solve_setup.hip.h: every load of the phase in one flight -- two at KQ = 7, more for the longer single-precision records)
-  lmpc_load_problem<real, io, 64, KQ, LEAN, true>(
-      P, B, b, lane, L, ws_lin, x_ic, u_ic, T_ref, bl, br, vref, s_shift);
-  wave_sync();
+  lmpc_load_problem<real, io, TEAM::THREADS, TEAM::CLASS, LEAN, TEAM::LEARN>(
+      P, B, b, tid, L, ws_lin, x_ic, u_ic, T_ref, bl, br, vref, s_shift);
+  tm.sync();
   PT_MARK(0)
 
   // ---------------- slot ownership ----------------
-  // slot j = lane + 64 q  ->  knot i = j / 11, kind sl = j % 11.  Kinds 0..9 constrain the primal
+  // slot j = SLOT0 + lane + 64 q (SLOT0: the first slot of this wave)  ->  knot i = j / 11, kind sl = j % 11.  Kinds 0..9 constrain the primal
   // component (z[0..7], v[0..1]) at offset sl of the knot record; kind 10 is the track boundary
   // row pair on e_y (offset 1) which also carries the shared slack sigma.  Everything a slot needs
   // is reduced to LDS offsets and flag bits here so that the per-iteration row code is branch-free
@@ -1662,7 +1713,7 @@ __device__ __forceinline__ void lmpc_solve_problem(
   real m_rows = 0.0;
 #pragma unroll
   for (int q = 0; q < KQ; ++q) {
-    const int j = lane + 64 * q;
+    const int j = TEAM::SLOT0 + lane + 64 * q;
     const bool valid = j < NSLOT * N;
     const int i = valid ? j / NSLOT : 0;
     const int sl = valid ? j - i * NSLOT : 0;
@@ -1706,20 +1757,22 @@ __device__ __forceinline__ void lmpc_solve_problem(
     s_pu[q] = s_pl[q] = 0.0;
   }
   // cell next to a boundary slot's weight that takes the sigma coupling coefficient (dead cell otherwise)
-  auto flags = [&](int q) { return s_gf[q] >> 20; };
+  // (a table integer read by itself goes through the team's table(): the empty asm below where the team's tables are opaque)
+  auto flags = [&](int q) { return TEAM::table(s_gf[q]) >> 20; };
   // where the slot writes its barrier weight / gradient entry: the rhs0 cell of its component, or the boundary cell
-  auto o_w = [&](int q) { return o_val[q] + ((flags(q) & F_EY) ? KN_EY - 1 : KN_R0); };
-  auto o_csig = [&](int q) { return (flags(q) & F_EY) ? o_val[q] + (KN_CSIG - 1) : JB + KN_CSIG; };
-  auto bounds = [&](int q) { return *reinterpret_cast<const real2*>(&lds[o_hl[q]]); };
+  auto o_w = [&](int q) { return TEAM::table(o_val[q]) + ((flags(q) & F_EY) ? KN_EY - 1 : KN_R0); };
+  auto o_csig = [&](int q) { return (flags(q) & F_EY) ? TEAM::table(o_val[q]) + (KN_CSIG - 1) : JB + KN_CSIG; };
+  auto bounds = [&](int q) { return *reinterpret_cast<const real2*>(&lds[TEAM::table(o_hl[q])]); };
   // The slot's three table entries as the row phases of the iteration read them.  Where lmpc_opaque_slots says so they pass
   // through an empty asm first: every LDS address of a slot is loop-invariant, so the optimiser hoists all of them out of the
   // iteration -- eight addresses per slot where the tables hold three integers --, the allocator spills them, and each use then
   // waits on its own scratch reload (`scratch_load_dword; s_waitcnt vmcnt(0); ds_read`: a gradient evaluation at KQ = 11 was ~60 of
   // those in a row).  Behind the asm the addresses are recomputed from the tables with a handful of integer instructions.
+  // (the two-wave kernels likewise: without it their gradient took 53 k cycles per iteration at N = 60 against 23 k in the one-wave kernel)
   struct SlotRef { int ov, oh, gf; };
   auto slot = [&](int q) {
     SlotRef r{o_val[q], o_hl[q], s_gf[q]};
-    if constexpr (lmpc_opaque_slots(sizeof(real), KQ, KS)) asm volatile("" : "+v"(r.ov), "+v"(r.oh), "+v"(r.gf));
+    if constexpr (TEAM::OPAQUE_SLOTS) asm volatile("" : "+v"(r.ov), "+v"(r.oh), "+v"(r.gf));
     return r;
   };
   // (the short-horizon tracking kernels keep the hoisted addresses -- the opaque tables cost them 1-3 % -- except at the sites of
@@ -1727,7 +1780,7 @@ __device__ __forceinline__ void lmpc_solve_problem(
   //  the gradient clears, 2 the coupling cell in the Schur sums, 3 the primal update)
   auto slot_at = [&](int q, int site) {
     SlotRef r{o_val[q], o_hl[q], s_gf[q]};
-    if constexpr (lmpc_opaque_slots(sizeof(real), KQ, KS)) {
+    if constexpr (TEAM::OPAQUE_SLOTS) {
       asm volatile("" : "+v"(r.ov), "+v"(r.oh), "+v"(r.gf));
     } else if ((SITES >> site) & 1) {
       asm volatile("" : "+v"(r.gf));
@@ -1850,22 +1903,22 @@ __device__ __forceinline__ void lmpc_solve_problem(
     sx.tau = uni(treal(TAU_REL) * wave_max(umax));
     sx.m = 0;
   }
-  const real m_tot = wave_sum(m_rows);
-  const real inv_m = uni(real(1) / m_tot);
+  const real m_tot = tm.sum(m_rows);
+  const real inv_m = TEAM::uniform(real(1) / m_tot);
 
   // knot-0 feasibility: the state box applies to x_0 = x_ic (racing_mpc.cpp:147,201)
   bool feasible = true;
   {
     bool ok = true;
-    if (lane < 6) {
-      const real v = KN0[lane];
-      ok = (v <= ct[CT_HL + 2 * lane]) && (v >= ct[CT_HL + 2 * lane + 1]);
+    if (tid < 6) {
+      const real v = KN0[tid];
+      ok = (v <= ct[CT_HL + 2 * tid]) && (v >= ct[CT_HL + 2 * tid + 1]);
     }
-    if (lane == 6 && !has_sigma) {
+    if (tid == 6 && !has_sigma) {
       const real ey = KN0[1];
       ok = (ey <= bl[b] - marg) && (ey >= br[b] + marg);
     }
-    feasible = wave_min(ok ? 1.0 : 0.0) > 0.5;
+    feasible = tm.all(ok);
   }
 
   // The row sigma >= 0 (racing_mpc.cpp:536) is redundant and not carried: replacing a negative sigma by 0 loosens every
@@ -1888,11 +1941,11 @@ __device__ __forceinline__ void lmpc_solve_problem(
   auto put_primal = [&]() {
     const size_t xk = P.out_aos ? 1 : (size_t)N * B, xi = P.out_aos ? 6 : (size_t)B, xb = P.out_aos ? (size_t)6 * N : 1;
     const size_t uk = P.out_aos ? 1 : (size_t)NS * B, ui = P.out_aos ? 2 : (size_t)B, ub = P.out_aos ? (size_t)2 * NS : 1;
-    for (int e = lane; e < 6 * N; e += 64) {
+    for (int e = tid; e < 6 * N; e += TEAM::THREADS) {
       const int k = e / N, i = e - k * N;
       X_out[k * xk + i * xi + b * xb] = io(L.kn(i)[k]) + (k == 0 ? s_shift : io(0));
     }
-    for (int e = lane; e < 2 * NS; e += 64) {
+    for (int e = tid; e < 2 * NS; e += TEAM::THREADS) {
       const int k = e / NS, i = e - k * NS;
       U_out[k * uk + i * ui + b * ub] = io(L.kn(i + 1)[6 + k]);
       dU_out[k * uk + i * ui + b * ub] = io(L.kn(i)[8 + k]);
@@ -1930,10 +1983,11 @@ __device__ __forceinline__ void lmpc_solve_problem(
     PolishResult<real, KS> pr;
     // (the warm-start kernels at two waves per SIMD keep the polish inline: their accepted attempts ARE the polish, and behind a call the
     //  closed loop loses 3 .. 5 %: 6.65 -> 6.43 M car-steps/s at 4096 cars, 12.5 -> 11.9 M at 16384)
-    if constexpr (lmpc_polish_is_call(sizeof(real), KQ, KS) && !(WARMK && lmpc_waves_per_simd(sizeof(real), KQ, KS) >= 2))
-      pr = lmpc_polish_call<real, KQ, KS, io, SECOND>(pa);
+    if constexpr (TEAM::POLISH_CALL && !WARM_INLINE)
+      pr = TEAM::template polish_call<real, io>(pa);
     else
-      pr = lmpc_polish<real, KQ, KS, io, Wave1<sizeof(real), KQ, KS, SECOND>>(pa);
+      pr = lmpc_polish<real, KQ, KS, io, TEAM>(pa);
+    tm.after_polish();
     pol_rounds = uni(pr.pol_rounds);
 #ifdef LMPC_PHASE_TIMING
     if constexpr (KS == 0) {  // (the learning kernels use buckets 13 .. 15 for their terminal block)
@@ -2008,9 +2062,9 @@ __device__ __forceinline__ void lmpc_solve_problem(
     if constexpr (KS > 0) {  // lambda frozen at 1/S: terminal cost eps'D eps only
       if (lane < 36) TT[TL_PT + lane] = (lane % 7 == 0) ? TT[TL_E + lane / 7] : treal(0);
     }
-    wave_sync();
+    tm.sync();
     PT_MARK(1)
-    riccati_factor<FORM, (KS > 0), false>(L, MS, lane, TT + TL_PT);
+    if constexpr (TEAM::CHAIN) riccati_factor<FORM, (KS > 0), false>(L, MS, lane, TT + TL_PT);
     PT_MARK(16)
     if constexpr (WARM_BUILT) {
       if (attempt == 0) {
@@ -2111,7 +2165,8 @@ __device__ __forceinline__ void lmpc_solve_problem(
         continue;
       }
     }
-    feedback_rollout<FORM>(L, MS, lane);
+    if constexpr (TEAM::CHAIN) feedback_rollout<FORM>(L, MS, lane);
+    tm.after_chain();
     PT_MARK(17)
   }
   if constexpr (KS > 0) {
@@ -2215,6 +2270,9 @@ __device__ __forceinline__ void lmpc_solve_problem(
         for (int qq = 0; qq < QC; ++qq) {
           const int q = q0 + qq;
           if (q >= KQ) continue;
+          // (two waves read the slot's tables afresh for the arithmetic, as their text did: the copies of the load loop, kept alive
+          //  across it, cost w2<11> / w2<14> 12 / 20 spilled VGPRs -- profiles/iteration_one_body.md)
+          if constexpr (TEAM::OPAQUE) sr[qq] = slot(q);
           const int f = r_flags(sr[qq]);
           const real sg = (f & F_SIG) ? sigma : 0.0;
           const real itu = frcp(s_tu[q]), itl = frcp(s_tl[q]);
@@ -2225,16 +2283,16 @@ __device__ __forceinline__ void lmpc_solve_problem(
           const real g = ca[qq] * val[qq] + cb[qq] * par[qq] + ((f & F_QLIN) ? ql[qq] : real(0));  // (zero coefficients on a boundary slot)
           lds[r_w(sr[qq])] = g + cu - cd;
           if (pass == 0 && !fused) {
-            const SlotRef sz = ((SITES & 2) && !lmpc_opaque_slots(sizeof(real), KQ, KS)) ? slot_at(q, 1) : sr[qq];
+            const SlotRef sz = ((SITES & 2) && !TEAM::OPAQUE_SLOTS) ? slot_at(q, 1) : sr[qq];
             lds[(r_flags(sz) & F_EY) ? JB + KN_EY : r_w(sz) + 10] = 0.0;
           }
           sgsum += (f & F_SIG) ? (cu + cd) : real(0);
         }
         if constexpr (QC < KQ) ISSUE_ORDER();
       }
-      wave_sync();
+      tm.sync();
       PT_MARK(12)
-      for (int i = lane; i < N; i += 64) {
+      for (int i = tid; i < N; i += TEAM::THREADS) {
         real* kn = L.kn(i);
         kn[KN_R0 + 1] += kn[KN_EY];
         if (pass == 0 && !fused) kn[KN_R1 + 1] = (i >= 1) ? kn[KN_CSIG] : 0.0;
@@ -2243,7 +2301,7 @@ __device__ __forceinline__ void lmpc_solve_problem(
         wave_sync();
         if (lane < 6) L.kn(N - 1)[KN_R0 + lane] += real(TT[TL_TG + lane]);
       }
-      wave_sync();
+      tm.sync();
       return sgsum;
     };
     // ======== rows: complementarity, residual, barrier weights ========
@@ -2266,6 +2324,7 @@ __device__ __forceinline__ void lmpc_solve_problem(
         for (int qq = 0; qq < QC; ++qq) {
           const int q = q0 + qq;
           if (q >= KQ) continue;
+          if constexpr (TEAM::OPAQUE) sr[qq] = slot(q);
           const int f = r_flags(sr[qq]);
           const real sg = (f & F_SIG) ? sigma : 0.0;
           const real thu = s_lu[q] * frcp(s_tu[q]), thd = s_ll[q] * frcp(s_tl[q]);
@@ -2273,7 +2332,14 @@ __device__ __forceinline__ void lmpc_solve_problem(
           rdl = fmax(rdl, (f & F_UP) ? fabs(val[qq] - sg + s_tu[q] - hl[qq].x) : real(0));
           rdl = fmax(rdl, (f & F_LO) ? fabs(-val[qq] - sg + s_tl[q] + hl[qq].y) : real(0));
           lds[r_w(sr[qq]) + (fuse ? ((f & F_EY) ? KN_TEY - KN_EY : KN_R1 - KN_R0) : 0)] = thu + thd;
-          lds[r_csig(((SITES & 1) && !lmpc_opaque_slots(sizeof(real), KQ, KS)) ? slot_at(q, 0) : sr[qq])] = (f & F_SIG) ? (thd - thu) : 0.0;
+          // (NOT a simplification to make: where this address is formed decides the bits.  With the address taken from sr[] the
+          //  difference below sits in the block of its two products and is fused with one of them, v_fma_f64 thd, -thu unrounded;
+          //  o_csig(q) has an empty asm in one arm of its conditional, which keeps control flow between them, and the two-wave kernels
+          //  have always computed the rounded difference -- profiles/iteration_one_body.md, section 2)
+          if constexpr (TEAM::ROUNDED_CSIG)
+            lds[o_csig(q)] = (f & F_SIG) ? (thd - thu) : 0.0;
+          else
+            lds[r_csig(((SITES & 1) && !TEAM::OPAQUE_SLOTS) ? slot_at(q, 0) : sr[qq])] = (f & F_SIG) ? (thd - thu) : 0.0;
           eysum += (f & F_SIG) ? (thu + thd) : real(0);
         }
         if constexpr (QC < KQ) ISSUE_ORDER();
@@ -2393,13 +2459,13 @@ __device__ __forceinline__ void lmpc_solve_problem(
       }
       {
         real red[2] = {musum, eysum};
-        wave_sum_n<2>(red);
+        tm.sum2(red);
         musum = red[0];
         hsig = qsig + red[1];
       }
-      rdmax = wave_max(rdl);
-      hsig = uni(hsig);
-      mu = uni(musum * inv_m);
+      rdmax = tm.max(rdl);  // (two waves: the two barriers above also publish the barrier weights for the factorisation)
+      hsig = TEAM::uniform(hsig);
+      mu = TEAM::uniform(musum * inv_m);
       // (see the step-length rule; far from feasibility mu may rise legitimately: IAC at 60 m/s into a corner)
       // (reentry: the same iterate a second time -- after a refused polish, or on the way to the final one: none of the
       // bookkeeping repeats)
@@ -2443,7 +2509,7 @@ __device__ __forceinline__ void lmpc_solve_problem(
           break;
         }
       }
-      wave_sync();
+      tm.published();
       PT_MARK(2)
       if constexpr (FUSEK) {
         if (fuse) {
@@ -2452,17 +2518,20 @@ __device__ __forceinline__ void lmpc_solve_problem(
           PT_MARK(4)
         }
       }
-      if (sizeof(real) == 8 && mu <= real(JOSEPH_MU)) {  // (single precision stops at mu ~ 2e-6)
-        if (FUSEK && fuse)
-          riccati_factor<FORM, (KS > 0), (sizeof(real) == 8), FUSEK>(L, MS, lane, TT + TL_PT, KN_R1, KN_TEY);
-        else
-          riccati_factor<FORM, (KS > 0), (sizeof(real) == 8)>(L, MS, lane, TT + TL_PT);
-      } else {
-        if (FUSEK && fuse)
-          riccati_factor<FORM, (KS > 0), false, FUSEK>(L, MS, lane, TT + TL_PT, KN_R1, KN_TEY);
-        else
-          riccati_factor<FORM, (KS > 0), false>(L, MS, lane, TT + TL_PT);
+      if constexpr (TEAM::CHAIN) {
+        if (sizeof(real) == 8 && mu <= real(JOSEPH_MU)) {  // (single precision stops at mu ~ 2e-6)
+          if (FUSEK && fuse)
+            riccati_factor<FORM, (KS > 0), (sizeof(real) == 8), FUSEK>(L, MS, lane, TT + TL_PT, KN_R1, KN_TEY);
+          else
+            riccati_factor<FORM, (KS > 0), (sizeof(real) == 8)>(L, MS, lane, TT + TL_PT);
+        } else {
+          if (FUSEK && fuse)
+            riccati_factor<FORM, (KS > 0), false, FUSEK>(L, MS, lane, TT + TL_PT, KN_R1, KN_TEY);
+          else
+            riccati_factor<FORM, (KS > 0), false>(L, MS, lane, TT + TL_PT);
+        }
       }
+      tm.after_chain();
       PT_MARK(3)
     }
 
@@ -2479,13 +2548,16 @@ __device__ __forceinline__ void lmpc_solve_problem(
         PT_MARK(4)
       }
       // ======== Newton step: predictor together with the Schur vector, then the corrector ========
-      if (pass == 0 && ipm && has_sigma) {
-        if (FUSEK && fuse)
-          riccati_solve<FORM, 2, FUSEK>(L, MS, lane, pf);
-        else
-          riccati_solve<FORM, 2>(L, MS, lane, pf);
-      } else
-        riccati_solve<FORM, 1>(L, MS, lane, pf);
+      if constexpr (TEAM::CHAIN) {
+        if (pass == 0 && ipm && has_sigma) {
+          if (FUSEK && fuse)
+            riccati_solve<FORM, 2, FUSEK>(L, MS, lane, pf);
+          else
+            riccati_solve<FORM, 2>(L, MS, lane, pf);
+        } else
+          riccati_solve<FORM, 1>(L, MS, lane, pf);
+      }
+      tm.after_chain();
       PT_MARK(5)
       // ======== step of every constrained value; boundary slack by Schur complement ========
       // (QC == KQ: the steps and values are loaded once, here, and stay in registers across the reduction; otherwise chunk-wise,
@@ -2495,9 +2567,9 @@ __device__ __forceinline__ void lmpc_solve_problem(
       if constexpr (QC == KQ) {
 #pragma unroll
         for (int q = 0; q < KQ; ++q) {
-          dz0[q] = lds[o_val[q] + 10];
-          dz1[q] = lds[o_val[q] + 20];
-          val[q] = lds[o_val[q]];
+          dz0[q] = lds[TEAM::table(o_val[q]) + 10];
+          dz1[q] = lds[TEAM::table(o_val[q]) + 20];
+          val[q] = lds[TEAM::table(o_val[q])];
           hl[q] = bounds(q);
         }
       }
@@ -2543,7 +2615,7 @@ __device__ __forceinline__ void lmpc_solve_problem(
             ISSUE_ORDER();
           }
         }
-        wave_sum_n<3>(red);
+        tm.sum3(red);
         if (pass == 0) ce = red[1];
         const real qsg = qsig * sigma - red[2];
         dsigma = uni(-(qsg + red[0]) / (hsig + ce));
@@ -2621,6 +2693,7 @@ __device__ __forceinline__ void lmpc_solve_problem(
         for (int qq = 0; qq < QC; ++qq) {
           const int q = q0 + qq;
           if (q >= KQ) continue;
+          if constexpr (TEAM::OPAQUE) sr[qq] = slot(q);
           const int f = r_flags(sr[qq]);
           const real dval = e0[qq] + dsigma * e1[qq];
           d_val[q] = dval;
@@ -2648,17 +2721,17 @@ __device__ __forceinline__ void lmpc_solve_problem(
           rmax = fmax(rmax, real(fmax(-dt_ * it_, -dl_ * frcp(fmax(sx.l[q], treal(1e-300))))));
         }
       }
-      rmax = wave_max(finite_step ? rmax : inf);
+      rmax = tm.max(finite_step ? rmax : inf);
       if (!(rmax < inf) || !(dsigma == dsigma)) {
         // a Newton step that is not a number (the Schur complement of sigma or the 2x2 H cancelled completely -- in
         // practice single precision on its last iteration): keep the iterate, report it by what it has reached
         numerics_failed = true;
         break;
       }
-      const real amax = uni(real(1) / rmax);
+      const real amax = TEAM::uniform(real(1) / rmax);
       if (pass == 1) {
-        alpha = uni(fmin(real(1), tau * amax));
-        if (sizeof(real) == 8 && KQ <= 7 && distress) {  // (fp64 arithmetic, N <= 40: see below)
+        alpha = TEAM::uniform(fmin(real(1), tau * amax));
+        if (TEAM::NBHD && distress) {  // (fp64 arithmetic, N <= 40 -- KQ <= 7 of the class: see below)
           // A problem whose complementarity has gone UP once gets the wide-neighbourhood rule from then on: the step is
           // cut back until no complementarity product falls below NBHD_GAMMA times their mean.  Mehrotra's iteration can
           // otherwise leave the neighbourhood of the central path and cycle -- seen on a learning problem whose safe set
@@ -2688,8 +2761,9 @@ __device__ __forceinline__ void lmpc_solve_problem(
                 pmin = fmin(pmin, sx.on[q] ? pr : inf);
               }
             }
-            if (wave_min(pmin) >= real(NBHD_GAMMA) * wave_sum(sl) * inv_m) break;
-            alpha = uni(alpha * real(0.6));
+            pmin = tm.min(pmin);  // (a statement of its own: two waves pair their exchanges by order, which C++ leaves open inside an expression)
+            if (pmin >= real(NBHD_GAMMA) * tm.sum(sl) * inv_m) break;
+            alpha = TEAM::uniform(alpha * real(0.6));
           }
         }
       }
@@ -2724,17 +2798,18 @@ __device__ __forceinline__ void lmpc_solve_problem(
           }
         }
       }
+      sacc = tm.exchanged(sacc);  // (two waves: ONE exchange ahead of both arms; one wave reduces where it reads, in the arm)
       if (pass == 1) {
         // no further progress: rows feasible, complementarity already small, and the corrector step would not lower it
         // (the Newton direction has reached the accuracy of the factorisation): keep the current primal iterate
-        sacc = wave_sum(sacc);
+        sacc = tm.sum_of(sacc);
         if (rdmax <= lim::rd_ok && mu <= real(STALL_MU) && sacc * inv_m >= mu) stalled = true;
       }
       if (pass == 0) {
-        sacc = wave_sum(sacc);
+        sacc = tm.sum_of(sacc);
         const real ratio = (sacc * inv_m) / mu;
-        sigc = uni(ratio * ratio * ratio);
-        wave_sync();
+        sigc = TEAM::uniform(ratio * ratio * ratio);
+        tm.published();
       }
     }
 
@@ -2751,8 +2826,8 @@ __device__ __forceinline__ void lmpc_solve_problem(
       //  polish as before, but unless the polish verifies it the status is MAX_ITER: oracle/c/lmpc_oracle.c, STALL_STEP, has the problem)
       real cand = 0.0;  // the step the stall declines to take, in the reference's scaled units (like the polish's steps)
 #pragma unroll
-      for (int q = 0; q < KQ; ++q) cand = fmax(cand, (flags(q) & F_MOVE) ? fabs(alpha * d_val[q]) * real(slot_inv_scale((s_gf[q] >> 27) & 15)) : real(0));
-      stall_moving = sizeof(real) == 8 && wave_max(cand) > real(STALL_STEP);
+      for (int q = 0; q < KQ; ++q) cand = fmax(cand, (flags(q) & F_MOVE) ? fabs(alpha * d_val[q]) * real(slot_inv_scale((TEAM::table(s_gf[q]) >> 27) & 15)) : real(0));
+      stall_moving = sizeof(real) == 8 && tm.max(cand) > real(STALL_STEP);
       status = (stall_moving && !polish_on) ? LMPC_SOLVE_MAX_ITER : LMPC_SOLVE_OPTIMAL;
       hand_over = polish_on ? 2 : 0;
       break;
@@ -2768,10 +2843,10 @@ __device__ __forceinline__ void lmpc_solve_problem(
       lds[mv ? sr.ov : JB + q] += dz;
       stepmax = fmax(stepmax, fabs(dz));
     }
-    wave_sync();
+    tm.publish(ipm);
     if (ipm) {
-      last_step = wave_max(stepmax);
-      if (has_sigma) sigma = uni(sigma + alpha * dsigma);
+      last_step = tm.max(stepmax);
+      if (has_sigma) sigma = TEAM::uniform(sigma + alpha * dsigma);
     } else {
       // ---- slacks and multipliers at the start point: t = max(slack, 0.5 range), lam = mu0 / t ----
       real val[KQ];
@@ -2806,7 +2881,7 @@ __device__ __forceinline__ void lmpc_solve_problem(
     }
   }
   if (hand_over == 0) break;
-  wave_sync();
+  tm.sync();
   if (polish_attempt(pol::rounds | (hand_over >= 2 ? POLISH_EXIT : 0))) {
     polished = true;
     status = LMPC_SOLVE_OPTIMAL;
@@ -2850,7 +2925,7 @@ __device__ __forceinline__ void lmpc_solve_problem(
   if (P.flag_unverified && (status != LMPC_SOLVE_OPTIMAL || (polish_on && !polished))) status = LMPC_SOLVE_UNVERIFIED;
 
   // ---------------- write back: X [6][N][B], U, dU [2][N-1][B] ----------------
-  wave_sync();
+  tm.sync();
   put_primal();
   if constexpr (KS > 0) {
     if (lam_out) {
@@ -2859,7 +2934,7 @@ __device__ __forceinline__ void lmpc_solve_problem(
         if (lane + 64 * q < S) lam_out[(size_t)(lane + 64 * q) * B + b] = sx.on[q] ? io(sx.lm[q]) : io(0);  // (a dropped copy: 0)
     }
   }
-  if (lane == 0) {
+  if (TEAM::CHAIN && lane == 0) {  // (two waves: the chain wave reports, and the clocks of the profiling build are its own)
     status_out[b] = status;
     iters_out[b] = it;
     if constexpr (WARMK) {

@@ -1,6 +1,6 @@
 // lmpc_solve_setup.hip.h -- a solve kernel's load phase: one problem's linearisation records, per-knot data and constant table from
 // global memory into the LDS block, in batched reads.
-// Holds: lmpc_load_problem, shared by the one-wave kernels (lmpc_solve_problem) and the two-wave kernels (lmpc_solve_problem_w2).
+// Holds: lmpc_load_problem, shared by the one-wave and the two-wave kernels (lmpc_solve_problem, under either team).
 // Needs: lmpc_solve_layout.hip.h (Lds, the record offsets) and LN_DT of the lean layout (lmpc_solve_kernel.hip).
 // Included by lmpc_solve_kernel.hip (all three translation units).
 //

@@ -35,7 +35,8 @@ if LMPC:
 if "w1" in sys.argv:
     solver.set_waves_per_problem(1)   # (since round 6 the library takes two waves from N = 41 on by itself)
 if "w2" in sys.argv:
-    solver.set_waves_per_problem(2)   # (round 6: the two-wave kernels; the clock is the chain wave's)
+    solver.set_waves_per_problem(2)   # (round 6: the two-wave kernels; the clock is the chain wave's, and since both kernels run one
+                                      #  lmpc_solve_problem its buckets are numbered as the one-wave kernel's, the polish's own clocks included)
 out = solver.alloc_outputs(B)
 out["kkt"] = torch.zeros((24, B), dtype=torch.float64, device="cuda")
 for _ in range(3):
