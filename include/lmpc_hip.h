@@ -29,14 +29,16 @@
  *     never to the null stream.  An entry point whose array arguments are device pointers is ASYNCHRONOUS unless its comment says
  *     otherwise: it enqueues and returns, and neither waits for the stream nor reads device data on the host.  An entry point that
  *     takes or returns HOST arrays, or that allocates or frees device memory (the create / destroy calls, lmpc_set_safe_set,
- *     lmpc_set_regression_laps, lmpc_fleet_ss_set_regression, lmpc_reserve, a first call that grows a workspace), is BLOCKING: it
- *     waits for the handle's stream where its comment says so, and the runtime's allocator may wait for the whole device.  Four of
- *     them -- lmpc_set_safe_set, lmpc_set_regression_laps, lmpc_fleet_ss_load, lmpc_fleet_ss_get_laps -- move their host arrays with
+ *     lmpc_set_regression_laps and lmpc_fleet_ss_set_regression with their _rows forms, lmpc_reserve, a first call that grows a
+ *     workspace), is BLOCKING: it waits for the handle's stream where its comment says so, and the runtime's allocator may wait for
+ *     the whole device.  Five of them -- lmpc_set_safe_set, lmpc_set_regression_laps, lmpc_set_regression_laps_rows,
+ *     lmpc_fleet_ss_load, lmpc_fleet_ss_get_laps -- move their host arrays with
  *     the synchronous hipMemcpy (a copy on the null stream that has finished when it returns), between waits on the handle's
  *     stream: behind the first wait nothing of the handle is in flight, and what they enqueue afterwards goes to the handle's
  *     stream again.  The rest only read or set host values of the handle.  The three lists are in INTEGRATION.md;
  *     tests/stream_cases.py holds one class per prototype and tests/test_gpu_streams.py holds every entry point to it on a stream
- *     that is held by a timed gate.
+ *     that is held by a timed gate (the two entry points of lmpc_hip_rows.h: tests/test_stream_table_rows.py and
+ *     tests/test_gpu_streams_rows.py).
  */
 #ifndef LMPC_HIP_H_
 #define LMPC_HIP_H_
@@ -756,6 +758,10 @@ int lmpc_fleet_ss_set_regression(lmpc_handle* h, const lmpc_regression_spec* spe
  * and no allocation (legal inside a captured control period). */
 int lmpc_fleet_ss_regress_batch(lmpc_handle* h, int32_t batch, const double* X_ref, const double* U_ref, double* A, double* Bm,
                                 double* g);
+
+/* The regression with one feature list per regressed row, shared (lmpc_set_regression_laps_rows) and per car
+ * (lmpc_fleet_ss_set_regression_rows), and its spec lmpc_regression_rows_spec: declared in lmpc_hip_rows.h. */
+#include "lmpc_hip_rows.h"
 
 /* Spline track: RacingTrajectory's interpolants on the device (racing_trajectory.cpp:25-120) and the two conversions built on them.
  * The five interpolating not-a-knot cubics -- x, y, speed, left and right boundary offset over the abscissa of the waypoints, closed by

@@ -35,6 +35,8 @@ _ABI_SYMBOLS = ("lmpc_create", "lmpc_destroy", "lmpc_last_error", "lmpc_set_stre
                 "lmpc_lqr_create", "lmpc_lqr_destroy", "lmpc_lqr_solve_batch",
                 "lmpc_vanilla_create", "lmpc_vanilla_destroy", "lmpc_vanilla_reset", "lmpc_vanilla_get", "lmpc_vanilla_solve_batch",
                 "lmpc_vanilla_rollout_batch")
+# the entry points of include/lmpc_hip_rows.h (one feature list per regressed row), resolved at load time with the rest
+_ABI_SYMBOLS_ROWS = ("lmpc_set_regression_laps_rows", "lmpc_fleet_ss_set_regression_rows")
 EKF_FALLBACK, EKF_R_REPAIRED, EKF_NOT_FINITE = 1, 2, 4   # bits of the per-car flags of Solver.ekf_update
 LQR_NOT_FINITE = 1   # per-car flag of Solver.lqr_solve: the car's X_optm, U_optm, K or P0 holds a NaN or Inf
 VANILLA_NOT_FINITE = 1   # per-car flag of Solver.vanilla_solve / vanilla_rollout: u_out (rollout: or the state after the plant) holds a NaN or Inf
@@ -68,6 +70,35 @@ class CRegressionSpec(C.Structure):
     """lmpc_regression_spec: RegQuery's index lists and bandwidth (safe_set.hpp:57-75)."""
     _fields_ = [("n_out", C.c_int32), ("out", C.c_int32 * 6), ("n_in_state", C.c_int32), ("in_state", C.c_int32 * 6),
                 ("n_in_ctrl", C.c_int32), ("in_ctrl", C.c_int32 * 2), ("as_written", C.c_int32), ("dist_max", C.c_double)]
+
+
+class CRegressionRowsSpec(C.Structure):
+    """lmpc_regression_rows_spec: RegQuery's index lists, one list per regressed row (safe_set.hpp:61-75), and its bandwidth."""
+    _fields_ = [("n_out", C.c_int32), ("out", C.c_int32 * 6), ("n_in_state", C.c_int32 * 6), ("in_state", (C.c_int32 * 6) * 6),
+                ("n_in_ctrl", C.c_int32 * 6), ("in_ctrl", (C.c_int32 * 2) * 6), ("as_written", C.c_int32), ("dist_max", C.c_double)]
+
+
+def _rows_exclude_one_list(rows, in_state, in_ctrl, out_rows):
+    """rows= carries its own lists: the one-list keywords must then be at their defaults (None, the fleet method's "off", included)."""
+    if rows is not None and not ((in_state is None or tuple(in_state) == (3, 4, 5)) and tuple(in_ctrl) == (0, 1) and tuple(out_rows) == (3, 4, 5)):
+        raise ValueError("rows= carries one (in_state, in_ctrl) list per regressed row: in_state=, in_ctrl= and out_rows= go with the one-list form")
+
+
+def _rows_spec(rows, dist_max, as_written) -> CRegressionRowsSpec:
+    """rows: {row: (in_state, in_ctrl), ...} in insertion order -> lmpc_regression_rows_spec.  Sizes the struct cannot hold are refused
+    here; everything else is the library's to refuse."""
+    rows = list(dict(rows).items())
+    if len(rows) > 6 or any(len(s) > 6 or len(c) > 2 for _, (s, c) in rows):
+        raise LmpcError("rows=: at most 6 rows of at most 6 feature states and 2 feature controls fit lmpc_regression_rows_spec")
+    spec = CRegressionRowsSpec()
+    spec.n_out, spec.dist_max, spec.as_written = len(rows), float(dist_max), 1 if as_written else 0
+    for o, (r, (ins, inc)) in enumerate(rows):
+        spec.out[o], spec.n_in_state[o], spec.n_in_ctrl[o] = int(r), len(ins), len(inc)
+        for f, v in enumerate(ins):
+            spec.in_state[o][f] = int(v)
+        for f, v in enumerate(inc):
+            spec.in_ctrl[o][f] = int(v)
+    return spec
 
 
 class CFleetLoop(C.Structure):
@@ -141,7 +172,7 @@ def load_library():
             raise LmpcError(f"{so} not built: run `python -c 'import __graft_entry__ as g; g.build()'` "
                             f"or `make -C {_HERE / 'csrc'}`")
         lib = C.CDLL(str(so))
-        for sym in _ABI_SYMBOLS:
+        for sym in _ABI_SYMBOLS + _ABI_SYMBOLS_ROWS:
             getattr(lib, sym)
         lib.lmpc_last_error.restype = C.c_char_p
         lib.lmpc_last_error.argtypes = [C.c_void_p]
@@ -595,11 +626,15 @@ class Solver:
 
     # ---- error-dynamics regression (safe_set.cpp:56-114, 182-245) ----
     def set_regression_laps(self, laps, in_state=(3, 4, 5), in_ctrl=(0, 1), out_rows=(3, 4, 5), dist_max: float = 1.0,
-                            as_written: bool = False):
+                            as_written: bool = False, rows=None):
         """laps: list of (x [n,6], u [n,2], k [n], t [n]) host arrays; an empty list switches the regression off.
+        in_state, in_ctrl, out_rows: one feature list for all regressed rows.
+        rows = {row: (in_state, in_ctrl), ...}: one feature list per regressed row instead (lmpc_set_regression_laps_rows), in
+        insertion order; the three one-list keywords then stay at their defaults.
         as_written = True reproduces the reference's literal signs (backward time step, b = -M'K y; lmpc_hip.h)."""
         import numpy as np
 
+        _rows_exclude_one_list(rows, in_state, in_ctrl, out_rows)
         if not laps:
             self._check(self.lib.lmpc_set_regression_laps(self._h, C.c_int32(0), None, None, None, None, None, None),
                         "lmpc_set_regression_laps")
@@ -607,6 +642,12 @@ class Solver:
         n_pts = np.array([np.asarray(l[0]).shape[0] for l in laps], dtype=np.int32)
         cat = [np.ascontiguousarray(np.concatenate([np.asarray(l[i], dtype=np.float64).reshape(n, -1) for l, n in zip(laps, n_pts)], 0))
                for i in range(4)]
+        if rows is not None:
+            spec = _rows_spec(rows, dist_max, as_written)
+            rc = self.lib.lmpc_set_regression_laps_rows(self._h, C.c_int32(len(laps)), n_pts.ctypes.data_as(C.c_void_p),
+                                                        *[a.ctypes.data_as(C.c_void_p) for a in cat], C.byref(spec))
+            self._check(rc, "lmpc_set_regression_laps_rows")
+            return
         spec = CRegressionSpec()
         spec.n_out, spec.n_in_state, spec.n_in_ctrl, spec.dist_max = len(out_rows), len(in_state), len(in_ctrl), float(dist_max)
         spec.out[:len(out_rows)] = list(out_rows)
@@ -811,13 +852,21 @@ class Solver:
 
     # ---- per-car error-dynamics regression on the fleet safe set (safe_set.cpp:182-245, one SafeSetManager per car) ----
     def fleet_ss_set_regression(self, in_state=(3, 4, 5), in_ctrl=(0, 1), out_rows=(3, 4, 5), dist_max: float = 1.0,
-                                as_written: bool = False, off: bool = False):
+                                as_written: bool = False, off: bool = False, rows=None):
         """lmpc_fleet_ss_set_regression: from now on every fp64 / mixed solve of this solver (and fleet_ss_regress) corrects problem
         b's model by the regression on car b's OWN closed laps in the fleet store, as they are at each call; nothing is uploaded.
+        in_state, in_ctrl, out_rows: one feature list for all regressed rows;
+        rows = {row: (in_state, in_ctrl), ...}: one list per regressed row instead (lmpc_fleet_ss_set_regression_rows), with
+        the three one-list keywords left at their defaults.
         in_state=None or off=True switches it off.  as_written: the reference's literal signs (set_regression_laps)."""
         self.use_current_stream()
+        _rows_exclude_one_list(rows, in_state, in_ctrl, out_rows)
         if off or in_state is None:
             self._check(self.lib.lmpc_fleet_ss_set_regression(self._h, None), "lmpc_fleet_ss_set_regression")
+            return
+        if rows is not None:
+            spec = _rows_spec(rows, dist_max, as_written)
+            self._check(self.lib.lmpc_fleet_ss_set_regression_rows(self._h, C.byref(spec)), "lmpc_fleet_ss_set_regression_rows")
             return
         spec = CRegressionSpec()
         spec.n_out, spec.n_in_state, spec.n_in_ctrl, spec.dist_max = len(out_rows), len(in_state), len(in_ctrl), float(dist_max)

@@ -25,6 +25,7 @@
 #include "lmpc_lqr.h"
 #include "lmpc_vanilla.h"
 #include "lmpc_fleet_reg.h"
+#include "lmpc_reg_rows.h"
 #include "lmpc_fleet_ss.h"
 #include "lmpc_fleet_loop.h"
 
@@ -107,6 +108,10 @@ struct __attribute__((visibility("hidden"))) lmpc_handle {  // (its members are 
   int reg_npad = 0;         // their number, padded to a multiple of four with unreachable rows
   bool reg_exact = false;   // features large against the bandwidth: the kernel recomputes each weight from sum (z - q)^2
   lmpc_regression_spec reg_spec{};
+  // one feature list per regressed row (lmpc_set_regression_laps_rows; csrc/lmpc_reg_rows.h): reg_on with reg_rows set -- the same
+  // store, reg_tab in the per-row layout [reg_npad][3 mf + 3], reg_rspec in place of reg_spec
+  bool reg_rows = false;
+  lmpc_reg_rows_dev reg_rspec{};
   // fleet safe set (lmpc_fleet_ss_create): one recorder and one ring of laps per car, csrc/lmpc_fleet_ss.h
   lmpc_fleet_store fleet{};  // raw copies of the five owners below, as the kernels take them
   dev_buf<double2> fleet_key;
@@ -119,6 +124,8 @@ struct __attribute__((visibility("hidden"))) lmpc_handle {  // (its members are 
   // per-car regression on the fleet store (lmpc_fleet_ss_set_regression): csrc/lmpc_fleet_reg.h
   bool freg_on = false;
   lmpc_regression_spec freg_spec{};
+  bool freg_rows = false;  // lmpc_fleet_ss_set_regression_rows: freg_on with freg_rspec in place of freg_spec, the table in the per-row layout
+  lmpc_reg_rows_dev freg_rspec{};
   lmpc_fleet_reg_table freg{};  // raw copies of the two owners below, as the kernels take them
   dev_buf<double> freg_tab;     // [fleet.B][freg.cap][NF + NOUT + 1]
   dev_buf<int> freg_meta;       // nrow [fleet.B] | stamp [fleet.B]
@@ -416,6 +423,16 @@ int launch_regress(lmpc_handle* h, int batch, const double* X_ref, const double*
   const long long queries = (long long)batch * (h->P.N - 1);
   const dim3 grid((unsigned)((queries + 63) / 64)), block(64);
   const double* tab = h->reg_tab.get();
+  if (h->reg_rows) {  // one feature list per row: one pass of lmpc_regress_rows_kernel for all rows
+    if (h->reg_rspec.mf == 4)
+      hipLaunchKernelGGL((lmpc_regress_rows_kernel<4, WS>), grid, block, 0, h->stream, h->P.N, batch, h->reg_rspec, h->reg_npad, tab, X_ref, U_ref, A,
+                         Bm, g);
+    else
+      hipLaunchKernelGGL((lmpc_regress_rows_kernel<5, WS>), grid, block, 0, h->stream, h->P.N, batch, h->reg_rspec, h->reg_npad, tab, X_ref, U_ref, A,
+                         Bm, g);
+    HIP_TRY(h, hipGetLastError());
+    return LMPC_OK;
+  }
   const double* zz = tab + (size_t)h->reg_npad * (size_t)(nf + h->reg_spec.n_out);
   const bool five = nf == 5 && h->reg_spec.n_out == 3;
   const void* fn = h->reg_exact ? (five ? (const void*)lmpc_regress_kernel<5, 3, WS, true> : (const void*)lmpc_regress_kernel<8, 6, WS, true>)
@@ -431,7 +448,10 @@ int launch_regress(lmpc_handle* h, int batch, const double* X_ref, const double*
 
 // the per-car regression (lmpc_fleet_ss_set_regression is in effect): pack what changed, then one wavefront per (car, 64 stages)
 int launch_fleet_regress(lmpc_handle* h, bool ws, const double* X_ref, const double* U_ref, double* A, double* Bm, double* g) {
-  HIP_TRY(h, lmpc_fleet_reg_launch(h->stream, h->fleet, h->P.veh, h->freg_spec, h->freg, h->P.N, ws, X_ref, U_ref, A, Bm, g));
+  if (h->freg_rows)
+    HIP_TRY(h, lmpc_fleet_reg_rows_launch(h->stream, h->fleet, h->P.veh, h->freg_rspec, h->freg, h->P.N, ws, X_ref, U_ref, A, Bm, g));
+  else
+    HIP_TRY(h, lmpc_fleet_reg_launch(h->stream, h->fleet, h->P.veh, h->freg_spec, h->freg, h->P.N, ws, X_ref, U_ref, A, Bm, g));
   return LMPC_OK;
 }
 
@@ -455,7 +475,90 @@ void fleet_reg_off(lmpc_handle* h) {
   h->freg_meta.release();
   h->freg = lmpc_fleet_reg_table{};
   h->freg_on = false;
+  h->freg_rows = false;
   h->freg_bytes = 0;
+}
+
+// the shared regression off, in either form, and its store freed (the caller has drained the stream: a launch may still read it)
+void reg_off(lmpc_handle* h) {
+  h->reg_end.release();
+  h->reg_x.release();
+  h->reg_u.release();
+  h->reg_y.release();
+  h->reg_tab.release();
+  h->reg_npad = 0;
+  h->reg_exact = false;
+  h->reg_on = false;
+  h->reg_rows = false;
+  h->reg_total = 0;
+}
+
+// The laps of the shared regression, either form, onto the device: end-of-lap flags, states, inputs and the nominal model's one-step
+// residuals (reg_end, reg_x, reg_u, reg_y); `valid` = the samples that have a successor, in order.  The kernel has run when it returns.
+int reg_upload_laps(lmpc_handle* h, const char* who, int32_t n_laps, const int32_t* n_pts, const double* x, const double* u, const double* k,
+                    const double* t, bool as_written, std::vector<int>& valid) {
+  size_t total = 0;
+  std::vector<int> end;
+  for (int l = 0; l < n_laps; ++l) {
+    if (n_pts[l] < 2) return fail(h, LMPC_ERR_ARGUMENT, std::string(who) + ": a lap needs two samples");
+    total += (size_t)n_pts[l];
+    end.resize(total, 0);
+    end[total - 1] = 1;
+  }
+  dev_buf<double> dk, dt;  // upload-time temporaries: freed on every way out of this function
+  HIP_TRY(h, h->reg_end.alloc(total));
+  HIP_TRY(h, h->reg_x.alloc(total * 6));
+  HIP_TRY(h, h->reg_u.alloc(total * 2));
+  HIP_TRY(h, h->reg_y.alloc(total * 6));
+  HIP_TRY(h, dk.alloc(total));
+  HIP_TRY(h, dt.alloc(total));
+  HIP_TRY(h, hipMemcpy(h->reg_end.get(), end.data(), total * sizeof(int), hipMemcpyHostToDevice));
+  HIP_TRY(h, hipMemcpy(h->reg_x.get(), x, total * 6 * sizeof(double), hipMemcpyHostToDevice));
+  HIP_TRY(h, hipMemcpy(h->reg_u.get(), u, total * 2 * sizeof(double), hipMemcpyHostToDevice));
+  HIP_TRY(h, hipMemcpy(dk.get(), k, total * sizeof(double), hipMemcpyHostToDevice));
+  HIP_TRY(h, hipMemcpy(dt.get(), t, total * sizeof(double), hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(lmpc_reg_residual_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, h->P.veh,
+                     (int)total, as_written ? 1 : 0, h->reg_end.get(), h->reg_x.get(), h->reg_u.get(), dk.get(), dt.get(),
+                     h->reg_y.get());
+  HIP_TRY(h, hipGetLastError());
+  HIP_TRY(h, hipStreamSynchronize(h->stream));  // dk and dt are read by it
+  valid.clear();
+  valid.reserve(total);
+  for (size_t j = 0; j < total; ++j)
+    if (!end[j]) valid.push_back((int)j);
+  h->reg_total = (int)total;
+  return LMPC_OK;
+}
+
+// The per-car tables of either form, `stride` doubles per sample: refuses a store too large for a car's table, allocates when the size
+// differs from what is there (the only case that drains the stream), and leaves every car to be packed again.
+int fleet_reg_table_setup(lmpc_handle* h, const char* who, size_t stride) {
+  if ((long long)h->fleet.R * (h->fleet.C - 1) > (1ll << 30))
+    return fail(h, LMPC_ERR_ARGUMENT, std::string(who) + ": max_lap_stored x max_pts_per_lap is too large for a car's table");
+  HIP_TRY(h, hipSetDevice(h->device));
+  const size_t Bz = (size_t)h->fleet.B;
+  const int cap = lmpc_fleet_reg_cap(h->fleet.R, h->fleet.C);
+  const size_t tab_n = Bz * (size_t)cap * stride;
+  if (!h->freg_on || cap != h->freg.cap || tab_n * sizeof(double) + 2 * Bz * sizeof(int) != (size_t)h->freg_bytes) {
+    fleet_reg_off(h);
+    // into local owners: a refused allocation leaves the regression off, and nothing behind
+    dev_buf<double> tab;
+    dev_buf<int> meta;
+    HIP_TRY_AS(h, who, tab.alloc(tab_n ? tab_n : 1));
+    HIP_TRY_AS(h, who, meta.alloc(2 * Bz));
+    h->freg_tab = std::move(tab);
+    h->freg_meta = std::move(meta);
+    h->freg.cap = cap;
+    h->freg.tab = h->freg_tab.get();
+    h->freg.nrow = h->freg_meta.get();
+    h->freg.stamp = h->freg_meta.get() + Bz;
+    h->freg_bytes = (int64_t)(tab_n * sizeof(double) + 2 * Bz * sizeof(int));
+  }
+  // behind every launch that still reads the old spec's table: no row count, and every stamp stale (a new spec or sign convention
+  // changes every row)
+  HIP_TRY(h, hipMemsetAsync(h->freg.nrow, 0, Bz * sizeof(int), h->stream));
+  HIP_TRY(h, hipMemsetAsync(h->freg.stamp, 0xff, Bz * sizeof(int), h->stream));
+  return LMPC_OK;
 }
 
 // the polish's save area for `batch` problems of `elem`-byte values: the single-precision entry needs nothing else of
@@ -1366,15 +1469,7 @@ int lmpc_set_regression_laps(lmpc_handle* h, int32_t n_laps, const int32_t* n_pt
   if (!h) return LMPC_ERR_ARGUMENT;
   HIP_TRY(h, hipSetDevice(h->device));
   HIP_TRY(h, hipStreamSynchronize(h->stream));
-  h->reg_end.release();
-  h->reg_x.release();
-  h->reg_u.release();
-  h->reg_y.release();
-  h->reg_tab.release();
-  h->reg_npad = 0;
-  h->reg_exact = false;
-  h->reg_on = false;
-  h->reg_total = 0;
+  reg_off(h);
   if (n_laps == 0 || !spec) return LMPC_OK;
   if (h->freg_on)
     return fail(h, LMPC_ERR_ARGUMENT, "lmpc_set_regression_laps: the per-car regression is on (lmpc_fleet_ss_set_regression); switch it off first");
@@ -1390,36 +1485,14 @@ int lmpc_set_regression_laps(lmpc_handle* h, int32_t n_laps, const int32_t* n_pt
     if (spec->in_state[i] < 0 || spec->in_state[i] > 5) return fail(h, LMPC_ERR_ARGUMENT, "feature state out of range");
   for (int i = 0; i < spec->n_in_ctrl; ++i)
     if (spec->in_ctrl[i] < 0 || spec->in_ctrl[i] > 1) return fail(h, LMPC_ERR_ARGUMENT, "feature control out of range");
-  size_t total = 0;
-  std::vector<int> end;
-  for (int l = 0; l < n_laps; ++l) {
-    if (n_pts[l] < 2) return fail(h, LMPC_ERR_ARGUMENT, "lmpc_set_regression_laps: a lap needs two samples");
-    total += (size_t)n_pts[l];
-    end.resize(total, 0);
-    end[total - 1] = 1;
+  std::vector<int> valid;
+  if (const int rc = reg_upload_laps(h, "lmpc_set_regression_laps", n_laps, n_pts, x, u, k, t, spec->as_written != 0, valid)) {
+    reg_off(h);
+    return rc;
   }
-  dev_buf<double> dk, dt;  // upload-time temporaries: freed on every way out of this function
+  const size_t total = (size_t)h->reg_total;
   dev_buf<int> dvalid;
-  HIP_TRY(h, h->reg_end.alloc(total));
-  HIP_TRY(h, h->reg_x.alloc(total * 6));
-  HIP_TRY(h, h->reg_u.alloc(total * 2));
-  HIP_TRY(h, h->reg_y.alloc(total * 6));
-  HIP_TRY(h, dk.alloc(total));
-  HIP_TRY(h, dt.alloc(total));
-  HIP_TRY(h, hipMemcpy(h->reg_end.get(), end.data(), total * sizeof(int), hipMemcpyHostToDevice));
-  HIP_TRY(h, hipMemcpy(h->reg_x.get(), x, total * 6 * sizeof(double), hipMemcpyHostToDevice));
-  HIP_TRY(h, hipMemcpy(h->reg_u.get(), u, total * 2 * sizeof(double), hipMemcpyHostToDevice));
-  HIP_TRY(h, hipMemcpy(dk.get(), k, total * sizeof(double), hipMemcpyHostToDevice));
-  HIP_TRY(h, hipMemcpy(dt.get(), t, total * sizeof(double), hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(lmpc_reg_residual_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, h->P.veh,
-                     (int)total, spec->as_written ? 1 : 0, h->reg_end.get(), h->reg_x.get(), h->reg_u.get(), dk.get(), dt.get(),
-                     h->reg_y.get());
-  HIP_TRY(h, hipGetLastError());
   {  // dense table of the samples that have a successor (what the per-solve kernel streams)
-    std::vector<int> valid;
-    valid.reserve(total);
-    for (size_t j = 0; j < total; ++j)
-      if (!end[j]) valid.push_back((int)j);
     const int nvalid = (int)valid.size(), npad = (nvalid + 3) / 4 * 4;
     HIP_TRY(h, dvalid.alloc((size_t)nvalid));
     HIP_TRY(h, h->reg_tab.alloc((size_t)npad * (size_t)(nf + spec->n_out + 1)));
@@ -1446,6 +1519,53 @@ int lmpc_set_regression_laps(lmpc_handle* h, int32_t n_laps, const int32_t* n_pt
   h->reg_exact = !(zmax2 <= 256.0 * spec->dist_max * spec->dist_max);
   h->reg_total = (int)total;
   h->reg_spec = *spec;
+  h->reg_on = true;
+  return LMPC_OK;
+}
+
+// the same store with one feature list per regressed row (csrc/lmpc_reg_rows.h, csrc/lmpc_reg_rows_kernel.hip).  Everything that can
+// refuse the call is looked at before the regression in effect is touched.
+int lmpc_set_regression_laps_rows(lmpc_handle* h, int32_t n_laps, const int32_t* n_pts, const double* x, const double* u,
+                                  const double* k, const double* t, const lmpc_regression_rows_spec* spec) {
+  if (!h) return LMPC_ERR_ARGUMENT;
+  HIP_TRY(h, hipSetDevice(h->device));
+  if (n_laps == 0 || !spec) {
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    reg_off(h);
+    return LMPC_OK;
+  }
+  if (h->freg_on)
+    return fail(h, LMPC_ERR_ARGUMENT,
+                "lmpc_set_regression_laps_rows: the per-car regression is on (lmpc_fleet_ss_set_regression / _rows); switch it off first");
+  if (n_laps < 0 || !n_pts || !x || !u || !k || !t) return fail(h, LMPC_ERR_ARGUMENT, "lmpc_set_regression_laps_rows: bad argument");
+  lmpc_reg_rows_dev rs;
+  const char* msg = nullptr;
+  if (const int rc = lmpc_reg_rows_digest(spec, &rs, &msg)) return fail(h, rc, std::string("lmpc_set_regression_laps_rows: ") + msg);
+  for (int l = 0; l < n_laps; ++l)
+    if (n_pts[l] < 2) return fail(h, LMPC_ERR_ARGUMENT, "lmpc_set_regression_laps_rows: a lap needs two samples");
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  reg_off(h);
+  std::vector<int> valid;
+  int rc = reg_upload_laps(h, "lmpc_set_regression_laps_rows", n_laps, n_pts, x, u, k, t, rs.as_written != 0, valid);
+  if (rc == LMPC_OK) rc = [&]() -> int {  // dense table of the samples that have a successor, in the per-row layout
+    const int nvalid = (int)valid.size(), npad = (nvalid + 3) / 4 * 4;
+    dev_buf<int> dvalid;
+    HIP_TRY(h, dvalid.alloc((size_t)nvalid));
+    HIP_TRY(h, h->reg_tab.alloc((size_t)npad * (size_t)lmpc_reg_rows_stride(rs)));
+    HIP_TRY(h, hipMemcpy(dvalid.get(), valid.data(), (size_t)nvalid * sizeof(int), hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(lmpc_reg_rows_pack_kernel, dim3((unsigned)((npad + 255) / 256)), dim3(256), 0, h->stream, rs, nvalid, npad, dvalid.get(),
+                       h->reg_x.get(), h->reg_u.get(), h->reg_y.get(), h->reg_tab.get());
+    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    h->reg_npad = npad;
+    return LMPC_OK;
+  }();
+  if (rc != LMPC_OK) {
+    reg_off(h);
+    return rc;
+  }
+  h->reg_rspec = rs;
+  h->reg_rows = true;
   h->reg_on = true;
   return LMPC_OK;
 }
@@ -1794,32 +1914,31 @@ int lmpc_fleet_ss_set_regression(lmpc_handle* h, const lmpc_regression_spec* spe
     if (spec->in_state[i] < 0 || spec->in_state[i] > 5) return fail(h, LMPC_ERR_ARGUMENT, "feature state out of range");
   for (int i = 0; i < spec->n_in_ctrl; ++i)
     if (spec->in_ctrl[i] < 0 || spec->in_ctrl[i] > 1) return fail(h, LMPC_ERR_ARGUMENT, "feature control out of range");
-  if ((long long)h->fleet.R * (h->fleet.C - 1) > (1ll << 30))
-    return fail(h, LMPC_ERR_ARGUMENT, "lmpc_fleet_ss_set_regression: max_lap_stored x max_pts_per_lap is too large for a car's table");
-  HIP_TRY(h, hipSetDevice(h->device));
-  const size_t Bz = (size_t)h->fleet.B, stride = (size_t)(nf + spec->n_out + 1);
-  const int cap = lmpc_fleet_reg_cap(h->fleet.R, h->fleet.C);
-  const size_t tab_n = Bz * (size_t)cap * stride;
-  if (!h->freg_on || cap != h->freg.cap || tab_n * sizeof(double) + 2 * Bz * sizeof(int) != (size_t)h->freg_bytes) {
-    fleet_reg_off(h);
-    // into local owners: a refused allocation leaves the regression off, and nothing behind
-    dev_buf<double> tab;
-    dev_buf<int> meta;
-    HIP_TRY_AS(h, "lmpc_fleet_ss_set_regression", tab.alloc(tab_n ? tab_n : 1));
-    HIP_TRY_AS(h, "lmpc_fleet_ss_set_regression", meta.alloc(2 * Bz));
-    h->freg_tab = std::move(tab);
-    h->freg_meta = std::move(meta);
-    h->freg.cap = cap;
-    h->freg.tab = h->freg_tab.get();
-    h->freg.nrow = h->freg_meta.get();
-    h->freg.stamp = h->freg_meta.get() + Bz;
-    h->freg_bytes = (int64_t)(tab_n * sizeof(double) + 2 * Bz * sizeof(int));
-  }
-  // behind every launch that still reads the old spec's table: no row count, and every stamp stale (a new spec or sign convention
-  // changes every row)
-  HIP_TRY(h, hipMemsetAsync(h->freg.nrow, 0, Bz * sizeof(int), h->stream));
-  HIP_TRY(h, hipMemsetAsync(h->freg.stamp, 0xff, Bz * sizeof(int), h->stream));
+  if (const int rc = fleet_reg_table_setup(h, "lmpc_fleet_ss_set_regression", (size_t)(nf + spec->n_out + 1))) return rc;
   h->freg_spec = *spec;
+  h->freg_rows = false;
+  h->freg_on = true;
+  return LMPC_OK;
+}
+
+// the same with one feature list per regressed row (csrc/lmpc_reg_rows.h, csrc/lmpc_fleet_reg_rows_kernel.hip)
+int lmpc_fleet_ss_set_regression_rows(lmpc_handle* h, const lmpc_regression_rows_spec* spec) {
+  if (!h) return LMPC_ERR_ARGUMENT;
+  if (!spec) {
+    (void)hipSetDevice(h->device);
+    fleet_reg_off(h);
+    return LMPC_OK;
+  }
+  if (!h->fleet.B) return fail(h, LMPC_ERR_ARGUMENT, "lmpc_fleet_ss_set_regression_rows: no fleet store (lmpc_fleet_ss_create)");
+  if (h->reg_on)
+    return fail(h, LMPC_ERR_ARGUMENT,
+                "lmpc_fleet_ss_set_regression_rows: lmpc_set_regression_laps / _rows is in effect; switch it off first");
+  lmpc_reg_rows_dev rs;
+  const char* msg = nullptr;
+  if (const int rc = lmpc_reg_rows_digest(spec, &rs, &msg)) return fail(h, rc, std::string("lmpc_fleet_ss_set_regression_rows: ") + msg);
+  if (const int rc = fleet_reg_table_setup(h, "lmpc_fleet_ss_set_regression_rows", (size_t)lmpc_reg_rows_stride(rs))) return rc;
+  h->freg_rspec = rs;
+  h->freg_rows = true;
   h->freg_on = true;
   return LMPC_OK;
 }

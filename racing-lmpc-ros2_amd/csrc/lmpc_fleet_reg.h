@@ -14,6 +14,7 @@
 
 #include "lmpc_device.h"
 #include "lmpc_fleet_ss.h"
+#include "lmpc_reg_rows.h"
 
 #define LMPC_FLEET_REG_STALE (-1)  // no lap_count is negative; a memset of 0xff bytes writes it
 
@@ -33,5 +34,12 @@ __attribute__((visibility("hidden"))) hipError_t lmpc_fleet_reg_launch(hipStream
                                                                        const lmpc_regression_spec& spec, const lmpc_fleet_reg_table& tb, int N,
                                                                        bool ws, const double* X_ref, const double* U_ref, double* A, double* Bm,
                                                                        double* g);
+
+// The same two launches for a per-row spec (lmpc_fleet_ss_set_regression_rows; csrc/lmpc_fleet_reg_rows_kernel.hip): the table's row is
+// lmpc_reg_rows.h's, 3 MF + 3 doubles -- 120 bytes for MF = 4, 144 for MF = 5 -- in the same three allocations.
+__attribute__((visibility("hidden"))) hipError_t lmpc_fleet_reg_rows_launch(hipStream_t stream, const lmpc_fleet_store& st, const lmpc_vehicle& veh,
+                                                                            const lmpc_reg_rows_dev& spec, const lmpc_fleet_reg_table& tb, int N,
+                                                                            bool ws, const double* X_ref, const double* U_ref, double* A,
+                                                                            double* Bm, double* g);
 
 #endif  // LMPC_FLEET_REG_H_

@@ -158,3 +158,6 @@ hipError_t lmpc_fleet_reg_launch(hipStream_t stream, const lmpc_fleet_store& st,
   return hipGetLastError();
 }
 #endif
+
+// the same with one feature list per regressed row: its pack kernel, its regression kernel and their launcher
+#include "lmpc_fleet_reg_rows_kernel.hip"

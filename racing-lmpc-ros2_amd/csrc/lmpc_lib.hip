@@ -6,6 +6,7 @@
 #include "lmpc_fleet_ss_kernel.hip"
 #include "lmpc_fleet_loop_kernel.hip"
 #include "lmpc_reg_kernel.hip"
+#include "lmpc_reg_rows_kernel.hip"
 #include "lmpc_sqp_kernel.hip"
 #include "lmpc_track_kernel.hip"
 #include "lmpc_capi.hip"
