@@ -762,6 +762,7 @@ int lmpc_fleet_ss_regress_batch(lmpc_handle* h, int32_t batch, const double* X_r
 /* The regression with one feature list per regressed row, shared (lmpc_set_regression_laps_rows) and per car
  * (lmpc_fleet_ss_set_regression_rows), and its spec lmpc_regression_rows_spec: declared in lmpc_hip_rows.h. */
 #include "lmpc_hip_rows.h"
+#include "lmpc_hip_cars.h"
 
 /* Spline track: RacingTrajectory's interpolants on the device (racing_trajectory.cpp:25-120) and the two conversions built on them.
  * The five interpolating not-a-knot cubics -- x, y, speed, left and right boundary offset over the abscissa of the waypoints, closed by

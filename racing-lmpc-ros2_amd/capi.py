@@ -37,6 +37,8 @@ _ABI_SYMBOLS = ("lmpc_create", "lmpc_destroy", "lmpc_last_error", "lmpc_set_stre
                 "lmpc_vanilla_rollout_batch")
 # the entry points of include/lmpc_hip_rows.h (one feature list per regressed row), resolved at load time with the rest
 _ABI_SYMBOLS_ROWS = ("lmpc_set_regression_laps_rows", "lmpc_fleet_ss_set_regression_rows")
+# the entry points of include/lmpc_hip_cars.h (one plant vehicle per car), resolved at load time in a loop of their own
+_ABI_SYMBOLS_CARS = ("lmpc_cars_set_vehicles", "lmpc_cars_get_vehicles", "lmpc_plant_step_cars_batch")
 EKF_FALLBACK, EKF_R_REPAIRED, EKF_NOT_FINITE = 1, 2, 4   # bits of the per-car flags of Solver.ekf_update
 LQR_NOT_FINITE = 1   # per-car flag of Solver.lqr_solve: the car's X_optm, U_optm, K or P0 holds a NaN or Inf
 VANILLA_NOT_FINITE = 1   # per-car flag of Solver.vanilla_solve / vanilla_rollout: u_out (rollout: or the state after the plant) holds a NaN or Inf
@@ -173,6 +175,8 @@ def load_library():
                             f"or `make -C {_HERE / 'csrc'}`")
         lib = C.CDLL(str(so))
         for sym in _ABI_SYMBOLS + _ABI_SYMBOLS_ROWS:
+            getattr(lib, sym)
+        for sym in _ABI_SYMBOLS_CARS:
             getattr(lib, sym)
         lib.lmpc_last_error.restype = C.c_char_p
         lib.lmpc_last_error.argtypes = [C.c_void_p]
@@ -395,6 +399,44 @@ class Solver:
         rc = self.lib.lmpc_plant_step_batch(self._h, C.c_int32(x.shape[1]), C.byref(ct), _ptr(x), _ptr(u),
                                             C.c_double(dt_sim), C.c_int32(n_sub))
         self._check(rc, "lmpc_plant_step_batch")
+        return x
+
+    # ---- one plant vehicle per car (include/lmpc_hip_cars.h) ----
+    def set_car_vehicles(self, vehicles):
+        """lmpc_cars_set_vehicles: a sequence of B vehicle dicts (the keys of this solver's `vehicle`; "integrator" "rk4" | "euler" per
+        car) becomes the handle's car table; None or an empty sequence switches it off.  While it is set, plant_step_cars steps car b
+        with vehicle b and so does fleet_loop_advance, which then refuses plant= and any batch but B.  Blocking."""
+        self.use_current_stream()
+        vehicles = list(vehicles) if vehicles is not None else []
+        if not vehicles:
+            self._check(self.lib.lmpc_cars_set_vehicles(self._h, C.c_int32(0), C.c_void_p(0)), "lmpc_cars_set_vehicles")
+            self._n_cars = 0
+            return
+        arr = (CVehicle * len(vehicles))()
+        filled = {}   # a dict that stands for many cars (a fleet of a few kinds) is converted once
+        for b, v in enumerate(vehicles):
+            if id(v) not in filled:
+                filled[id(v)] = _fill(CVehicle(), v)
+            arr[b] = filled[id(v)]
+        self._check(self.lib.lmpc_cars_set_vehicles(self._h, C.c_int32(len(vehicles)), arr), "lmpc_cars_set_vehicles")
+        self._n_cars = len(vehicles)   # (a refused call has raised: the table in effect before it, and its size, stay)
+
+    def car_vehicles(self):
+        """lmpc_cars_get_vehicles: the car table read back, a list of B vehicle dicts ("integrator" as 0 | 1).  Blocking; refused
+        without a table."""
+        self.use_current_stream()
+        n = getattr(self, "_n_cars", 0)
+        arr = (CVehicle * max(n, 1))()
+        self._check(self.lib.lmpc_cars_get_vehicles(self._h, C.c_int32(n), arr), "lmpc_cars_get_vehicles")
+        return [{name: getattr(cv, name) for name, _ in CVehicle._fields_} for cv in arr[:n]]
+
+    def plant_step_cars(self, track: dict, x, u, dt_sim: float, n_sub: int = 1):
+        """lmpc_plant_step_cars_batch: plant_step with car b stepped by vehicle b of the car table."""
+        self.use_current_stream()
+        ct = self._ctrack(track)
+        rc = self.lib.lmpc_plant_step_cars_batch(self._h, C.c_int32(x.shape[1]), C.byref(ct), _ptr(x), _ptr(u),
+                                                 C.c_double(dt_sim), C.c_int32(n_sub))
+        self._check(rc, "lmpc_plant_step_cars_batch")
         return x
 
     def loop_advance(self, track: dict, inp: dict, sol: dict, x, u_prev, dt: float, dt_sim: float, n_sub: int = 1, speed_scale: float = 1.0,
@@ -817,7 +859,8 @@ class Solver:
         references in place in `inp`, state["x_ic"], the car's recorder and ring, the lap book (state["lap_time"], ["lap_kind"],
         ["n_learn"]), the phase and state["counters"], and state["query"].  Both solutions None: the head-only call of period 0.
         speed_scale / speed_limit / max_vel_ref_diff: (tracking, learning) pairs; a None limit is this solver's x_max[3], a None
-        difference its max_vel_ref_diff.  plant: a vehicle dict for the plant (None: this solver's).  `state` is fleet_loop_state's
+        difference its max_vel_ref_diff.  plant: a vehicle dict for the plant (None: this solver's, or while a car table is set --
+        set_car_vehicles -- car b's own vehicle; the library refuses plant= then).  `state` is fleet_loop_state's
         dict; n_rec (default: the lap book's first dimension) is how many of its rows the call may write.  Asynchronous; nothing is
         read back."""
         self.use_current_stream()

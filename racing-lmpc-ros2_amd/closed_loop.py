@@ -398,9 +398,23 @@ def run_lmpc(tracker, learner, track: dict, x0, u0, warm_laps: int = 2, learn_la
             "laps_in_set": len(man.laps), "x": x, "warm_hit_rate": (n_hit / n_warm) if n_warm else None}
 
 
+def _check_plants(plant, plants, B: int, who: str):
+    if plants is not None and plant is not None:
+        raise ValueError(who + ": plants= (one vehicle per car) and plant= (one for all) are exclusive")
+    if plants is not None and len(plants) != B:
+        raise ValueError(who + ": plants= holds %d vehicles for %d cars" % (len(plants), B))
+
+
+class _CarsPlant:
+    """run_lmpc_fleet's `plant` for plants=: plant_step is the solver's plant_step_cars (car b stepped by vehicle b of its car table)."""
+
+    def __init__(self, solver):
+        self.plant_step = solver.plant_step_cars
+
+
 def run_lmpc_fleet(tracker, learner, track: dict, x0, u0, warm_laps: int = 2, learn_laps: int = 4, dt: float = 0.025,
                    n_sub: int = 2, warm_speed_scale: float = 0.7, max_steps: int = 20000, max_pts_per_lap: int = 1024,
-                   record_trace: bool = False, regression: dict | None = None, plant=None):
+                   record_trace: bool = False, regression: dict | None = None, plant=None, plants=None):
     """run_lmpc with every car learning from ITS OWN laps: the fleet safe set on `learner` (lmpc_fleet_ss_*: one recorder and one
     ring of max_lap_stored laps per car, on the device) replaces the host recorder of car 0 and the shared store.  Per period, in
     run_lmpc's order: record (x, u_prev, curvature at s, t) for all cars, query every learning car's own ring, solve, plant step,
@@ -420,13 +434,23 @@ def run_lmpc_fleet(tracker, learner, track: dict, x0, u0, warm_laps: int = 2, le
     regression (a dict of Solver.fleet_ss_set_regression's keyword arguments): the learning controller also corrects each car's model
     by the error-dynamics regression on that car's own closed laps (it is switched on on `learner`, and stays on after the run).
     plant (a Solver): its plant_step drives the cars instead of the controllers' -- a plant whose vehicle differs from the
-    controllers' gives the regression something to learn."""
+    controllers' gives the regression something to learn.
+    plants (a list of B vehicle dicts, exclusive with plant=): car b drives on plants[b] -- the list becomes `learner`'s car table
+    (Solver.set_car_vehicles) for the run, every period steps with its plant_step_cars, and the table is cleared at the end."""
     import numpy as np
     import torch
 
+    B = x0.shape[1]
+    _check_plants(plant, plants, B, "run_lmpc_fleet")
+    if plants is not None:
+        learner.set_car_vehicles(plants)
+        try:
+            return run_lmpc_fleet(tracker, learner, track, x0, u0, warm_laps, learn_laps, dt, n_sub, warm_speed_scale, max_steps, max_pts_per_lap,
+                                  record_trace, regression, plant=_CarsPlant(learner))
+        finally:
+            learner.set_car_vehicles(None)
     trk = tracker.device_track(track)
     L = float(track["L"])
-    B = x0.shape[1]
     dev = x0.device
     learner.fleet_ss_create(B, max_pts_per_lap)
     if regression is not None:
@@ -535,7 +559,7 @@ def run_lmpc_fleet(tracker, learner, track: dict, x0, u0, warm_laps: int = 2, le
 
 def run_lmpc_fleet_fused(tracker, learner, track: dict, x0, u0, warm_laps: int = 2, learn_laps: int = 4, dt: float = 0.025,
                          n_sub: int = 2, warm_speed_scale: float = 0.7, max_steps: int = 20000, max_pts_per_lap: int = 1024,
-                         record_trace: bool = False, regression: dict | None = None, plant=None, poll: int = 1):
+                         record_trace: bool = False, regression: dict | None = None, plant=None, poll: int = 1, plants=None):
     """run_lmpc_fleet with everything between two solves in one launch, lmpc_fleet_loop_advance_batch on `learner`: input selection
     between the two controllers' results, plant, shift, x_ic, every car's recorder and ring, the lap book, the per-car phase and the
     next query point.  Same arguments, same experiment, same return dictionary; per period the fleet query when any car learns, the
@@ -549,6 +573,8 @@ def run_lmpc_fleet_fused(tracker, learner, track: dict, x0, u0, warm_laps: int =
 
     plant (a Solver): its VEHICLE drives the cars (the call takes the plant's vehicle by value).  record_trace: the curvature in the
     (x, u, k, t) tuples is run_lmpc_fleet's torch interpolation; the ring holds the kernel's own lookup at the same abscissa.
+    plants (a list of B vehicle dicts, exclusive with plant=): car b drives on plants[b] -- the list is `learner`'s car table
+    (Solver.set_car_vehicles) for the run, which the fused call reads, and the table is cleared at the end.
     Raises ValueError when the two solvers differ in N or vehicle: one launch shifts both controllers' plans with one model."""
     import numpy as np
     import torch
@@ -557,9 +583,17 @@ def run_lmpc_fleet_fused(tracker, learner, track: dict, x0, u0, warm_laps: int =
         raise ValueError("run_lmpc_fleet_fused: tracker and learner must have the same N and the same vehicle")
     if poll < 1:
         raise ValueError("run_lmpc_fleet_fused: poll must be >= 1")
+    B = x0.shape[1]
+    _check_plants(plant, plants, B, "run_lmpc_fleet_fused")
+    if plants is not None:
+        learner.set_car_vehicles(plants)
+        try:
+            return run_lmpc_fleet_fused(tracker, learner, track, x0, u0, warm_laps, learn_laps, dt, n_sub, warm_speed_scale, max_steps,
+                                        max_pts_per_lap, record_trace, regression, None, poll)
+        finally:
+            learner.set_car_vehicles(None)
     trk = tracker.device_track(track)
     L = float(track["L"])
-    B = x0.shape[1]
     dev = x0.device
     learner.fleet_ss_create(B, max_pts_per_lap)
     if regression is not None:

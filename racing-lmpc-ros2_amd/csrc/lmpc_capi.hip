@@ -28,6 +28,7 @@
 #include "lmpc_reg_rows.h"
 #include "lmpc_fleet_ss.h"
 #include "lmpc_fleet_loop.h"
+#include "lmpc_cars.h"
 
 namespace {
 // Move-only owner of one device (PINNED: pinned host) allocation: freed by the destructor, and by alloc() before it allocates anew.
@@ -130,6 +131,9 @@ struct __attribute__((visibility("hidden"))) lmpc_handle {  // (its members are 
   dev_buf<double> freg_tab;     // [fleet.B][freg.cap][NF + NOUT + 1]
   dev_buf<int> freg_meta;       // nrow [fleet.B] | stamp [fleet.B]
   int64_t freg_bytes = 0;
+  // car table (lmpc_cars_set_vehicles): one plant vehicle per car, csrc/lmpc_cars.h
+  dev_buf<double> cars_tab;  // [lmpc_cars_fields][cars_B] doubles | integrator int32 [cars_B]
+  int cars_B = 0;            // 0: no table
   // batched extended Kalman filter (lmpc_ekf_create): one filter per car, csrc/lmpc_ekf.h
   lmpc_ekf_store ekf{};  // raw copies of the two owners below, as the kernels take them
   dev_buf<double> ekf_xup;  // x [6][B] | u [2][B] | P [36][B]
@@ -1769,6 +1773,10 @@ int lmpc_fleet_loop_advance_batch(lmpc_handle* h, int32_t batch, const lmpc_trac
     return fail(h, LMPC_ERR_ARGUMENT, std::string(who) + ": plant: integrator must be LMPC_INTEGRATOR_RK4 or LMPC_INTEGRATOR_EULER");
   if ((io->X_trk && (io->X_ref == io->X_trk || io->U_ref == io->U_trk)) || (io->X_lrn && (io->X_ref == io->X_lrn || io->U_ref == io->U_lrn)))
     return fail(h, LMPC_ERR_ARGUMENT, std::string(who) + ": the references must not alias a solution");
+  if (h->cars_B && io->plant)
+    return fail(h, LMPC_ERR_ARGUMENT, std::string(who) + ": plant must be NULL while a car table is set (lmpc_cars_set_vehicles): one source for the plant");
+  if (h->cars_B && h->cars_B != batch)
+    return fail(h, LMPC_ERR_ARGUMENT, std::string(who) + ": the car table holds " + std::to_string(h->cars_B) + " vehicles, the store " + std::to_string(batch) + " cars");
   if (h->out_aos) return fail(h, LMPC_ERR_UNSUPPORTED, std::string(who) + " reads the solutions in the [component][knot][batch] layout");
   HIP_TRY(h, hipSetDevice(h->device));
   lmpc_fleet_loop_consts K{};
@@ -1780,7 +1788,87 @@ int lmpc_fleet_loop_advance_batch(lmpc_handle* h, int32_t batch, const lmpc_trac
   dev.plant = nullptr;  // (a host pointer: the kernel takes the vehicle by value)
   dev.restart_failed = io->restart_failed ? 1 : 0;
   h->fleet_L = track->L;  // what the query unrolls the laps by, as lmpc_fleet_ss_record_batch notes it
-  hipLaunchKernelGGL(lmpc_fleet_loop_kernel, dim3((batch + 63) / 64), dim3(64 * lmpc_loop_waves), 0, h->stream, K, h->fleet, *track, dev);
+  if (h->cars_B) {  // the kernel's table instantiation reads the DEVICE car table where the host's vehicle pointer was
+    dev.plant = reinterpret_cast<const lmpc_vehicle*>(h->cars_tab.get());
+    hipLaunchKernelGGL(lmpc_fleet_loop_kernel<true>, dim3((batch + 63) / 64), dim3(64 * lmpc_loop_waves), 0, h->stream, K, h->fleet, *track, dev);
+  } else {
+    hipLaunchKernelGGL(lmpc_fleet_loop_kernel<false>, dim3((batch + 63) / 64), dim3(64 * lmpc_loop_waves), 0, h->stream, K, h->fleet, *track, dev);
+  }
+  HIP_TRY(h, hipGetLastError());
+  return LMPC_OK;
+}
+
+// ---- the car table: one plant vehicle per car (include/lmpc_hip_cars.h, csrc/lmpc_cars.h, csrc/lmpc_cars_kernel.hip) ----
+int lmpc_cars_set_vehicles(lmpc_handle* h, int32_t batch, const lmpc_vehicle* veh) {
+  if (!h) return LMPC_ERR_ARGUMENT;
+  const char* who = "lmpc_cars_set_vehicles";
+  if (batch < 0) return fail(h, LMPC_ERR_ARGUMENT, std::string(who) + ": batch is negative");
+  const bool off = !veh || batch == 0;
+  for (int b = 0; !off && b < batch; ++b) {
+    if (veh[b].model_id != LMPC_MODEL_SINGLE_TRACK_PLANAR)
+      return fail(h, LMPC_ERR_ARGUMENT, std::string(who) + ": vehicle " + std::to_string(b) + ": only single_track_planar_model is built");
+    if (veh[b].integrator != LMPC_INTEGRATOR_RK4 && veh[b].integrator != LMPC_INTEGRATOR_EULER)
+      return fail(h, LMPC_ERR_ARGUMENT, std::string(who) + ": vehicle " + std::to_string(b) + ": integrator must be LMPC_INTEGRATOR_RK4 or LMPC_INTEGRATOR_EULER");
+  }
+  HIP_TRY(h, hipSetDevice(h->device));
+  HIP_TRY(h, hipStreamSynchronize(h->stream));  // nothing in flight reads the older table
+  if (off) {
+    h->cars_tab.release();
+    h->cars_B = 0;
+    return LMPC_OK;
+  }
+  const size_t B = (size_t)batch, nd = lmpc_cars_doubles(B);
+  std::vector<double> host(nd, 0.0);
+  int* const integ = reinterpret_cast<int*>(host.data() + (size_t)lmpc_cars_fields * B);
+  for (size_t b = 0; b < B; ++b) {
+    size_t f = 0;
+#define LMPC_CARS_PACK_(name) host[(f++) * B + b] = veh[b].name;
+    LMPC_VEHICLE_DOUBLES(LMPC_CARS_PACK_)
+#undef LMPC_CARS_PACK_
+    integ[b] = veh[b].integrator;
+  }
+  dev_buf<double> tab;  // into a local owner: a refused allocation or copy leaves the older table in effect
+  HIP_TRY_AS(h, who, tab.alloc(nd));
+  HIP_TRY_AS(h, who, hipMemcpy(tab.get(), host.data(), nd * sizeof(double), hipMemcpyHostToDevice));
+  h->cars_tab = std::move(tab);
+  h->cars_B = batch;
+  return LMPC_OK;
+}
+
+int lmpc_cars_get_vehicles(lmpc_handle* h, int32_t batch, lmpc_vehicle* veh) {
+  if (!h) return LMPC_ERR_ARGUMENT;
+  const char* who = "lmpc_cars_get_vehicles";
+  if (!h->cars_B) return fail(h, LMPC_ERR_ARGUMENT, std::string(who) + ": no car table (lmpc_cars_set_vehicles)");
+  if (batch != h->cars_B || !veh)
+    return fail(h, LMPC_ERR_ARGUMENT, std::string(who) + ": veh is NULL or batch " + std::to_string(batch) + " is not the table's " + std::to_string(h->cars_B));
+  HIP_TRY(h, hipSetDevice(h->device));
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  const size_t B = (size_t)batch, nd = lmpc_cars_doubles(B);
+  std::vector<double> host(nd);
+  HIP_TRY_AS(h, who, hipMemcpy(host.data(), h->cars_tab.get(), nd * sizeof(double), hipMemcpyDeviceToHost));
+  const int* const integ = reinterpret_cast<const int*>(host.data() + (size_t)lmpc_cars_fields * B);
+  for (size_t b = 0; b < B; ++b) {
+    size_t f = 0;
+#define LMPC_CARS_UNPACK_(name) veh[b].name = host[(f++) * B + b];
+    LMPC_VEHICLE_DOUBLES(LMPC_CARS_UNPACK_)
+#undef LMPC_CARS_UNPACK_
+    veh[b].model_id = LMPC_MODEL_SINGLE_TRACK_PLANAR;
+    veh[b].integrator = integ[b];
+  }
+  return LMPC_OK;
+}
+
+int lmpc_plant_step_cars_batch(lmpc_handle* h, int32_t batch, const lmpc_track* track, double* x, const double* u, double dt_sim,
+                               int32_t n_sub) {
+  if (!h) return LMPC_ERR_ARGUMENT;
+  const char* who = "lmpc_plant_step_cars_batch";
+  if (!h->cars_B) return fail(h, LMPC_ERR_ARGUMENT, std::string(who) + ": no car table (lmpc_cars_set_vehicles)");
+  if (batch != h->cars_B)
+    return fail(h, LMPC_ERR_ARGUMENT, std::string(who) + ": batch " + std::to_string(batch) + " is not the table's " + std::to_string(h->cars_B));
+  if (!track_ok(track) || !x || !u || !(dt_sim > 0.0) || n_sub < 1) return fail(h, LMPC_ERR_ARGUMENT, std::string(who) + ": bad argument");
+  HIP_TRY(h, hipSetDevice(h->device));
+  hipLaunchKernelGGL(lmpc_plant_cars_kernel, dim3((batch + 255) / 256), dim3(256), 0, h->stream, h->cars_tab.get(), batch, *track, x, u, dt_sim,
+                     n_sub);
   HIP_TRY(h, hipGetLastError());
   return LMPC_OK;
 }

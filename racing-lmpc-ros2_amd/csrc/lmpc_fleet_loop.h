@@ -16,6 +16,9 @@ struct lmpc_fleet_loop_consts {
   lmpc_vehicle plant;           // the plant's vehicle: lmpc_fleet_loop.plant, or the handle's
 };
 
+// <false>: every car's plant is consts.plant.  <true>: lmpc_fleet_loop.plant is the DEVICE car table of csrc/lmpc_cars.h, a table
+// of the store's batch, and car b's plant is vehicle b (consts.plant is not read).
+template <bool CARS>
 __global__ void lmpc_fleet_loop_kernel(lmpc_fleet_loop_consts, lmpc_fleet_store, lmpc_track, lmpc_fleet_loop);
 
 #endif  // LMPC_FLEET_LOOP_H_

@@ -21,6 +21,7 @@
 // Ordinary vector loads and stores, and two vector atomics (the counters).
 #include <hip/hip_runtime.h>
 
+#include "lmpc_cars.h"
 #include "lmpc_fleet_loop.h"
 #include "lmpc_loop_steps.hip.h"
 
@@ -60,6 +61,15 @@ __device__ __noinline__ lmpc_last_knot fleet_loop_shift_in_place(lmpc_vehicle ve
   return {x[0], x[1]};
 }
 
+// One text, two instantiations.  CARS = false is the kernel as it always was: io.plant blanked by the host, every car's plant
+// K.plant.  CARS = true: io.plant is the DEVICE car table of csrc/lmpc_cars.h (the host puts it there; a table of st.B cars), and
+// step 2 loads car b's vehicle from it and hands that to the same fleet_loop_plant.  A second kernel and not a run-time branch in
+// the first, and the kernel itself the template, not a wrapper around an inlined body: so instantiated, <false> is the instruction
+// stream, the 256 VGPRs and the 848 bytes of scratch it had as a plain kernel (compared on the compiler's assembly; behind a
+// wrapper its scratch grew to 928 bytes), which is what tests/test_gpu_fleet_loop.py and profiles/fleet_lmpc_fused.md hold it to.
+// Everything but step 2's vehicle is the same in both: the reference rollouts, the cold restart, the in-place shift and the body
+// width of worst_excess use the handle's vehicle K.veh -- the controllers share one model.
+template <bool CARS>
 __global__ __launch_bounds__(64 * lmpc_loop_waves) void lmpc_fleet_loop_kernel(lmpc_fleet_loop_consts K, lmpc_fleet_store st, lmpc_track trk,
                                                                                lmpc_fleet_loop io) {
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -94,7 +104,13 @@ __global__ __launch_bounds__(64 * lmpc_loop_waves) void lmpc_fleet_loop_kernel(l
 #pragma unroll
       for (int k = 0; k < 6; ++k) x[k] = io.x[(size_t)k * B + b];
       const double s_before = x[0];
-      fleet_loop_plant(K.plant, trk, x, u[0], u[1], io.dt_sim, io.n_sub);
+      if constexpr (CARS) {
+        lmpc_vehicle car;
+        lmpc_car_vehicle(reinterpret_cast<const double*>(io.plant), B, b, car);
+        fleet_loop_plant(car, trk, x, u[0], u[1], io.dt_sim, io.n_sub);
+      } else {
+        fleet_loop_plant(K.plant, trk, x, u[0], u[1], io.dt_sim, io.n_sub);
+      }
 #pragma unroll
       for (int k = 0; k < 6; ++k) io.x[(size_t)k * B + b] = x[k];
 #pragma unroll
@@ -160,3 +176,6 @@ __global__ __launch_bounds__(64 * lmpc_loop_waves) void lmpc_fleet_loop_kernel(l
   io.query[b] = last_s + ll * (double)((ds > 0.0) - (ds < 0.0));  // (ll is a whole number of laps times +-1 or 0: the product is exact)
   io.query[(size_t)B + b] = last_ey;
 }
+
+template __global__ void lmpc_fleet_loop_kernel<false>(lmpc_fleet_loop_consts, lmpc_fleet_store, lmpc_track, lmpc_fleet_loop);
+template __global__ void lmpc_fleet_loop_kernel<true>(lmpc_fleet_loop_consts, lmpc_fleet_store, lmpc_track, lmpc_fleet_loop);

@@ -5,6 +5,7 @@
 #include "lmpc_ss_kernel.hip"
 #include "lmpc_fleet_ss_kernel.hip"
 #include "lmpc_fleet_loop_kernel.hip"
+#include "lmpc_cars_kernel.hip"
 #include "lmpc_reg_kernel.hip"
 #include "lmpc_reg_rows_kernel.hip"
 #include "lmpc_sqp_kernel.hip"
