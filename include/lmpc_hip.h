@@ -75,7 +75,8 @@ typedef enum lmpc_status {
                                    single-precision residuals (the default two-pass solve re-solves these in fp64, which has
                                    the last word, and never reports 3) */
 
-/* vehicle_model_factory.cpp:31-49 -- same selector names; only the first is built */
+/* vehicle_model_factory.cpp:31-49 -- same selector names; only the first is built as a controller's model (lmpc_create); the
+ * third is built as a PLANT only, lmpc_hip_dtrack.h */
 #define LMPC_MODEL_SINGLE_TRACK_PLANAR 0
 #define LMPC_MODEL_KINEMATIC_BICYCLE 1
 #define LMPC_MODEL_DOUBLE_TRACK_PLANAR 2
@@ -763,6 +764,7 @@ int lmpc_fleet_ss_regress_batch(lmpc_handle* h, int32_t batch, const double* X_r
  * (lmpc_fleet_ss_set_regression_rows), and its spec lmpc_regression_rows_spec: declared in lmpc_hip_rows.h. */
 #include "lmpc_hip_rows.h"
 #include "lmpc_hip_cars.h"
+#include "lmpc_hip_dtrack.h"
 
 /* Spline track: RacingTrajectory's interpolants on the device (racing_trajectory.cpp:25-120) and the two conversions built on them.
  * The five interpolating not-a-knot cubics -- x, y, speed, left and right boundary offset over the abscissa of the waypoints, closed by

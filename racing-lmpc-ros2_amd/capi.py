@@ -39,6 +39,8 @@ _ABI_SYMBOLS = ("lmpc_create", "lmpc_destroy", "lmpc_last_error", "lmpc_set_stre
 _ABI_SYMBOLS_ROWS = ("lmpc_set_regression_laps_rows", "lmpc_fleet_ss_set_regression_rows")
 # the entry points of include/lmpc_hip_cars.h (one plant vehicle per car), resolved at load time in a loop of their own
 _ABI_SYMBOLS_CARS = ("lmpc_cars_set_vehicles", "lmpc_cars_get_vehicles", "lmpc_plant_step_cars_batch")
+# the entry points of include/lmpc_hip_dtrack.h (the double-track plant), resolved at load time in a loop of their own
+_ABI_SYMBOLS_DTRACK = ("lmpc_dtrack_set_vehicles", "lmpc_dtrack_get_vehicles", "lmpc_plant_step_dtrack_batch")
 EKF_FALLBACK, EKF_R_REPAIRED, EKF_NOT_FINITE = 1, 2, 4   # bits of the per-car flags of Solver.ekf_update
 LQR_NOT_FINITE = 1   # per-car flag of Solver.lqr_solve: the car's X_optm, U_optm, K or P0 holds a NaN or Inf
 VANILLA_NOT_FINITE = 1   # per-car flag of Solver.vanilla_solve / vanilla_rollout: u_out (rollout: or the state after the plant) holds a NaN or Inf
@@ -53,6 +55,11 @@ class CVehicle(C.Structure):
         (n, C.c_double) for n in
         ("m Jzz l cg_ratio h b fr kd kb cd Af rho cl_f cl_r mu Bf Cf Br Cr Fd_max Fb_max Td Tb "
          "max_steer max_steer_rate").split()]
+
+
+class CVehicleDT(C.Structure):
+    """lmpc_vehicle_dt of include/lmpc_hip_dtrack.h: a CVehicle and the nine doubles of the four-wheel model."""
+    _fields_ = [("base", CVehicle)] + [(n, C.c_double) for n in "tw_f tw_r kroll_f Ef Fz0_f eps_f Er Fz0_r eps_r".split()]
 
 
 class CConfig(C.Structure):
@@ -177,6 +184,8 @@ def load_library():
         for sym in _ABI_SYMBOLS + _ABI_SYMBOLS_ROWS:
             getattr(lib, sym)
         for sym in _ABI_SYMBOLS_CARS:
+            getattr(lib, sym)
+        for sym in _ABI_SYMBOLS_DTRACK:
             getattr(lib, sym)
         lib.lmpc_last_error.restype = C.c_char_p
         lib.lmpc_last_error.argtypes = [C.c_void_p]
@@ -437,6 +446,51 @@ class Solver:
         rc = self.lib.lmpc_plant_step_cars_batch(self._h, C.c_int32(x.shape[1]), C.byref(ct), _ptr(x), _ptr(u),
                                                  C.c_double(dt_sim), C.c_int32(n_sub))
         self._check(rc, "lmpc_plant_step_cars_batch")
+        return x
+
+    # ---- the double-track plant: one four-wheel vehicle per car (include/lmpc_hip_dtrack.h) ----
+    def set_dtrack_vehicles(self, vehicles):
+        """lmpc_dtrack_set_vehicles: a sequence of B double-track vehicle dicts (presets.barc_double_track's keys: the vehicle's, with
+        model_id 2, and tw_f, tw_r, kroll_f, Ef, Fz0_f, eps_f, Er, Fz0_r, eps_r; "integrator" "rk4" | "euler" per car) becomes the
+        handle's double-track table; None or an empty sequence switches it off.  Only plant_step_dtrack reads it.  Blocking."""
+        self.use_current_stream()
+        vehicles = list(vehicles) if vehicles is not None else []
+        if not vehicles:
+            self._check(self.lib.lmpc_dtrack_set_vehicles(self._h, C.c_int32(0), C.c_void_p(0)), "lmpc_dtrack_set_vehicles")
+            self._n_dtrack = 0
+            return
+        arr = (CVehicleDT * len(vehicles))()
+        filled = {}   # a dict that stands for many cars (a fleet of a few kinds) is converted once
+        for b, v in enumerate(vehicles):
+            if id(v) not in filled:
+                cv = CVehicleDT()
+                _fill(cv.base, v)
+                for name, _ in CVehicleDT._fields_[1:]:
+                    setattr(cv, name, float(v[name]))
+                filled[id(v)] = cv
+            arr[b] = filled[id(v)]
+        self._check(self.lib.lmpc_dtrack_set_vehicles(self._h, C.c_int32(len(vehicles)), arr), "lmpc_dtrack_set_vehicles")
+        self._n_dtrack = len(vehicles)   # (a refused call has raised: the table in effect before it, and its size, stay)
+
+    def get_dtrack_vehicles(self):
+        """lmpc_dtrack_get_vehicles: the double-track table read back, a list of B flat vehicle dicts ("integrator" as 0 | 1).
+        Blocking; refused without a table."""
+        self.use_current_stream()
+        n = getattr(self, "_n_dtrack", 0)
+        arr = (CVehicleDT * max(n, 1))()
+        self._check(self.lib.lmpc_dtrack_get_vehicles(self._h, C.c_int32(n), arr), "lmpc_dtrack_get_vehicles")
+        return [dict({name: getattr(cv.base, name) for name, _ in CVehicle._fields_},
+                     **{name: getattr(cv, name) for name, _ in CVehicleDT._fields_[1:]}) for cv in arr[:n]]
+
+    def plant_step_dtrack(self, track: dict, x, u, dt_sim: float, n_sub: int = 1, gamma_y=None):
+        """lmpc_plant_step_dtrack_batch: x [6, B] = [s, e_y, e_psi, vx, vy, omega] advanced in place on the double-track model, car b
+        with vehicle b of the double-track table; gamma_y (a float64 [B] tensor, optional) receives the lateral load transfer solved
+        in the first evaluation of the last sub-step."""
+        self.use_current_stream()
+        ct = self._ctrack(track)
+        rc = self.lib.lmpc_plant_step_dtrack_batch(self._h, C.c_int32(x.shape[1]), C.byref(ct), _ptr(x), _ptr(u),
+                                                   C.c_double(dt_sim), C.c_int32(n_sub), _ptr(gamma_y))
+        self._check(rc, "lmpc_plant_step_dtrack_batch")
         return x
 
     def loop_advance(self, track: dict, inp: dict, sol: dict, x, u_prev, dt: float, dt_sim: float, n_sub: int = 1, speed_scale: float = 1.0,

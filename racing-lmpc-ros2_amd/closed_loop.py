@@ -398,11 +398,11 @@ def run_lmpc(tracker, learner, track: dict, x0, u0, warm_laps: int = 2, learn_la
             "laps_in_set": len(man.laps), "x": x, "warm_hit_rate": (n_hit / n_warm) if n_warm else None}
 
 
-def _check_plants(plant, plants, B: int, who: str):
+def _check_plants(plant, plants, B: int, who: str, what: str = "plants"):
     if plants is not None and plant is not None:
-        raise ValueError(who + ": plants= (one vehicle per car) and plant= (one for all) are exclusive")
+        raise ValueError(who + ": " + what + "= (one vehicle per car) and plant= (one for all) are exclusive")
     if plants is not None and len(plants) != B:
-        raise ValueError(who + ": plants= holds %d vehicles for %d cars" % (len(plants), B))
+        raise ValueError(who + ": " + what + "= holds %d vehicles for %d cars" % (len(plants), B))
 
 
 class _CarsPlant:
@@ -412,9 +412,17 @@ class _CarsPlant:
         self.plant_step = solver.plant_step_cars
 
 
+class _DtrackPlant:
+    """run_lmpc_fleet's `plant` for plants_dt=: plant_step is the solver's plant_step_dtrack (car b stepped by the four-wheel vehicle
+    b of its double-track table)."""
+
+    def __init__(self, solver):
+        self.plant_step = solver.plant_step_dtrack
+
+
 def run_lmpc_fleet(tracker, learner, track: dict, x0, u0, warm_laps: int = 2, learn_laps: int = 4, dt: float = 0.025,
                    n_sub: int = 2, warm_speed_scale: float = 0.7, max_steps: int = 20000, max_pts_per_lap: int = 1024,
-                   record_trace: bool = False, regression: dict | None = None, plant=None, plants=None):
+                   record_trace: bool = False, regression: dict | None = None, plant=None, plants=None, plants_dt=None):
     """run_lmpc with every car learning from ITS OWN laps: the fleet safe set on `learner` (lmpc_fleet_ss_*: one recorder and one
     ring of max_lap_stored laps per car, on the device) replaces the host recorder of car 0 and the shared store.  Per period, in
     run_lmpc's order: record (x, u_prev, curvature at s, t) for all cars, query every learning car's own ring, solve, plant step,
@@ -436,11 +444,25 @@ def run_lmpc_fleet(tracker, learner, track: dict, x0, u0, warm_laps: int = 2, le
     plant (a Solver): its plant_step drives the cars instead of the controllers' -- a plant whose vehicle differs from the
     controllers' gives the regression something to learn.
     plants (a list of B vehicle dicts, exclusive with plant=): car b drives on plants[b] -- the list becomes `learner`'s car table
-    (Solver.set_car_vehicles) for the run, every period steps with its plant_step_cars, and the table is cleared at the end."""
+    (Solver.set_car_vehicles) for the run, every period steps with its plant_step_cars, and the table is cleared at the end.
+    plants_dt (a list of B double-track vehicle dicts, presets.barc_double_track's keys; exclusive with plant= and plants=): car b
+    drives on the FOUR-WHEEL model with plants_dt[b] while the controllers stay single-track -- the list becomes `learner`'s
+    double-track table (Solver.set_dtrack_vehicles) for the run, every period steps with its plant_step_dtrack, and the table is
+    cleared at the end."""
     import numpy as np
     import torch
 
     B = x0.shape[1]
+    if plants_dt is not None:
+        if plants is not None:
+            raise ValueError("run_lmpc_fleet: plants= (single-track cars) and plants_dt= (double-track cars) are exclusive")
+        _check_plants(plant, plants_dt, B, "run_lmpc_fleet", "plants_dt")
+        learner.set_dtrack_vehicles(plants_dt)
+        try:
+            return run_lmpc_fleet(tracker, learner, track, x0, u0, warm_laps, learn_laps, dt, n_sub, warm_speed_scale, max_steps, max_pts_per_lap,
+                                  record_trace, regression, plant=_DtrackPlant(learner))
+        finally:
+            learner.set_dtrack_vehicles(None)
     _check_plants(plant, plants, B, "run_lmpc_fleet")
     if plants is not None:
         learner.set_car_vehicles(plants)

@@ -29,6 +29,7 @@
 #include "lmpc_fleet_ss.h"
 #include "lmpc_fleet_loop.h"
 #include "lmpc_cars.h"
+#include "lmpc_dtrack.h"
 
 namespace {
 // Move-only owner of one device (PINNED: pinned host) allocation: freed by the destructor, and by alloc() before it allocates anew.
@@ -134,6 +135,9 @@ struct __attribute__((visibility("hidden"))) lmpc_handle {  // (its members are 
   // car table (lmpc_cars_set_vehicles): one plant vehicle per car, csrc/lmpc_cars.h
   dev_buf<double> cars_tab;  // [lmpc_cars_fields][cars_B] doubles | integrator int32 [cars_B]
   int cars_B = 0;            // 0: no table
+  // double-track table (lmpc_dtrack_set_vehicles): one four-wheel plant vehicle per car, csrc/lmpc_dtrack.h
+  dev_buf<double> dtrack_tab;  // [lmpc_dtrack_fields][dtrack_B] doubles | integrator int32 [dtrack_B]
+  int dtrack_B = 0;            // 0: no table
   // batched extended Kalman filter (lmpc_ekf_create): one filter per car, csrc/lmpc_ekf.h
   lmpc_ekf_store ekf{};  // raw copies of the two owners below, as the kernels take them
   dev_buf<double> ekf_xup;  // x [6][B] | u [2][B] | P [36][B]
@@ -1870,6 +1874,67 @@ int lmpc_plant_step_cars_batch(lmpc_handle* h, int32_t batch, const lmpc_track* 
   hipLaunchKernelGGL(lmpc_plant_cars_kernel, dim3((batch + 255) / 256), dim3(256), 0, h->stream, h->cars_tab.get(), batch, *track, x, u, dt_sim,
                      n_sub);
   HIP_TRY(h, hipGetLastError());
+  return LMPC_OK;
+}
+
+// ---- the double-track table: one four-wheel plant vehicle per car (include/lmpc_hip_dtrack.h, csrc/lmpc_dtrack.h, csrc/lmpc_dtrack_kernel.hip) ----
+int lmpc_dtrack_set_vehicles(lmpc_handle* h, int32_t batch, const lmpc_vehicle_dt* veh) {
+  if (!h) return LMPC_ERR_ARGUMENT;
+  const char* who = "lmpc_dtrack_set_vehicles";
+  if (batch < 0) return fail(h, LMPC_ERR_ARGUMENT, std::string(who) + ": batch is negative");
+  const bool off = !veh || batch == 0;
+  for (int b = 0; !off && b < batch; ++b) {
+    const std::string car = std::string(who) + ": vehicle " + std::to_string(b);
+    if (veh[b].base.model_id != LMPC_MODEL_DOUBLE_TRACK_PLANAR)
+      return fail(h, LMPC_ERR_ARGUMENT, car + ": model_id must be LMPC_MODEL_DOUBLE_TRACK_PLANAR");
+    if (veh[b].base.integrator != LMPC_INTEGRATOR_RK4 && veh[b].base.integrator != LMPC_INTEGRATOR_EULER)
+      return fail(h, LMPC_ERR_ARGUMENT, car + ": integrator must be LMPC_INTEGRATOR_RK4 or LMPC_INTEGRATOR_EULER");
+    if (!(veh[b].tw_f + veh[b].tw_r > 0.0)) return fail(h, LMPC_ERR_ARGUMENT, car + ": tw_f + tw_r must be positive");
+    if (veh[b].Fz0_f == 0.0 || veh[b].Fz0_r == 0.0) return fail(h, LMPC_ERR_ARGUMENT, car + ": Fz0_f and Fz0_r must not be 0");
+  }
+  HIP_TRY(h, hipSetDevice(h->device));
+  HIP_TRY(h, hipStreamSynchronize(h->stream));  // nothing in flight reads the older table
+  if (off) {
+    h->dtrack_tab.release();
+    h->dtrack_B = 0;
+    return LMPC_OK;
+  }
+  const size_t nd = lmpc_dtrack_doubles((size_t)batch);
+  std::vector<double> host(nd, 0.0);
+  lmpc_dtrack_pack(veh, (size_t)batch, host.data());
+  dev_buf<double> tab;  // into a local owner: a refused allocation or copy leaves the older table in effect
+  HIP_TRY_AS(h, who, tab.alloc(nd));
+  HIP_TRY_AS(h, who, hipMemcpy(tab.get(), host.data(), nd * sizeof(double), hipMemcpyHostToDevice));
+  h->dtrack_tab = std::move(tab);
+  h->dtrack_B = batch;
+  return LMPC_OK;
+}
+
+int lmpc_dtrack_get_vehicles(lmpc_handle* h, int32_t batch, lmpc_vehicle_dt* veh) {
+  if (!h) return LMPC_ERR_ARGUMENT;
+  const char* who = "lmpc_dtrack_get_vehicles";
+  if (!h->dtrack_B) return fail(h, LMPC_ERR_ARGUMENT, std::string(who) + ": no double-track table (lmpc_dtrack_set_vehicles)");
+  if (batch != h->dtrack_B || !veh)
+    return fail(h, LMPC_ERR_ARGUMENT, std::string(who) + ": veh is NULL or batch " + std::to_string(batch) + " is not the table's " + std::to_string(h->dtrack_B));
+  HIP_TRY(h, hipSetDevice(h->device));
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  const size_t nd = lmpc_dtrack_doubles((size_t)batch);
+  std::vector<double> host(nd);
+  HIP_TRY_AS(h, who, hipMemcpy(host.data(), h->dtrack_tab.get(), nd * sizeof(double), hipMemcpyDeviceToHost));
+  lmpc_dtrack_unpack(host.data(), (size_t)batch, veh);
+  return LMPC_OK;
+}
+
+int lmpc_plant_step_dtrack_batch(lmpc_handle* h, int32_t batch, const lmpc_track* track, double* x, const double* u, double dt_sim,
+                                 int32_t n_sub, double* gamma_y_or_null) {
+  if (!h) return LMPC_ERR_ARGUMENT;
+  const char* who = "lmpc_plant_step_dtrack_batch";
+  if (!h->dtrack_B) return fail(h, LMPC_ERR_ARGUMENT, std::string(who) + ": no double-track table (lmpc_dtrack_set_vehicles)");
+  if (batch != h->dtrack_B)
+    return fail(h, LMPC_ERR_ARGUMENT, std::string(who) + ": batch " + std::to_string(batch) + " is not the table's " + std::to_string(h->dtrack_B));
+  if (!track_ok(track) || !x || !u || !(dt_sim > 0.0) || n_sub < 1) return fail(h, LMPC_ERR_ARGUMENT, std::string(who) + ": bad argument");
+  HIP_TRY(h, hipSetDevice(h->device));
+  HIP_TRY(h, lmpc_dtrack_launch_step(h->stream, h->dtrack_tab.get(), batch, *track, x, u, dt_sim, n_sub, gamma_y_or_null));
   return LMPC_OK;
 }
 

@@ -25,6 +25,20 @@ def iac_vehicle() -> dict:
                 max_steer=0.314159, max_steer_rate=0.66)
 
 
+def barc_double_track() -> dict:
+    """lmpc_vehicle_dt (include/lmpc_hip_dtrack.h) for the BARC car: barc_vehicle() with model_id 2 (LMPC_MODEL_DOUBLE_TRACK_PLANAR),
+    chassis.tw_f / tw_r and front_tyre / rear_tyre pacejka_e / pacejka_fz0 / pacejka_eps of barc_base.param.yaml, kroll_f = 0.5 (the
+    only value the reference ships, double_track_planar_model/param/sample_vehicle.param.yaml) and mu the single-track preset's."""
+    return dict(barc_vehicle(), model_id=2, tw_f=0.281, tw_r=0.281, kroll_f=0.5,
+                Ef=1.0, Fz0_f=1543.5, eps_f=-0.0813, Er=1.0, Fz0_r=1886.5, eps_r=-0.1263)
+
+
+def iac_double_track() -> dict:
+    """barc_double_track() for the IAC car, off iac_car_base.param.yaml."""
+    return dict(iac_vehicle(), model_id=2, tw_f=1.6, tw_r=1.6, kroll_f=0.5,
+                Ef=1.0, Fz0_f=1543.5, eps_f=-0.0813, Er=1.0, Fz0_r=1886.5, eps_r=-0.1263)
+
+
 def barc_tracking_mpc(N: int = 20) -> dict:
     return dict(N=N, learning=0, num_ss_pts=96, num_ss_pts_per_lap=32, max_lap_stored=3, max_iter=0, tol=0.0,
                 margin=0.1, q_contour=1.0, q_heading=1.0, q_vel=0.2, q_vy=1e-3, q_vyaw=1e-3, q_boundary=20.0,

@@ -17,7 +17,7 @@ from __future__ import annotations
 import math
 from pathlib import Path
 
-__all__ = ["load_ros_params", "vehicle_from_params", "mpc_config_from_params", "host_options_from_params",
+__all__ = ["load_ros_params", "vehicle_from_params", "double_track_vehicle_from_params", "mpc_config_from_params", "host_options_from_params",
            "vanilla_config_from_params"]
 
 
@@ -113,6 +113,35 @@ def vehicle_from_params(params: dict, model: str = "single_track_planar_model") 
                 Fd_max=f("single_track_planar.fd_max"), Fb_max=f("single_track_planar.fb_max"),
                 Td=f("single_track_planar.td"), Tb=f("single_track_planar.tb"),
                 max_steer=f("steer.max_steer"), max_steer_rate=f("steer.max_steer_rate"))
+
+
+def double_track_vehicle_from_params(params: dict) -> dict:
+    """lmpc_vehicle_dt fields (include/lmpc_hip_dtrack.h; presets.barc_double_track's keys) from the merged vehicle parameter files:
+    the base keys vehicle_from_params reads, the extras of the four-wheel model off the same base file (chassis.tw_f / tw_r,
+    front_tyre / rear_tyre pacejka_e / pacejka_fz0 / pacejka_eps) and the model's own double_track_planar.mu, kroll_f, fd_max,
+    fb_max, td and tb (double_track_planar_model/src/ros_param_loader.cpp:30-47).  Every one is mandatory, as there; the plant
+    carries the four actuator limits and does not read them.  double_track_planar.v_max and p_max, which the reference declares
+    beside them, bound rows of its NLP and are not required here."""
+    f = lambda k: _need(params, k, float)  # noqa: E731
+    if not _need(params, "modeling.use_frenet", bool):
+        raise NotImplementedError("modeling.use_frenet = false is not built (the plant is the Frenet model)")
+    integ = _need(params, "modeling.integrator_type", str)
+    if integ not in ("rk4", "euler"):
+        raise ValueError(f"Unknown integrator type: {integ}")
+    return dict(model_id=2, integrator=integ,
+                m=f("chassis.total_mass"), Jzz=f("chassis.moi"), l=f("chassis.wheel_base"),
+                cg_ratio=f("chassis.cg_ratio"), h=f("chassis.cg_height"), b=f("chassis.b"), fr=f("chassis.fr"),
+                kd=f("powertrain.kd"), kb=f("front_brake.bias"),
+                cd=f("aero.drag_coeff"), Af=f("aero.frontal_area"), rho=f("aero.air_density"),
+                cl_f=f("aero.cl_f"), cl_r=f("aero.cl_r"), mu=f("double_track_planar.mu"),
+                Bf=f("front_tyre.pacejka_b"), Cf=f("front_tyre.pacejka_c"),
+                Br=f("rear_tyre.pacejka_b"), Cr=f("rear_tyre.pacejka_c"),
+                Fd_max=f("double_track_planar.fd_max"), Fb_max=f("double_track_planar.fb_max"),
+                Td=f("double_track_planar.td"), Tb=f("double_track_planar.tb"),
+                max_steer=f("steer.max_steer"), max_steer_rate=f("steer.max_steer_rate"),
+                tw_f=f("chassis.tw_f"), tw_r=f("chassis.tw_r"), kroll_f=f("double_track_planar.kroll_f"),
+                Ef=f("front_tyre.pacejka_e"), Fz0_f=f("front_tyre.pacejka_fz0"), eps_f=f("front_tyre.pacejka_eps"),
+                Er=f("rear_tyre.pacejka_e"), Fz0_r=f("rear_tyre.pacejka_fz0"), eps_r=f("rear_tyre.pacejka_eps"))
 
 
 def mpc_config_from_params(params: dict, horizon: int | None = None) -> dict:
