@@ -965,6 +965,9 @@ int lmpc_vanilla_rollout_batch(lmpc_handle* h, int32_t batch, const lmpc_spline_
                                int32_t periods, double dt_sim, int32_t n_sub, double speed_scale, double* X_log, double* U_log, double* k_log,
                                double* distance, double* worst_excess, int32_t* flags);
 
+/* The rollout of a fleet: a plant per car and the fleet recorder in the period loop (behind the types its prototype names). */
+#include "lmpc_hip_vanilla_fleet.h"
+
 #ifdef __cplusplus
 }
 #endif

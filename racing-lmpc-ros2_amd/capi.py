@@ -41,6 +41,10 @@ _ABI_SYMBOLS_ROWS = ("lmpc_set_regression_laps_rows", "lmpc_fleet_ss_set_regress
 _ABI_SYMBOLS_CARS = ("lmpc_cars_set_vehicles", "lmpc_cars_get_vehicles", "lmpc_plant_step_cars_batch")
 # the entry points of include/lmpc_hip_dtrack.h (the double-track plant), resolved at load time in a loop of their own
 _ABI_SYMBOLS_DTRACK = ("lmpc_dtrack_set_vehicles", "lmpc_dtrack_get_vehicles", "lmpc_plant_step_dtrack_batch")
+# the entry point of include/lmpc_hip_vanilla_fleet.h (the vanilla rollout of a fleet), resolved at load time in a loop of its own
+_ABI_SYMBOLS_VANILLA_FLEET = ("lmpc_vanilla_rollout_fleet_batch",)
+VANILLA_PLANT = {"handle": 0, "cars": 1, "dtrack": 2}           # LMPC_VANILLA_PLANT_*
+VANILLA_RECORD = {None: 0, "applied": 1, "arrived": 2}          # LMPC_VANILLA_RECORD_*
 EKF_FALLBACK, EKF_R_REPAIRED, EKF_NOT_FINITE = 1, 2, 4   # bits of the per-car flags of Solver.ekf_update
 LQR_NOT_FINITE = 1   # per-car flag of Solver.lqr_solve: the car's X_optm, U_optm, K or P0 holds a NaN or Inf
 VANILLA_NOT_FINITE = 1   # per-car flag of Solver.vanilla_solve / vanilla_rollout: u_out (rollout: or the state after the plant) holds a NaN or Inf
@@ -139,6 +143,14 @@ class CVanillaConfig(C.Structure):
                                           "min_i max_i dt force_to_lon").split()]
 
 
+class CVanillaFleetRollout(C.Structure):
+    """lmpc_vanilla_fleet_rollout of include/lmpc_hip_vanilla_fleet.h: everything lmpc_vanilla_rollout_fleet_batch takes beside the
+    handle, the batch, the spline track and the table."""
+    _fields_ = ([("x", C.c_void_p), ("u_prev", C.c_void_p)] + [(n, C.c_int32) for n in "periods n_sub plant record".split()]
+                + [("dt_sim", C.c_double), ("speed_scale", C.c_double), ("period0", C.c_int64), ("dt", C.c_double)]
+                + [(n, C.c_void_p) for n in "X_log U_log k_log distance worst_excess flags".split()])
+
+
 class CTrack(C.Structure):
     _fields_ = [("L", C.c_double), ("M", C.c_int32), ("reserved", C.c_int32),
                 ("curvature", C.c_void_p), ("bound_left", C.c_void_p), ("bound_right", C.c_void_p),
@@ -186,6 +198,8 @@ def load_library():
         for sym in _ABI_SYMBOLS_CARS:
             getattr(lib, sym)
         for sym in _ABI_SYMBOLS_DTRACK:
+            getattr(lib, sym)
+        for sym in _ABI_SYMBOLS_VANILLA_FLEET:
             getattr(lib, sym)
         lib.lmpc_last_error.restype = C.c_char_p
         lib.lmpc_last_error.argtypes = [C.c_void_p]
@@ -1262,4 +1276,41 @@ class Solver:
                                                  _ptr(out.get("X_log")), _ptr(out.get("U_log")), _ptr(out.get("k_log")), _ptr(distance),
                                                  _ptr(worst_excess), _ptr(out.get("flags")))
         self._check(rc, "lmpc_vanilla_rollout_batch")
+        return out
+
+    def vanilla_rollout_fleet(self, track: SplineTrack, table: dict, x, periods: int, dt_sim: float, n_sub: int = 1, *, plant: str = "handle",
+                              record=None, period0: int = 0, dt=None, u_prev=None, speed_scale: float = 1.0, logs: bool = False,
+                              distance=None, worst_excess=None, out=None):
+        """lmpc_vanilla_rollout_fleet_batch: vanilla_rollout with a plant per car and the fleet safe set's recorder inside the period
+        loop, ONE launch for `periods` control periods.  plant: "handle" (this solver's vehicle: vanilla_rollout's plant, bit for bit),
+        "cars" (car b on vehicle b of set_car_vehicles' table) or "dtrack" (car b on four-wheel vehicle b of set_dtrack_vehicles'
+        table); the decision reads this solver's vehicle whatever the plant.  record: None, "applied" (sample p = the state of period
+        p and the input applied from it, run_vanilla's convention) or "arrived" (the input that led to it, what fleet_loop_advance
+        records; period 0 takes u_prev); the samples of live periods go to the fleet store (fleet_ss_create) with the time stamp
+        (period0 + p) * dt.  u_prev (float64 [2][B], updated in place where given): on return the last input applied.  x [6][B] is
+        updated in place, as is the PID state.  Returns vanilla_rollout's dictionary ("X_log", "U_log", "k_log" only with logs=True);
+        `out` reuses buffers, a None or missing entry is not asked of the kernel.  Asynchronous."""
+        torch = self._torch
+        self.use_current_stream()
+        if x.dim() != 2 or x.shape[0] != 6 or x.dtype != torch.float64 or not x.is_contiguous():
+            raise ValueError("vanilla_rollout_fleet: x is a contiguous float64 [6][B] device tensor (it is updated in place)")
+        B, P = x.shape[1], int(periods)
+        if u_prev is not None and (tuple(u_prev.shape) != (2, B) or u_prev.dtype != torch.float64 or not u_prev.is_contiguous()):
+            raise ValueError("vanilla_rollout_fleet: u_prev is a contiguous float64 [2][B] device tensor (it is updated in place)")
+        if plant not in VANILLA_PLANT or record not in VANILLA_RECORD:
+            raise ValueError("vanilla_rollout_fleet: plant is one of %s, record one of %s" % (sorted(VANILLA_PLANT), list(VANILLA_RECORD)))
+        ct = self._ctrack(table)
+        if out is None:
+            kw = dict(dtype=torch.float64, device=self.device)
+            out = {"flags": torch.empty((B,), dtype=torch.int32, device=self.device)}
+            if logs and P >= 1:
+                out.update(X_log=torch.empty((6, P, B), **kw), U_log=torch.empty((2, P, B), **kw), k_log=torch.empty((P, B), **kw))
+        io = CVanillaFleetRollout()
+        io.x, io.u_prev = _ptr(x), _ptr(u_prev)
+        io.periods, io.n_sub, io.plant, io.record = P, int(n_sub), VANILLA_PLANT[plant], VANILLA_RECORD[record]
+        io.dt_sim, io.speed_scale, io.period0, io.dt = float(dt_sim), float(speed_scale), int(period0), 0.0 if dt is None else float(dt)
+        io.X_log, io.U_log, io.k_log = _ptr(out.get("X_log")), _ptr(out.get("U_log")), _ptr(out.get("k_log"))
+        io.distance, io.worst_excess, io.flags = _ptr(distance), _ptr(worst_excess), _ptr(out.get("flags"))
+        rc = self.lib.lmpc_vanilla_rollout_fleet_batch(self._h, C.c_int32(B), track._p if track is not None else None, C.byref(ct), C.byref(io))
+        self._check(rc, "lmpc_vanilla_rollout_fleet_batch")
         return out

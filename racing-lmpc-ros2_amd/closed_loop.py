@@ -422,7 +422,8 @@ class _DtrackPlant:
 
 def run_lmpc_fleet(tracker, learner, track: dict, x0, u0, warm_laps: int = 2, learn_laps: int = 4, dt: float = 0.025,
                    n_sub: int = 2, warm_speed_scale: float = 0.7, max_steps: int = 20000, max_pts_per_lap: int = 1024,
-                   record_trace: bool = False, regression: dict | None = None, plant=None, plants=None, plants_dt=None):
+                   record_trace: bool = False, regression: dict | None = None, plant=None, plants=None, plants_dt=None,
+                   warmup: dict | None = None, _warm_plant: str = "handle"):
     """run_lmpc with every car learning from ITS OWN laps: the fleet safe set on `learner` (lmpc_fleet_ss_*: one recorder and one
     ring of max_lap_stored laps per car, on the device) replaces the host recorder of car 0 and the shared store.  Per period, in
     run_lmpc's order: record (x, u_prev, curvature at s, t) for all cars, query every learning car's own ring, solve, plant step,
@@ -448,11 +449,17 @@ def run_lmpc_fleet(tracker, learner, track: dict, x0, u0, warm_laps: int = 2, le
     plants_dt (a list of B double-track vehicle dicts, presets.barc_double_track's keys; exclusive with plant= and plants=): car b
     drives on the FOUR-WHEEL model with plants_dt[b] while the controllers stay single-track -- the list becomes `learner`'s
     double-track table (Solver.set_dtrack_vehicles) for the run, every period steps with its plant_step_dtrack, and the table is
-    cleared at the end."""
+    cleared at the end.
+    warmup (a dict, _fleet_warm_up's): the warm laps are driven by the vanilla controller on the run's own plants in a few launches
+    (warm_up_vanilla) instead of by the tracking controller; the loop starts where they end, with its clock at their end, and
+    "lap_times" / "lap_kind" list only the laps closed after them, and "warmup" = {"periods", "t_end", "lap_count"} says where they
+    ended.  None: the run as it always was."""
     import numpy as np
     import torch
 
     B = x0.shape[1]
+    if warmup is not None and plant is not None and _warm_plant == "handle":
+        raise ValueError("run_lmpc_fleet: warmup= drives the warm laps on the learner's vehicle, plants= or plants_dt=, not on plant=")
     if plants_dt is not None:
         if plants is not None:
             raise ValueError("run_lmpc_fleet: plants= (single-track cars) and plants_dt= (double-track cars) are exclusive")
@@ -460,7 +467,7 @@ def run_lmpc_fleet(tracker, learner, track: dict, x0, u0, warm_laps: int = 2, le
         learner.set_dtrack_vehicles(plants_dt)
         try:
             return run_lmpc_fleet(tracker, learner, track, x0, u0, warm_laps, learn_laps, dt, n_sub, warm_speed_scale, max_steps, max_pts_per_lap,
-                                  record_trace, regression, plant=_DtrackPlant(learner))
+                                  record_trace, regression, plant=_DtrackPlant(learner), warmup=warmup, _warm_plant="dtrack")
         finally:
             learner.set_dtrack_vehicles(None)
     _check_plants(plant, plants, B, "run_lmpc_fleet")
@@ -468,7 +475,7 @@ def run_lmpc_fleet(tracker, learner, track: dict, x0, u0, warm_laps: int = 2, le
         learner.set_car_vehicles(plants)
         try:
             return run_lmpc_fleet(tracker, learner, track, x0, u0, warm_laps, learn_laps, dt, n_sub, warm_speed_scale, max_steps, max_pts_per_lap,
-                                  record_trace, regression, plant=_CarsPlant(learner))
+                                  record_trace, regression, plant=_CarsPlant(learner), warmup=warmup, _warm_plant="cars")
         finally:
             learner.set_car_vehicles(None)
     trk = tracker.device_track(track)
@@ -478,6 +485,10 @@ def run_lmpc_fleet(tracker, learner, track: dict, x0, u0, warm_laps: int = 2, le
     if regression is not None:
         learner.fleet_ss_set_regression(**regression)
     x, u_prev = x0.clone(), u0.clone()
+    t_start, laps_before, warmed = 0.0, np.zeros(B, dtype=np.int64), {}
+    if warmup is not None:
+        x, u_prev, t_start, laps_before = _fleet_warm_up(learner, trk, x, u_prev, warm_laps, dt, n_sub, warmup, _warm_plant)
+        warmed = {"warmup": {"periods": int(round(t_start / dt)), "t_end": t_start, "lap_count": laps_before}}
     half_b = float(tracker.vehicle["b"]) / 2.0
     worst_excess = torch.zeros(B, dtype=torch.float64, device=dev)
     n_fail = torch.zeros(B, dtype=torch.int64, device=dev)
@@ -493,7 +504,7 @@ def run_lmpc_fleet(tracker, learner, track: dict, x0, u0, warm_laps: int = 2, le
     x_hi = torch.as_tensor(learner.config["x_max"], dtype=torch.float64, device=dev)[:, None]
     keys = ("X_ref", "U_ref", "T_ref", "bound_left", "bound_right", "curvatures", "vel_ref")
     # device bookkeeping of the laps: slot i of car b is its i-th closed lap
-    n_rec = warm_laps + learn_laps + 8
+    n_rec = warm_laps + learn_laps + 8 + int(laps_before.max())   # (the laps of a warm-up keep their slots: none after them is lost)
     lap_time = torch.zeros((n_rec, B), dtype=torch.float64, device=dev)
     lap_learn = torch.zeros((n_rec, B), dtype=torch.bool, device=dev)
     n_learn = torch.zeros(B, dtype=torch.int64, device=dev)
@@ -501,9 +512,9 @@ def run_lmpc_fleet(tracker, learner, track: dict, x0, u0, warm_laps: int = 2, le
     small = torch.zeros((2, B), dtype=torch.int32, device=dev)   # what the host reads: laps_in_ring, done
     stats = {"laps_in_ring": small[0], "lap_count": torch.zeros(B, dtype=torch.int32, device=dev),
              "n_dropped": torch.zeros(B, dtype=torch.int32, device=dev), "last_lap_time": torch.zeros(B, dtype=torch.float64, device=dev)}
-    count_prev = torch.zeros(B, dtype=torch.int32, device=dev)
+    count_prev = torch.as_tensor(laps_before, dtype=torch.int32, device=dev)
     learning = np.zeros(B, dtype=bool)   # host mirror of learning_d
-    trace, t, k = [], 0.0, -1
+    trace, t, k = [], t_start, -1
     for k in range(max_steps):
         # x_ic by the phase the car was in BEFORE this period's sample (run_lmpc sets it before its recorder step): learning cars get
         # the measured state projected onto the state box
@@ -572,16 +583,18 @@ def run_lmpc_fleet(tracker, learner, track: dict, x0, u0, warm_laps: int = 2, le
         t += dt
     learner.fleet_ss_stats(B, out=stats)
     n_closed = np.minimum(np.maximum(count_prev.cpu().numpy() - 1, 0), n_rec)
+    skip = np.maximum(laps_before - 1, 0)   # the laps a warm-up closed
     lt, lk = lap_time.cpu().numpy(), lap_learn.cpu().numpy()
-    return {"lap_times": [[float(v) for v in lt[:n_closed[b], b]] for b in range(B)],
-            "lap_kind": [["lmpc" if v else "tracking" for v in lk[:n_closed[b], b]] for b in range(B)],
+    return {"lap_times": [[float(v) for v in lt[skip[b]:n_closed[b], b]] for b in range(B)],
+            "lap_kind": [["lmpc" if v else "tracking" for v in lk[skip[b]:n_closed[b], b]] for b in range(B)],
             "worst_excess": worst_excess, "n_fail": n_fail, "n_dropped": stats["n_dropped"].clone(),
-            "laps_in_ring": stats["laps_in_ring"].clone(), "steps": k + 1, "x": x, "trace": trace}
+            "laps_in_ring": stats["laps_in_ring"].clone(), "steps": k + 1, "x": x, "trace": trace, **warmed}
 
 
 def run_lmpc_fleet_fused(tracker, learner, track: dict, x0, u0, warm_laps: int = 2, learn_laps: int = 4, dt: float = 0.025,
                          n_sub: int = 2, warm_speed_scale: float = 0.7, max_steps: int = 20000, max_pts_per_lap: int = 1024,
-                         record_trace: bool = False, regression: dict | None = None, plant=None, poll: int = 1, plants=None):
+                         record_trace: bool = False, regression: dict | None = None, plant=None, poll: int = 1, plants=None,
+                         warmup: dict | None = None, _warm_plant: str = "handle"):
     """run_lmpc_fleet with everything between two solves in one launch, lmpc_fleet_loop_advance_batch on `learner`: input selection
     between the two controllers' results, plant, shift, x_ic, every car's recorder and ring, the lap book, the per-car phase and the
     next query point.  Same arguments, same experiment, same return dictionary; per period the fleet query when any car learns, the
@@ -597,6 +610,8 @@ def run_lmpc_fleet_fused(tracker, learner, track: dict, x0, u0, warm_laps: int =
     (x, u, k, t) tuples is run_lmpc_fleet's torch interpolation; the ring holds the kernel's own lookup at the same abscissa.
     plants (a list of B vehicle dicts, exclusive with plant=): car b drives on plants[b] -- the list is `learner`'s car table
     (Solver.set_car_vehicles) for the run, which the fused call reads, and the table is cleared at the end.
+    warmup (a dict, _fleet_warm_up's): run_lmpc_fleet's -- the warm laps by the vanilla controller on the run's own plants; the
+    head-only call then sends every car whose ring holds warm_laps laps straight to the learning controller.
     Raises ValueError when the two solvers differ in N or vehicle: one launch shifts both controllers' plans with one model."""
     import numpy as np
     import torch
@@ -607,11 +622,13 @@ def run_lmpc_fleet_fused(tracker, learner, track: dict, x0, u0, warm_laps: int =
         raise ValueError("run_lmpc_fleet_fused: poll must be >= 1")
     B = x0.shape[1]
     _check_plants(plant, plants, B, "run_lmpc_fleet_fused")
+    if warmup is not None and plant is not None:
+        raise ValueError("run_lmpc_fleet_fused: warmup= drives the warm laps on the learner's vehicle or plants=, not on plant=")
     if plants is not None:
         learner.set_car_vehicles(plants)
         try:
             return run_lmpc_fleet_fused(tracker, learner, track, x0, u0, warm_laps, learn_laps, dt, n_sub, warm_speed_scale, max_steps,
-                                        max_pts_per_lap, record_trace, regression, None, poll)
+                                        max_pts_per_lap, record_trace, regression, None, poll, warmup=warmup, _warm_plant="cars")
         finally:
             learner.set_car_vehicles(None)
     trk = tracker.device_track(track)
@@ -621,6 +638,10 @@ def run_lmpc_fleet_fused(tracker, learner, track: dict, x0, u0, warm_laps: int =
     if regression is not None:
         learner.fleet_ss_set_regression(**regression)
     x, u_prev = x0.clone(), u0.clone()
+    t_start, laps_before, warmed = 0.0, np.zeros(B, dtype=np.int64), {}
+    if warmup is not None:
+        x, u_prev, t_start, laps_before = _fleet_warm_up(learner, trk, x, u_prev, warm_laps, dt, n_sub, warmup, _warm_plant)
+        warmed = {"warmup": {"periods": int(round(t_start / dt)), "t_end": t_start, "lap_count": laps_before}}
     worst_excess = torch.zeros(B, dtype=torch.float64, device=dev)
     n_fail = torch.zeros(B, dtype=torch.int64, device=dev)
     inp = tracker.prepare(trk, x, dt, speed_scale=warm_speed_scale)
@@ -629,7 +650,7 @@ def run_lmpc_fleet_fused(tracker, learner, track: dict, x0, u0, warm_laps: int =
     out_l["convex_combi_optm"] = torch.zeros((S, B), dtype=torch.float64, device=dev)
     ss_buf = (torch.zeros((6, S, B), dtype=torch.float64, device=dev), torch.zeros((S, B), dtype=torch.float64, device=dev),
               torch.zeros((B,), dtype=torch.int32, device=dev))
-    n_rec = warm_laps + learn_laps + 8
+    n_rec = warm_laps + learn_laps + 8 + int(laps_before.max())   # (the laps of a warm-up keep their slots: none after them is lost)
     state = learner.fleet_loop_state(B, n_rec)
     kw = dict(dt=dt, dt_sim=dt / n_sub, n_sub=n_sub, speed_scale=(warm_speed_scale, 1.0),
               speed_limit=(float(tracker.config["x_max"][3]), float(learner.config["x_max"][3])),
@@ -638,7 +659,7 @@ def run_lmpc_fleet_fused(tracker, learner, track: dict, x0, u0, warm_laps: int =
               worst_excess=worst_excess, n_fail=n_fail)
     curv = trk["curvature"]
     M = int(curv.numel())
-    trace, t, k = [], 0.0, -1
+    trace, t, k = [], t_start, -1
 
     def note():
         pos = torch.remainder(x[0], L) * (M / L)
@@ -670,11 +691,12 @@ def run_lmpc_fleet_fused(tracker, learner, track: dict, x0, u0, warm_laps: int =
             note()
     stats = learner.fleet_ss_stats(B)
     n_closed = np.minimum(np.maximum(stats["lap_count"].cpu().numpy() - 1, 0), n_rec)
+    skip = np.maximum(laps_before - 1, 0)   # the laps a warm-up closed
     lt, lk = state["lap_time"].cpu().numpy(), state["lap_kind"].cpu().numpy()
-    return {"lap_times": [[float(v) for v in lt[:n_closed[b], b]] for b in range(B)],
-            "lap_kind": [["lmpc" if v else "tracking" for v in lk[:n_closed[b], b]] for b in range(B)],
+    return {"lap_times": [[float(v) for v in lt[skip[b]:n_closed[b], b]] for b in range(B)],
+            "lap_kind": [["lmpc" if v else "tracking" for v in lk[skip[b]:n_closed[b], b]] for b in range(B)],
             "worst_excess": worst_excess, "n_fail": n_fail, "n_dropped": stats["n_dropped"], "laps_in_ring": stats["laps_in_ring"],
-            "steps": k + 1, "x": x, "trace": trace}
+            "steps": k + 1, "x": x, "trace": trace, **warmed}
 
 
 def run_lqr(solver, x0, X_traj, U_traj, steps: int):
@@ -801,3 +823,89 @@ def run_vanilla(solver, track: dict, spline, x0, steps: int, dt: float = 0.025, 
                 record(p, p + 1)
     return {"x": x, "distance": dist, "worst_excess": worst, "n_fail": torch.isnan(k_log).sum(dim=0).to(torch.int64), "trace": [],
             "warm_hit_rate": None, "flags": flags, "X_log": X_log, "U_log": U_log, "k_log": k_log}
+
+
+def _warm_up_chunks(solver, trk, spline, x, u_prev, laps: int, dt: float, n_sub: int, speed_scale: float, chunk: int, max_periods: int,
+                    plant: str, record):
+    """warm_up_vanilla's loop on tables that are already set: x and u_prev are updated in place."""
+    import torch
+
+    B, dev = x.shape[1], x.device
+    kw = dict(dtype=torch.float64, device=dev)
+    dist, worst = torch.zeros(B, **kw), torch.full((B,), -float("inf"), **kw)
+    flags = torch.zeros(B, dtype=torch.int32, device=dev)
+    out, stats, periods = None, None, 0
+    while periods < max_periods:
+        n = min(chunk, max_periods - periods)
+        out = solver.vanilla_rollout_fleet(spline, trk, x, n, dt / n_sub, n_sub, plant=plant, record=record, period0=periods, dt=dt, u_prev=u_prev,
+                                           speed_scale=speed_scale, distance=dist, worst_excess=worst, out=out if n == chunk else None)
+        flags |= out["flags"]
+        periods += n
+        stats = solver.fleet_ss_stats(B, out=stats)
+        if int(stats["laps_in_ring"].min()) >= laps:   # the chunk's one read
+            break
+    if stats is None:
+        stats = solver.fleet_ss_stats(B)
+    return {"x": x, "u_prev": u_prev, "periods": periods, "t_end": periods * dt, "flags": flags, "distance": dist, "worst_excess": worst,
+            "laps_in_ring": stats["laps_in_ring"].clone(), "lap_count": stats["lap_count"].clone()}
+
+
+def warm_up_vanilla(solver, track: dict, spline, x0, u0, laps: int, dt: float = 0.025, n_sub: int = 2, speed_scale: float = 1.0, chunk: int = 64,
+                    max_periods: int = 4096, plants=None, plants_dt=None, record="arrived"):
+    """The first laps of a fleet LMPC experiment without a QP: the vanilla controller (pure pursuit + PID) drives every car ON ITS OWN
+    PLANT and every car's recorder takes its samples inside the same launch (Solver.vanilla_rollout_fleet), `chunk` periods per
+    launch, until every car's ring holds `laps` laps or `max_periods` periods have been driven.  Every car drives the same number of
+    periods -- the fleet shares one clock -- and the host reads one fleet_ss_stats per chunk.
+
+    The caller has made the controllers (solver.vanilla_create for B cars; the PID state is used as it stands) and the fleet store
+    (solver.fleet_ss_create).  `track` holds the uniform tables, `spline` is Solver.spline_track of the same track; x0 [6][B], u0
+    [2][B] the input applied before the first period (the "arrived" convention records it with x0).  plants (B vehicle dicts) /
+    plants_dt (B double-track vehicle dicts), exclusive: car b's plant; the list is the solver's car table / double-track table for
+    the call and the table is cleared at the end, as run_lmpc_fleet does.  Neither: the solver's vehicle.  record: "arrived" (what the
+    LMPC loop records: continue with fleet_loop_advance at t_end) or "applied" (run_vanilla's convention).
+
+    Returns {"x" [6][B], "u_prev" [2][B] the last input applied, "periods", "t_end" = periods * dt (the time stamp of the next sample),
+    "flags" int32 [B] (the OR over the chunks: VANILLA_NOT_FINITE), "distance" [B], "worst_excess" [B] (from -inf), "laps_in_ring" [B]}."""
+    if getattr(solver, "_vanilla_B", None) is None:
+        raise ValueError("warm_up_vanilla: no controller (Solver.vanilla_create)")
+    if chunk < 1 or max_periods < 1:
+        raise ValueError("warm_up_vanilla: chunk and max_periods must be at least 1")
+    x, u_prev = solver._t(x0).clone(), solver._t(u0).clone()
+    B = x.shape[1]
+    if plants is not None and plants_dt is not None:
+        raise ValueError("warm_up_vanilla: plants= (single-track cars) and plants_dt= (double-track cars) are exclusive")
+    _check_plants(None, plants if plants is not None else plants_dt, B, "warm_up_vanilla", "plants" if plants is not None else "plants_dt")
+    trk = solver.device_track(track)
+    plant = "cars" if plants is not None else "dtrack" if plants_dt is not None else "handle"
+    if plants is not None:
+        solver.set_car_vehicles(plants)
+    if plants_dt is not None:
+        solver.set_dtrack_vehicles(plants_dt)
+    try:
+        res = _warm_up_chunks(solver, trk, spline, x, u_prev, laps, dt, n_sub, speed_scale, chunk, max_periods, plant, record)
+    finally:
+        if plants is not None:
+            solver.set_car_vehicles(None)
+        if plants_dt is not None:
+            solver.set_dtrack_vehicles(None)
+    res.pop("lap_count")
+    return res
+
+
+def _fleet_warm_up(learner, trk, x, u_prev, warm_laps: int, dt: float, n_sub: int, warmup: dict, plant: str):
+    """warmup= of run_lmpc_fleet and run_lmpc_fleet_fused, after the store is made and the run's table is set: the vanilla controllers
+    are made on `learner`, the warm laps are driven on the run's plants and recorded by the loop's convention.  warmup: "config" (the
+    vanilla controller's, Solver.vanilla_create's dict) and "spline" (Solver.spline_track of the run's track on `learner`, or the
+    dict it is made from), and optionally warm_up_vanilla's "laps" (default: warm_laps), "speed_scale", "chunk", "max_periods".
+    -> (x, u_prev, t_end, the recorders' lap_count [B] as a host array)."""
+    unknown = set(warmup) - {"config", "spline", "laps", "speed_scale", "chunk", "max_periods"}
+    if unknown or "config" not in warmup or "spline" not in warmup:
+        raise ValueError("warmup= takes config, spline and optionally laps, speed_scale, chunk, max_periods; got %s" % sorted(warmup))
+    spline = warmup["spline"]
+    if isinstance(spline, dict):
+        spline = learner.spline_track(spline)
+    learner.vanilla_create(warmup["config"], x.shape[1])
+    res = _warm_up_chunks(learner, trk, spline, x, u_prev, int(warmup.get("laps", warm_laps)), dt, n_sub, float(warmup.get("speed_scale", 1.0)),
+                          int(warmup.get("chunk", 64)), int(warmup.get("max_periods", 4096)), plant, "arrived")
+    learner.vanilla_destroy()
+    return res["x"], res["u_prev"], res["t_end"], res["lap_count"].cpu().numpy().astype("int64")

@@ -2534,4 +2534,49 @@ int lmpc_vanilla_rollout_batch(lmpc_handle* h, int32_t batch, const lmpc_spline_
   return LMPC_OK;
 }
 
+// the rollout of a fleet: a plant per car, the fleet recorder in the period loop (include/lmpc_hip_vanilla_fleet.h)
+int lmpc_vanilla_rollout_fleet_batch(lmpc_handle* h, int32_t batch, const lmpc_spline_track* track, const lmpc_track* table,
+                                     const lmpc_vanilla_fleet_rollout* io) {
+  if (!h) return LMPC_ERR_ARGUMENT;
+  const std::string who = "lmpc_vanilla_rollout_fleet_batch";
+  int rc = vanilla_check(h, batch, who.c_str());
+  if (rc != LMPC_OK) return rc;
+  rc = spline_track_check(h, track, who.c_str());
+  if (rc != LMPC_OK) return rc;
+  if (!track_ok(table)) return fail(h, LMPC_ERR_ARGUMENT, who + ": null or empty track table");
+  if (!io || !io->x) return fail(h, LMPC_ERR_ARGUMENT, who + ": io or io->x is NULL");
+  if (io->periods < 1 || io->n_sub < 1) return fail(h, LMPC_ERR_ARGUMENT, who + ": periods and n_sub must be at least 1");
+  if (!(io->dt_sim > 0.0) || !std::isfinite(io->dt_sim)) return fail(h, LMPC_ERR_ARGUMENT, who + ": dt_sim must be positive and finite");
+  if (io->plant != LMPC_VANILLA_PLANT_HANDLE && io->plant != LMPC_VANILLA_PLANT_CARS && io->plant != LMPC_VANILLA_PLANT_DTRACK)
+    return fail(h, LMPC_ERR_ARGUMENT, who + ": plant is none of LMPC_VANILLA_PLANT_HANDLE, _CARS, _DTRACK");
+  if (io->record != LMPC_VANILLA_RECORD_NONE && io->record != LMPC_VANILLA_RECORD_APPLIED && io->record != LMPC_VANILLA_RECORD_ARRIVED)
+    return fail(h, LMPC_ERR_ARGUMENT, who + ": record is none of LMPC_VANILLA_RECORD_NONE, _APPLIED, _ARRIVED");
+  if (io->period0 < 0) return fail(h, LMPC_ERR_ARGUMENT, who + ": period0 is negative");
+  lmpc_vanilla_fleet_io fx{nullptr, io->u_prev, io->record == LMPC_VANILLA_RECORD_ARRIVED, (long long)io->period0, io->dt};
+  if (io->plant == LMPC_VANILLA_PLANT_CARS) {
+    if (!h->cars_B) return fail(h, LMPC_ERR_ARGUMENT, who + ": no car table (lmpc_cars_set_vehicles)");
+    if (h->cars_B != batch)
+      return fail(h, LMPC_ERR_ARGUMENT, who + ": batch " + std::to_string(batch) + " is not the car table's " + std::to_string(h->cars_B));
+    fx.table = h->cars_tab.get();
+  } else if (io->plant == LMPC_VANILLA_PLANT_DTRACK) {
+    if (!h->dtrack_B) return fail(h, LMPC_ERR_ARGUMENT, who + ": no double-track table (lmpc_dtrack_set_vehicles)");
+    if (h->dtrack_B != batch)
+      return fail(h, LMPC_ERR_ARGUMENT, who + ": batch " + std::to_string(batch) + " is not the double-track table's " + std::to_string(h->dtrack_B));
+    fx.table = h->dtrack_tab.get();
+  }
+  const bool record = io->record != LMPC_VANILLA_RECORD_NONE;
+  if (record) {
+    rc = fleet_check(h, batch, who.c_str());
+    if (rc != LMPC_OK) return rc;
+    if (!(io->dt > 0.0) || !std::isfinite(io->dt)) return fail(h, LMPC_ERR_ARGUMENT, who + ": dt must be positive and finite when recording");
+    if (fx.arrived && !io->u_prev) return fail(h, LMPC_ERR_ARGUMENT, who + ": LMPC_VANILLA_RECORD_ARRIVED needs u_prev");
+  }
+  HIP_TRY(h, hipSetDevice(h->device));
+  if (record) h->fleet_L = table->L;  // what the query unrolls the laps by, as lmpc_fleet_ss_record_batch notes it
+  const lmpc_vanilla_rollout_io rio{io->x, io->X_log, io->U_log, io->k_log, io->distance, io->worst_excess, io->flags};
+  HIP_TRY(h, lmpc_vanilla_launch_fleet(h->stream, h->vanilla, h->P.veh, track->view, *table, batch, io->periods, io->dt_sim, io->n_sub,
+                                       io->speed_scale, rio, io->plant, record, fx, h->fleet));
+  return LMPC_OK;
+}
+
 }  // extern "C"

@@ -19,6 +19,7 @@
 #include <hip/hip_runtime.h>
 
 #include "lmpc_device.h"
+#include "lmpc_fleet_ss.h"
 #include "lmpc_track.hip.h"
 
 #define LMPC_VANILLA_GRAVITY 9.81  // vanilla_controller.cpp:27 -- that file's own constant, not the model's 9.8
@@ -39,6 +40,14 @@ struct lmpc_vanilla_rollout_io {  // the caller's arrays, batch fastest; every p
   int* flags;            // [B]
 };
 
+struct lmpc_vanilla_fleet_io {  // what lmpc_vanilla_rollout_fleet_batch adds to the rollout (include/lmpc_hip_vanilla_fleet.h)
+  const double* table;   // the car table (csrc/lmpc_cars.h) or the double-track table (csrc/lmpc_dtrack.h) of B cars; null: the handle's vehicle
+  double* u_prev;        // [2][B] or null: in (where arrived), the input applied before period 0; out, the last input applied
+  int arrived;           // the recorder takes the input that led TO the sample (else the one applied FROM it)
+  long long period0;     // sample p is stamped (double)(period0 + p) * dt
+  double dt;
+};
+
 // Defined in lmpc_vanilla_kernel.hip, a translation unit of its own.  One launch each on `stream`.
 __attribute__((visibility("hidden"))) hipError_t lmpc_vanilla_launch_solve(hipStream_t stream, const lmpc_vanilla_store& st, const lmpc_vehicle& veh,
                                                                            const lmpc_spline_view& track, int batch, const double* x_ic,
@@ -48,5 +57,11 @@ __attribute__((visibility("hidden"))) hipError_t lmpc_vanilla_launch_rollout(hip
                                                                              const lmpc_spline_view& track, const lmpc_track& table, int batch,
                                                                              int periods, double dt_sim, int n_sub, double speed_scale,
                                                                              const lmpc_vanilla_rollout_io& io);
+// plant: LMPC_VANILLA_PLANT_*; record: whether `fs` (car b's recorder and ring, of `batch` cars) is fed
+__attribute__((visibility("hidden"))) hipError_t lmpc_vanilla_launch_fleet(hipStream_t stream, const lmpc_vanilla_store& st, const lmpc_vehicle& veh,
+                                                                           const lmpc_spline_view& track, const lmpc_track& table, int batch,
+                                                                           int periods, double dt_sim, int n_sub, double speed_scale,
+                                                                           const lmpc_vanilla_rollout_io& io, int plant, bool record,
+                                                                           const lmpc_vanilla_fleet_io& fx, const lmpc_fleet_store& fs);
 
 #endif  // LMPC_VANILLA_H_

@@ -3,10 +3,12 @@
 // and the kernel that runs controller and plant for many control periods in one launch.  See lmpc_vanilla.h and, for the formulas,
 // lmpc_vanilla_create in include/lmpc_hip.h.
 //
-// Two kernels, both __launch_bounds__(64), ONE LANE PER CAR, fp64:
+// Three kernels, all __launch_bounds__(64), ONE LANE PER CAR, fp64:
 //   lmpc_vanilla_solve_kernel    one control decision per car; reads and writes the PID state
 //   lmpc_vanilla_rollout_kernel  `periods` control periods per car: the decision, then n_sub plant sub-steps (the arithmetic of
 //                                lmpc_plant_kernel), logs and accumulators; x and the PID state are updated in place
+//   lmpc_vanilla_fleet_kernel    the rollout with a plant per car and the fleet safe set's recorder in the period loop
+//                                (include/lmpc_hip_vanilla_fleet.h), a template over (plant kind, recording on / off)
 // The work is a serial chain per car -- two spline evaluations, a handful of transcendental calls, and in the rollout 4 n_sub model
 // evaluations per period, each waiting for the last -- and the only parallelism is across cars.  A workgroup is one wave so that
 // 4096 cars are 64 workgroups on 64 CUs instead of 16 workgroups of four waves on 16; nothing is shared between lanes: no LDS, no
@@ -23,8 +25,11 @@
 
 #include <math.h>
 
+#include "lmpc_cars.h"
 #include "lmpc_device.h"
+#include "lmpc_dtrack_dynamics.hip.h"
 #include "lmpc_dynamics.hip.h"
+#include "lmpc_loop_steps.hip.h"
 #include "lmpc_track.hip.h"
 #include "lmpc_vanilla.h"
 
@@ -260,6 +265,125 @@ __global__ __launch_bounds__(64) void lmpc_vanilla_rollout_kernel(lmpc_spline_vi
   if (io.flags) io.flags[b] = frozen ? LMPC_VANILLA_FLAG_NOT_FINITE : 0;
 }
 
+// The double-track plant of one period (lmpc_plant_dtrack_kernel: conversion on entry and exit, guard, lookup, Newton on gamma_y,
+// wrap), OUT OF LINE in vanilla_plant's form -- vehicle and table by value, x_io [6] loaded once and stored once -- around the one
+// text of lmpc_dtrack_dynamics.hip.h.  Out of line it is also the only code of the rollout that needs the model's registers.
+__device__ __noinline__ void vanilla_plant_dtrack(lmpc_vehicle_dt veh, lmpc_track trk, double* __restrict__ x_io, double u0, double u1,
+                                                  double dt_sim, int nsub) {
+#define LMPC_VANILLA_XIO_(k) x_io[k]
+  LMPC_DTRACK_STEP_CAR(veh, trk, LMPC_VANILLA_XIO_, u0, u1, dt_sim, nsub)
+#undef LMPC_VANILLA_XIO_
+  (void)gamma_first;
+}
+
+// lmpc_vanilla_rollout_kernel with car b on a plant of its own and its recorder fed inside the period loop
+// (include/lmpc_hip_vanilla_fleet.h).  PLANT: LMPC_VANILLA_PLANT_HANDLE steps with `veh` (vanilla_plant as lmpc_vanilla_rollout_kernel
+// calls it), _CARS with vehicle b of the car table (loaded once, the same out-of-line function), _DTRACK with four-wheel vehicle b
+// of the double-track table.  REC: a live period -- finite decision, finite state after the plant -- hands (x_p, input, curvature,
+// (period0 + p) dt) to lmpc_fleet_record_car; the input is the one applied from x_p, or with fx.arrived the one that led to it.
+// The decision reads `veh`, the handle's vehicle, whatever the plant.  The text of the period loop is lmpc_vanilla_rollout_kernel's.
+template <int PLANT, bool REC>
+__global__ __launch_bounds__(64) void lmpc_vanilla_fleet_kernel(lmpc_spline_view T, lmpc_vehicle veh, lmpc_vanilla_store st, lmpc_track trk,
+                                                                int B, int periods, double dt_sim, int nsub, double speed_scale,
+                                                                lmpc_vanilla_rollout_io io, lmpc_vanilla_fleet_io fx, lmpc_fleet_store fs) {
+  const int b = blockIdx.x * 64 + threadIdx.x;
+  if (b >= B) return;
+  const size_t Bz = (size_t)B, Pz = (size_t)periods;
+  lmpc_vehicle car;
+  lmpc_vehicle_dt car_dt;
+  if constexpr (PLANT == LMPC_VANILLA_PLANT_CARS) lmpc_car_vehicle(fx.table, B, b, car);
+  if constexpr (PLANT == LMPC_VANILLA_PLANT_DTRACK) dtrack_vehicle(fx.table, B, b, car_dt);
+  double x[6], xs[6];
+#pragma unroll
+  for (int k = 0; k < 6; ++k) x[k] = io.x[k * Bz + b];
+  vanilla_pid pid = {st.pid[b], st.pid[Bz + b], st.pid[2 * Bz + b]};
+  // the accumulators continue from the caller's values, sample by sample: two launches of 32 periods leave the bits of one of 64
+  double dist = io.distance ? io.distance[b] : 0.0, worst = io.worst_excess ? io.worst_excess[b] : -INFINITY;
+  const double half_b = veh.b / 2.0;
+  int piece = 0, piece_la = 0;  // carried from one period to the next: the car moves a fraction of a piece per period
+  bool frozen = false, moved = false;
+  double up0 = 0.0, up1 = 0.0;  // the last input applied; on entry the caller's (read where the recorder takes it)
+  if (REC && fx.arrived) {
+    up0 = fx.u_prev[b];
+    up1 = fx.u_prev[Bz + b];
+  }
+#pragma unroll 1
+  for (size_t p = 0; p < Pz; ++p) {
+    if (!frozen) {
+      const vanilla_decision o = vanilla_decide(T, veh, st.cfg, x, false, 0.0, speed_scale, pid, piece, piece_la);
+      if (!o.finite) {
+        frozen = true;
+      } else {
+        const double u[2] = {o.um0, o.steer};
+#pragma unroll
+        for (int k = 0; k < 6; ++k) xs[k] = x[k];
+        if constexpr (PLANT == LMPC_VANILLA_PLANT_HANDLE) vanilla_plant(veh, trk, xs, u[0], u[1], dt_sim, nsub);
+        if constexpr (PLANT == LMPC_VANILLA_PLANT_CARS) vanilla_plant(car, trk, xs, u[0], u[1], dt_sim, nsub);
+        if constexpr (PLANT == LMPC_VANILLA_PLANT_DTRACK) vanilla_plant_dtrack(car_dt, trk, xs, u[0], u[1], dt_sim, nsub);
+        bool ok = true;
+#pragma unroll
+        for (int k = 0; k < 6; ++k) ok = ok && isfinite(xs[k]);
+        if (!ok) {
+          frozen = true;  // the period is undone: x and the PID state stay as they were before it
+        } else {
+          if (io.X_log) {
+#pragma unroll
+            for (int k = 0; k < 6; ++k) io.X_log[(k * Pz + p) * Bz + b] = x[k];
+          }
+          if (io.U_log) {
+            io.U_log[p * Bz + b] = u[0];
+            io.U_log[(Pz + p) * Bz + b] = u[1];
+          }
+          if (io.k_log || REC) {
+            const double kap = vanilla_lookup(trk.curvature, trk.M, trk.L, x[0]);
+            if (io.k_log) io.k_log[p * Bz + b] = kap;
+            if constexpr (REC) {
+              const double t = (double)(fx.period0 + (long long)p) * fx.dt;
+              lmpc_fleet_record_car(fs, b, x, fx.arrived ? up0 : u[0], fx.arrived ? up1 : u[1], kap, t, trk.L);
+            }
+          }
+          up0 = u[0];
+          up1 = u[1];
+          moved = true;
+          // bookkeeping, as lmpc_loop_advance_kernel keeps it
+          const double ds = xs[0] - x[0];
+          dist += (ds < -trk.L / 2.0) ? ds + trk.L : ds;
+          if (io.worst_excess) {
+            const double bl = vanilla_lookup(trk.bound_left, trk.M, trk.L, x[0]), br = vanilla_lookup(trk.bound_right, trk.M, trk.L, x[0]);
+            worst = fmax(worst, fmax(xs[1] + half_b - bl, br - (xs[1] - half_b)));
+          }
+#pragma unroll
+          for (int k = 0; k < 6; ++k) x[k] = xs[k];
+          pid = o.pid;
+        }
+      }
+    }
+    if (frozen) {
+      if (io.X_log) {
+#pragma unroll
+        for (int k = 0; k < 6; ++k) io.X_log[(k * Pz + p) * Bz + b] = NAN;
+      }
+      if (io.U_log) {
+        io.U_log[p * Bz + b] = NAN;
+        io.U_log[(Pz + p) * Bz + b] = NAN;
+      }
+      if (io.k_log) io.k_log[p * Bz + b] = NAN;
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < 6; ++k) io.x[k * Bz + b] = x[k];
+  st.pid[b] = pid.integral;
+  st.pid[Bz + b] = pid.error;
+  st.pid[2 * Bz + b] = pid.last_error;
+  if (fx.u_prev && moved) {  // (a car frozen in period 0 applied nothing: its u_prev stays)
+    fx.u_prev[b] = up0;
+    fx.u_prev[Bz + b] = up1;
+  }
+  if (io.distance) io.distance[b] = dist;
+  if (io.worst_excess) io.worst_excess[b] = worst;
+  if (io.flags) io.flags[b] = frozen ? LMPC_VANILLA_FLAG_NOT_FINITE : 0;
+}
+
 }  // namespace
 
 hipError_t lmpc_vanilla_launch_solve(hipStream_t stream, const lmpc_vanilla_store& st, const lmpc_vehicle& veh, const lmpc_spline_view& track,
@@ -275,5 +399,26 @@ hipError_t lmpc_vanilla_launch_rollout(hipStream_t stream, const lmpc_vanilla_st
                                        const lmpc_vanilla_rollout_io& io) {
   hipLaunchKernelGGL(lmpc_vanilla_rollout_kernel, dim3((unsigned)((batch + 63) / 64)), dim3(64), 0, stream, track, veh, st, table, batch, periods,
                      dt_sim, n_sub, speed_scale, io);
+  return hipGetLastError();
+}
+
+hipError_t lmpc_vanilla_launch_fleet(hipStream_t stream, const lmpc_vanilla_store& st, const lmpc_vehicle& veh, const lmpc_spline_view& track,
+                                     const lmpc_track& table, int batch, int periods, double dt_sim, int n_sub, double speed_scale,
+                                     const lmpc_vanilla_rollout_io& io, int plant, bool record, const lmpc_vanilla_fleet_io& fx,
+                                     const lmpc_fleet_store& fs) {
+  const dim3 grid((unsigned)((batch + 63) / 64)), block(64);
+#define LMPC_VANILLA_FLEET_LAUNCH_(PLANT, REC)                                                                                        \
+  hipLaunchKernelGGL((lmpc_vanilla_fleet_kernel<PLANT, REC>), grid, block, 0, stream, track, veh, st, table, batch, periods, dt_sim, n_sub, \
+                     speed_scale, io, fx, fs)
+  switch (plant * 2 + (record ? 1 : 0)) {
+    case LMPC_VANILLA_PLANT_HANDLE * 2: LMPC_VANILLA_FLEET_LAUNCH_(LMPC_VANILLA_PLANT_HANDLE, false); break;
+    case LMPC_VANILLA_PLANT_HANDLE * 2 + 1: LMPC_VANILLA_FLEET_LAUNCH_(LMPC_VANILLA_PLANT_HANDLE, true); break;
+    case LMPC_VANILLA_PLANT_CARS * 2: LMPC_VANILLA_FLEET_LAUNCH_(LMPC_VANILLA_PLANT_CARS, false); break;
+    case LMPC_VANILLA_PLANT_CARS * 2 + 1: LMPC_VANILLA_FLEET_LAUNCH_(LMPC_VANILLA_PLANT_CARS, true); break;
+    case LMPC_VANILLA_PLANT_DTRACK * 2: LMPC_VANILLA_FLEET_LAUNCH_(LMPC_VANILLA_PLANT_DTRACK, false); break;
+    case LMPC_VANILLA_PLANT_DTRACK * 2 + 1: LMPC_VANILLA_FLEET_LAUNCH_(LMPC_VANILLA_PLANT_DTRACK, true); break;
+    default: return hipErrorInvalidValue;
+  }
+#undef LMPC_VANILLA_FLEET_LAUNCH_
   return hipGetLastError();
 }
