@@ -31,7 +31,9 @@
  * the fleet store's and lmpc_fleet_loop.plant must be NULL -- the call has one source for its plant --, either violation is
  * LMPC_ERR_ARGUMENT before anything is written.  Everything else in that call keeps the handle's vehicle: the rollouts of the
  * references (the shift's last knot, the in-place shift, the cold restart) and the body width in worst_excess.  Without a table the
- * call is what it is without this header.  No other entry point reads the table. */
+ * call is what it is without this header.  No other entry point reads the table.  The same call on four-wheel cars is
+ * lmpc_fleet_loop_advance_dtrack_batch of lmpc_hip_fleet_dtrack.h, whose plant is the double-track table of lmpc_hip_dtrack.h: by
+ * the same rule it is refused (LMPC_ERR_ARGUMENT) while a car table is set. */
 int lmpc_cars_set_vehicles(lmpc_handle* h, int32_t batch, const lmpc_vehicle* veh);
 
 /* The table read back to a HOST array of `batch` vehicles (checks, checkpoints): what lmpc_cars_set_vehicles was given, field for

@@ -11,8 +11,10 @@
  * (double_track_planar_model.cpp:163-347): four tyres, a lateral load transfer gamma_y that feeds back into the tyre forces, and
  * the tyre curve's falloff (pacejka_e) and load-sensitivity (pacejka_eps / pacejka_fz0) terms.  The controllers stay single-track:
  * only the PLANT exists for this model.  lmpc_create with model_id LMPC_MODEL_DOUBLE_TRACK_PLANAR stays LMPC_ERR_UNSUPPORTED, and
- * no existing entry point reads the table: lmpc_fleet_loop_advance_batch, lmpc_loop_advance_batch, lmpc_vanilla_rollout_batch and
- * the sharded solver are what they are without this header, table or no table.
+ * no entry point of lmpc_hip.h itself reads the table: lmpc_fleet_loop_advance_batch, lmpc_loop_advance_batch,
+ * lmpc_vanilla_rollout_batch and the sharded solver are what they are without this header, table or no table.  Two entry points
+ * with headers of their own do read it: the vanilla rollout of a fleet with LMPC_VANILLA_PLANT_DTRACK (lmpc_hip_vanilla_fleet.h) and
+ * the fused fleet LMPC period on four-wheel cars, lmpc_fleet_loop_advance_dtrack_batch (lmpc_hip_fleet_dtrack.h).
  *
  * The model, as the reference writes it (quirks included): GRAVITY 9.8; BOTH Fz_f and Fz_r carry lr in their static term
  * (:230,234); ax carries no air density and v_dot does (:227,260); the slip-angle denominators are v cos(beta) -/+ 0.5 tw omega

@@ -43,6 +43,8 @@ _ABI_SYMBOLS_CARS = ("lmpc_cars_set_vehicles", "lmpc_cars_get_vehicles", "lmpc_p
 _ABI_SYMBOLS_DTRACK = ("lmpc_dtrack_set_vehicles", "lmpc_dtrack_get_vehicles", "lmpc_plant_step_dtrack_batch")
 # the entry point of include/lmpc_hip_vanilla_fleet.h (the vanilla rollout of a fleet), resolved at load time in a loop of its own
 _ABI_SYMBOLS_VANILLA_FLEET = ("lmpc_vanilla_rollout_fleet_batch",)
+# the entry point of include/lmpc_hip_fleet_dtrack.h (the fused fleet LMPC period on the double-track table), in a loop of its own
+_ABI_SYMBOLS_FLEET_DTRACK = ("lmpc_fleet_loop_advance_dtrack_batch",)
 VANILLA_PLANT = {"handle": 0, "cars": 1, "dtrack": 2}           # LMPC_VANILLA_PLANT_*
 VANILLA_RECORD = {None: 0, "applied": 1, "arrived": 2}          # LMPC_VANILLA_RECORD_*
 EKF_FALLBACK, EKF_R_REPAIRED, EKF_NOT_FINITE = 1, 2, 4   # bits of the per-car flags of Solver.ekf_update
@@ -200,6 +202,8 @@ def load_library():
         for sym in _ABI_SYMBOLS_DTRACK:
             getattr(lib, sym)
         for sym in _ABI_SYMBOLS_VANILLA_FLEET:
+            getattr(lib, sym)
+        for sym in _ABI_SYMBOLS_FLEET_DTRACK:
             getattr(lib, sym)
         lib.lmpc_last_error.restype = C.c_char_p
         lib.lmpc_last_error.argtypes = [C.c_void_p]
@@ -466,7 +470,8 @@ class Solver:
     def set_dtrack_vehicles(self, vehicles):
         """lmpc_dtrack_set_vehicles: a sequence of B double-track vehicle dicts (presets.barc_double_track's keys: the vehicle's, with
         model_id 2, and tw_f, tw_r, kroll_f, Ef, Fz0_f, eps_f, Er, Fz0_r, eps_r; "integrator" "rk4" | "euler" per car) becomes the
-        handle's double-track table; None or an empty sequence switches it off.  Only plant_step_dtrack reads it.  Blocking."""
+        handle's double-track table; None or an empty sequence switches it off.  plant_step_dtrack reads it, vanilla_rollout_fleet(plant="dtrack") and
+        fleet_loop_advance(dtrack=True).  Blocking."""
         self.use_current_stream()
         vehicles = list(vehicles) if vehicles is not None else []
         if not vehicles:
@@ -920,7 +925,7 @@ class Solver:
     def fleet_loop_advance(self, track: dict, inp: dict, sol_trk, sol_lrn, x, u_prev, state: dict, dt: float, dt_sim: float, n_sub: int = 1,
                            t: float = 0.0, speed_scale=(1.0, 1.0), speed_limit=(None, None), max_vel_ref_diff=(None, None),
                            restart_failed: bool = False, warm_laps: int = 2, learn_laps: int = 4, switch_phase: bool = True, plant=None,
-                           distance=None, worst_excess=None, n_fail=None, n_rec: int | None = None):
+                           distance=None, worst_excess=None, n_fail=None, n_rec: int | None = None, dtrack: bool = False, gamma_y=None):
         """lmpc_fleet_loop_advance_batch on this (the learning) solver, which owns the fleet store: everything between two solves of a
         fleet LMPC period in one launch -- per car the solution of the controller it drives with (state["phase"]: 0 `sol_trk`, 1
         `sol_lrn`; each a dict with X_optm, U_optm, status, or None when that controller did not run), input and plant, the next
@@ -929,8 +934,11 @@ class Solver:
         speed_scale / speed_limit / max_vel_ref_diff: (tracking, learning) pairs; a None limit is this solver's x_max[3], a None
         difference its max_vel_ref_diff.  plant: a vehicle dict for the plant (None: this solver's, or while a car table is set --
         set_car_vehicles -- car b's own vehicle; the library refuses plant= then).  `state` is fleet_loop_state's
-        dict; n_rec (default: the lap book's first dimension) is how many of its rows the call may write.  Asynchronous; nothing is
-        read back."""
+        dict; n_rec (default: the lap book's first dimension) is how many of its rows the call may write.
+        dtrack=True: lmpc_fleet_loop_advance_dtrack_batch (include/lmpc_hip_fleet_dtrack.h) -- the same call with car b's plant the
+        four-wheel vehicle b of the double-track table (set_dtrack_vehicles; the library refuses plant= and a car table then);
+        gamma_y (a float64 [B] tensor, optional, with dtrack=True only) receives plant_step_dtrack's gamma_y.  Asynchronous; nothing
+        is read back."""
         self.use_current_stream()
         ct = self._ctrack(track)
         io = CFleetLoop()
@@ -958,6 +966,12 @@ class Solver:
         for key in ("phase", "n_learn", "lap_time", "lap_kind", "counters", "x_ic", "query"):
             setattr(io, key, _ptr(state.get(key)))
         io.distance, io.worst_excess, io.n_fail = _ptr(distance), _ptr(worst_excess), _ptr(n_fail)
+        if dtrack:
+            rc = self.lib.lmpc_fleet_loop_advance_dtrack_batch(self._h, C.c_int32(x.shape[1]), C.byref(ct), C.byref(io), _ptr(gamma_y))
+            self._check(rc, "lmpc_fleet_loop_advance_dtrack_batch")
+            return
+        if gamma_y is not None:
+            raise ValueError("fleet_loop_advance: gamma_y= goes with dtrack=True")
         rc = self.lib.lmpc_fleet_loop_advance_batch(self._h, C.c_int32(x.shape[1]), C.byref(ct), C.byref(io))
         self._check(rc, "lmpc_fleet_loop_advance_batch")
 

@@ -594,7 +594,7 @@ def run_lmpc_fleet(tracker, learner, track: dict, x0, u0, warm_laps: int = 2, le
 def run_lmpc_fleet_fused(tracker, learner, track: dict, x0, u0, warm_laps: int = 2, learn_laps: int = 4, dt: float = 0.025,
                          n_sub: int = 2, warm_speed_scale: float = 0.7, max_steps: int = 20000, max_pts_per_lap: int = 1024,
                          record_trace: bool = False, regression: dict | None = None, plant=None, poll: int = 1, plants=None,
-                         warmup: dict | None = None, _warm_plant: str = "handle"):
+                         warmup: dict | None = None, _warm_plant: str = "handle", plants_dt=None):
     """run_lmpc_fleet with everything between two solves in one launch, lmpc_fleet_loop_advance_batch on `learner`: input selection
     between the two controllers' results, plant, shift, x_ic, every car's recorder and ring, the lap book, the per-car phase and the
     next query point.  Same arguments, same experiment, same return dictionary; per period the fleet query when any car learns, the
@@ -610,6 +610,9 @@ def run_lmpc_fleet_fused(tracker, learner, track: dict, x0, u0, warm_laps: int =
     (x, u, k, t) tuples is run_lmpc_fleet's torch interpolation; the ring holds the kernel's own lookup at the same abscissa.
     plants (a list of B vehicle dicts, exclusive with plant=): car b drives on plants[b] -- the list is `learner`'s car table
     (Solver.set_car_vehicles) for the run, which the fused call reads, and the table is cleared at the end.
+    plants_dt (a list of B double-track vehicle dicts, exclusive with plant= and plants=): car b drives on the FOUR-WHEEL model with
+    plants_dt[b] -- the list is `learner`'s double-track table (Solver.set_dtrack_vehicles) for the run, every period is
+    lmpc_fleet_loop_advance_dtrack_batch (fleet_loop_advance(dtrack=True)), and the table is cleared at the end.
     warmup (a dict, _fleet_warm_up's): run_lmpc_fleet's -- the warm laps by the vanilla controller on the run's own plants; the
     head-only call then sends every car whose ring holds warm_laps laps straight to the learning controller.
     Raises ValueError when the two solvers differ in N or vehicle: one launch shifts both controllers' plans with one model."""
@@ -621,9 +624,19 @@ def run_lmpc_fleet_fused(tracker, learner, track: dict, x0, u0, warm_laps: int =
     if poll < 1:
         raise ValueError("run_lmpc_fleet_fused: poll must be >= 1")
     B = x0.shape[1]
+    if plants_dt is not None:
+        if plants is not None:
+            raise ValueError("run_lmpc_fleet_fused: plants= (single-track cars) and plants_dt= (double-track cars) are exclusive")
+        _check_plants(plant, plants_dt, B, "run_lmpc_fleet_fused", "plants_dt")
+        learner.set_dtrack_vehicles(plants_dt)
+        try:
+            return run_lmpc_fleet_fused(tracker, learner, track, x0, u0, warm_laps, learn_laps, dt, n_sub, warm_speed_scale, max_steps,
+                                        max_pts_per_lap, record_trace, regression, None, poll, warmup=warmup, _warm_plant="dtrack")
+        finally:
+            learner.set_dtrack_vehicles(None)
     _check_plants(plant, plants, B, "run_lmpc_fleet_fused")
     if warmup is not None and plant is not None:
-        raise ValueError("run_lmpc_fleet_fused: warmup= drives the warm laps on the learner's vehicle or plants=, not on plant=")
+        raise ValueError("run_lmpc_fleet_fused: warmup= drives the warm laps on the learner's vehicle, plants= or plants_dt=, not on plant=")
     if plants is not None:
         learner.set_car_vehicles(plants)
         try:
@@ -656,7 +669,7 @@ def run_lmpc_fleet_fused(tracker, learner, track: dict, x0, u0, warm_laps: int =
               speed_limit=(float(tracker.config["x_max"][3]), float(learner.config["x_max"][3])),
               max_vel_ref_diff=(float(tracker.config["max_vel_ref_diff"]), float(learner.config["max_vel_ref_diff"])),
               restart_failed=False, warm_laps=warm_laps, learn_laps=learn_laps, plant=None if plant is None else plant.vehicle,
-              worst_excess=worst_excess, n_fail=n_fail)
+              worst_excess=worst_excess, n_fail=n_fail, dtrack=_warm_plant == "dtrack")   # ("dtrack": the plants_dt= branch above)
     curv = trk["curvature"]
     M = int(curv.numel())
     trace, t, k = [], t_start, -1

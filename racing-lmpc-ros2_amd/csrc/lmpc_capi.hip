@@ -1754,9 +1754,11 @@ int lmpc_fleet_ss_stats(lmpc_handle* h, int32_t batch, int32_t* laps_in_ring, in
 }
 
 // ---- everything between two solves of a fleet LMPC period (csrc/lmpc_fleet_loop_kernel.hip) ----
-int lmpc_fleet_loop_advance_batch(lmpc_handle* h, int32_t batch, const lmpc_track* track, const lmpc_fleet_loop* io) {
+// Both entry points: the validation, the constants and the launch.  dtrack: step 2's plant is the handle's double-track table
+// (lmpc_fleet_loop_advance_dtrack_batch, include/lmpc_hip_fleet_dtrack.h); else the call as it always was, table or no table.
+static int fleet_loop_advance(lmpc_handle* h, int32_t batch, const lmpc_track* track, const lmpc_fleet_loop* io, bool dtrack, double* gamma_y,
+                              const char* who) {
   if (!h) return LMPC_ERR_ARGUMENT;
-  const char* who = "lmpc_fleet_loop_advance_batch";
   if (!io) return fail(h, LMPC_ERR_ARGUMENT, std::string(who) + ": io is NULL");
   const int rc = fleet_check(h, batch, who);
   if (rc != LMPC_OK) return rc;
@@ -1777,6 +1779,14 @@ int lmpc_fleet_loop_advance_batch(lmpc_handle* h, int32_t batch, const lmpc_trac
     return fail(h, LMPC_ERR_ARGUMENT, std::string(who) + ": plant: integrator must be LMPC_INTEGRATOR_RK4 or LMPC_INTEGRATOR_EULER");
   if ((io->X_trk && (io->X_ref == io->X_trk || io->U_ref == io->U_trk)) || (io->X_lrn && (io->X_ref == io->X_lrn || io->U_ref == io->U_lrn)))
     return fail(h, LMPC_ERR_ARGUMENT, std::string(who) + ": the references must not alias a solution");
+  if (dtrack) {  // one source for the plant: the double-track table, of the store's batch
+    if (!h->dtrack_B) return fail(h, LMPC_ERR_ARGUMENT, std::string(who) + ": no double-track table (lmpc_dtrack_set_vehicles)");
+    if (h->dtrack_B != batch)
+      return fail(h, LMPC_ERR_ARGUMENT, std::string(who) + ": the double-track table holds " + std::to_string(h->dtrack_B) + " vehicles, the store " + std::to_string(batch) + " cars");
+    if (io->plant) return fail(h, LMPC_ERR_ARGUMENT, std::string(who) + ": plant must be NULL: the double-track table is the plant, one source for it");
+    if (h->cars_B)
+      return fail(h, LMPC_ERR_ARGUMENT, std::string(who) + ": a car table is set (lmpc_cars_set_vehicles) beside the double-track table: one source for the plant");
+  }
   if (h->cars_B && io->plant)
     return fail(h, LMPC_ERR_ARGUMENT, std::string(who) + ": plant must be NULL while a car table is set (lmpc_cars_set_vehicles): one source for the plant");
   if (h->cars_B && h->cars_B != batch)
@@ -1792,14 +1802,31 @@ int lmpc_fleet_loop_advance_batch(lmpc_handle* h, int32_t batch, const lmpc_trac
   dev.plant = nullptr;  // (a host pointer: the kernel takes the vehicle by value)
   dev.restart_failed = io->restart_failed ? 1 : 0;
   h->fleet_L = track->L;  // what the query unrolls the laps by, as lmpc_fleet_ss_record_batch notes it
-  if (h->cars_B) {  // the kernel's table instantiation reads the DEVICE car table where the host's vehicle pointer was
+  const dim3 grid((batch + 63) / 64), block(64 * lmpc_loop_waves);
+  if (dtrack) {  // the double-track instantiation: the constants, and behind them the DEVICE double-track table and gamma_y
+    lmpc_fleet_loop_consts_dt Kd{};
+    static_cast<lmpc_fleet_loop_consts&>(Kd) = K;
+    Kd.table = h->dtrack_tab.get();
+    Kd.gamma_y = gamma_y;
+    hipLaunchKernelGGL(lmpc_fleet_loop_kernel<LMPC_FLEET_PLANT_DTRACK>, grid, block, 0, h->stream, Kd, h->fleet, *track, dev);
+  } else if (h->cars_B) {  // the kernel's table instantiation reads the DEVICE car table where the host's vehicle pointer was
     dev.plant = reinterpret_cast<const lmpc_vehicle*>(h->cars_tab.get());
-    hipLaunchKernelGGL(lmpc_fleet_loop_kernel<true>, dim3((batch + 63) / 64), dim3(64 * lmpc_loop_waves), 0, h->stream, K, h->fleet, *track, dev);
+    hipLaunchKernelGGL(lmpc_fleet_loop_kernel<LMPC_FLEET_PLANT_CARS>, grid, block, 0, h->stream, K, h->fleet, *track, dev);
   } else {
-    hipLaunchKernelGGL(lmpc_fleet_loop_kernel<false>, dim3((batch + 63) / 64), dim3(64 * lmpc_loop_waves), 0, h->stream, K, h->fleet, *track, dev);
+    hipLaunchKernelGGL(lmpc_fleet_loop_kernel<LMPC_FLEET_PLANT_HANDLE>, grid, block, 0, h->stream, K, h->fleet, *track, dev);
   }
   HIP_TRY(h, hipGetLastError());
   return LMPC_OK;
+}
+
+int lmpc_fleet_loop_advance_batch(lmpc_handle* h, int32_t batch, const lmpc_track* track, const lmpc_fleet_loop* io) {
+  return fleet_loop_advance(h, batch, track, io, false, nullptr, "lmpc_fleet_loop_advance_batch");
+}
+
+// ---- the same period on four-wheel cars (include/lmpc_hip_fleet_dtrack.h) ----
+int lmpc_fleet_loop_advance_dtrack_batch(lmpc_handle* h, int32_t batch, const lmpc_track* track, const lmpc_fleet_loop* io,
+                                         double* gamma_y_or_null) {
+  return fleet_loop_advance(h, batch, track, io, true, gamma_y_or_null, "lmpc_fleet_loop_advance_dtrack_batch");
 }
 
 // ---- the car table: one plant vehicle per car (include/lmpc_hip_cars.h, csrc/lmpc_cars.h, csrc/lmpc_cars_kernel.hip) ----

@@ -3,7 +3,8 @@
 //   1 the solution of the controller the car drives with (phase 0: tracking, 1: learning), 2 the input applied and the plant,
 //   3 the next references (lmpc_loop_advance_kernel's three routes, with the phase's speed triple), 4 x_ic, 5 the car's recorder and
 //   ring (lmpc_fleet_ss_record_kernel's body), 6 the lap book, 7 the phase, 8 the next k-NN query point.
-// Steps 2, 3 and 5 are the text of lmpc_loop_steps.hip.h, the same the kernels they come from are made of.
+// Steps 2, 3 and 5 are the text of lmpc_loop_steps.hip.h, the same the kernels they come from are made of.  On four-wheel cars
+// (lmpc_fleet_loop_advance_dtrack_batch, include/lmpc_hip_fleet_dtrack.h) step 2's plant is the text of lmpc_dtrack_dynamics.hip.h.
 //
 // Shape: lmpc_loop_advance_kernel's.  A workgroup is 64 cars (the lanes) x lmpc_loop_waves waves; wave 0 is the car -- input, plant,
 // books, recorder, phase, query -- and the waves share the knots of a shifted solution.  A failed car is wave 0's alone.
@@ -22,6 +23,7 @@
 #include <hip/hip_runtime.h>
 
 #include "lmpc_cars.h"
+#include "lmpc_dtrack_dynamics.hip.h"
 #include "lmpc_fleet_loop.h"
 #include "lmpc_loop_steps.hip.h"
 
@@ -61,17 +63,33 @@ __device__ __noinline__ lmpc_last_knot fleet_loop_shift_in_place(lmpc_vehicle ve
   return {x[0], x[1]};
 }
 
-// One text, two instantiations.  CARS = false is the kernel as it always was: io.plant blanked by the host, every car's plant
-// K.plant.  CARS = true: io.plant is the DEVICE car table of csrc/lmpc_cars.h (the host puts it there; a table of st.B cars), and
-// step 2 loads car b's vehicle from it and hands that to the same fleet_loop_plant.  A second kernel and not a run-time branch in
-// the first, and the kernel itself the template, not a wrapper around an inlined body: so instantiated, <false> is the instruction
-// stream, the 256 VGPRs and the 848 bytes of scratch it had as a plain kernel (compared on the compiler's assembly; behind a
-// wrapper its scratch grew to 928 bytes), which is what tests/test_gpu_fleet_loop.py and profiles/fleet_lmpc_fused.md hold it to.
-// Everything but step 2's vehicle is the same in both: the reference rollouts, the cold restart, the in-place shift and the body
+// The double-track plant of one period (lmpc_plant_dtrack_kernel: conversion on entry and exit, guard, lookup, Newton on gamma_y,
+// wrap), OUT OF LINE in vanilla_plant_dtrack's form (lmpc_vanilla_kernel.hip) -- vehicle and table by value, x_io [6] loaded once and
+// stored once -- around the one text of lmpc_dtrack_dynamics.hip.h.  Out of line it is the only code of the kernel that needs the
+// four-wheel model's registers: none of them is live across steps 3 to 8.  Returns the gamma_y solved in the first evaluation of the
+// dynamics of the last sub-step.
+__device__ __noinline__ double fleet_loop_plant_dtrack(lmpc_vehicle_dt veh, lmpc_track trk, double* __restrict__ x_io, double u0, double u1,
+                                                       double dt_sim, int nsub) {
+#define LMPC_FLEET_LOOP_XIO_(k) x_io[k]
+  LMPC_DTRACK_STEP_CAR(veh, trk, LMPC_FLEET_LOOP_XIO_, u0, u1, dt_sim, nsub)
+#undef LMPC_FLEET_LOOP_XIO_
+  return gamma_first;
+}
+
+// One text, three instantiations (lmpc_fleet_loop.h names them).  _HANDLE is the kernel as it always was: io.plant blanked by the
+// host, every car's plant K.plant.  _CARS: io.plant is the DEVICE car table of csrc/lmpc_cars.h (the host puts it there; a table of
+// st.B cars), and step 2 loads car b's vehicle from it and hands that to the same fleet_loop_plant.  _DTRACK: step 2 loads car b's
+// four-wheel vehicle from K.table, the double-track table of csrc/lmpc_dtrack.h, and hands it to fleet_loop_plant_dtrack; K.gamma_y,
+// when not null, receives what that returns.  A kernel each and not a run-time branch in the first, and the kernel itself the
+// template, not a wrapper around an inlined body: so instantiated, _HANDLE is the instruction stream, the 256 VGPRs and the 848
+// bytes of scratch it had as a plain kernel (compared on the compiler's assembly; behind a wrapper its scratch grew to 928 bytes),
+// which is what tests/test_gpu_fleet_loop.py and profiles/fleet_lmpc_fused.md hold it to; profiles/fleet_dtrack_fused.md has the
+// same comparison with the third instantiation beside the two.
+// Everything but step 2's vehicle is the same in all: the reference rollouts, the cold restart, the in-place shift and the body
 // width of worst_excess use the handle's vehicle K.veh -- the controllers share one model.
-template <bool CARS>
-__global__ __launch_bounds__(64 * lmpc_loop_waves) void lmpc_fleet_loop_kernel(lmpc_fleet_loop_consts K, lmpc_fleet_store st, lmpc_track trk,
-                                                                               lmpc_fleet_loop io) {
+template <int PLANT>
+__global__ __launch_bounds__(64 * lmpc_loop_waves) void lmpc_fleet_loop_kernel(lmpc_fleet_loop_consts_of<PLANT> K, lmpc_fleet_store st,
+                                                                               lmpc_track trk, lmpc_fleet_loop io) {
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int b = blockIdx.x * 64 + lane;
   const int B = st.B, N = K.N, NS = N - 1;
@@ -104,7 +122,12 @@ __global__ __launch_bounds__(64 * lmpc_loop_waves) void lmpc_fleet_loop_kernel(l
 #pragma unroll
       for (int k = 0; k < 6; ++k) x[k] = io.x[(size_t)k * B + b];
       const double s_before = x[0];
-      if constexpr (CARS) {
+      if constexpr (PLANT == LMPC_FLEET_PLANT_DTRACK) {
+        lmpc_vehicle_dt car;
+        dtrack_vehicle(K.table, B, b, car);
+        const double gamma_first = fleet_loop_plant_dtrack(car, trk, x, u[0], u[1], io.dt_sim, io.n_sub);
+        if (K.gamma_y) K.gamma_y[b] = gamma_first;
+      } else if constexpr (PLANT == LMPC_FLEET_PLANT_CARS) {
         lmpc_vehicle car;
         lmpc_car_vehicle(reinterpret_cast<const double*>(io.plant), B, b, car);
         fleet_loop_plant(car, trk, x, u[0], u[1], io.dt_sim, io.n_sub);
@@ -177,5 +200,6 @@ __global__ __launch_bounds__(64 * lmpc_loop_waves) void lmpc_fleet_loop_kernel(l
   io.query[(size_t)B + b] = last_ey;
 }
 
-template __global__ void lmpc_fleet_loop_kernel<false>(lmpc_fleet_loop_consts, lmpc_fleet_store, lmpc_track, lmpc_fleet_loop);
-template __global__ void lmpc_fleet_loop_kernel<true>(lmpc_fleet_loop_consts, lmpc_fleet_store, lmpc_track, lmpc_fleet_loop);
+template __global__ void lmpc_fleet_loop_kernel<LMPC_FLEET_PLANT_HANDLE>(lmpc_fleet_loop_consts, lmpc_fleet_store, lmpc_track, lmpc_fleet_loop);
+template __global__ void lmpc_fleet_loop_kernel<LMPC_FLEET_PLANT_CARS>(lmpc_fleet_loop_consts, lmpc_fleet_store, lmpc_track, lmpc_fleet_loop);
+template __global__ void lmpc_fleet_loop_kernel<LMPC_FLEET_PLANT_DTRACK>(lmpc_fleet_loop_consts_dt, lmpc_fleet_store, lmpc_track, lmpc_fleet_loop);
