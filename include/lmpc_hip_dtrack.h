@@ -9,12 +9,15 @@
  * What it is for: model mismatch that is STRUCTURAL, not parametric.  The car table of lmpc_hip_cars.h steps every car with the
  * controllers' own single-track equations and other numbers; this plant is DoubleTrackPlanarModel::compile_dynamics
  * (double_track_planar_model.cpp:163-347): four tyres, a lateral load transfer gamma_y that feeds back into the tyre forces, and
- * the tyre curve's falloff (pacejka_e) and load-sensitivity (pacejka_eps / pacejka_fz0) terms.  The controllers stay single-track:
- * only the PLANT exists for this model.  lmpc_create with model_id LMPC_MODEL_DOUBLE_TRACK_PLANAR stays LMPC_ERR_UNSUPPORTED, and
- * no entry point of lmpc_hip.h itself reads the table: lmpc_fleet_loop_advance_batch, lmpc_loop_advance_batch,
- * lmpc_vanilla_rollout_batch and the sharded solver are what they are without this header, table or no table.  Two entry points
- * with headers of their own do read it: the vanilla rollout of a fleet with LMPC_VANILLA_PLANT_DTRACK (lmpc_hip_vanilla_fleet.h) and
- * the fused fleet LMPC period on four-wheel cars, lmpc_fleet_loop_advance_dtrack_batch (lmpc_hip_fleet_dtrack.h).
+ * the tyre curve's falloff (pacejka_e) and load-sensitivity (pacejka_eps / pacejka_fz0) terms.  This header is the PLANT; a handle's
+ * controllers are single-track unless lmpc_dtrack_set_controller_model (lmpc_hip_dtrack_model.h) puts the batched fp64 / mixed
+ * solves on the four-wheel model of this table, problem b on vehicle b.  lmpc_create with model_id LMPC_MODEL_DOUBLE_TRACK_PLANAR
+ * stays LMPC_ERR_UNSUPPORTED, and no entry point of lmpc_hip.h itself reads the table while that switch is off:
+ * lmpc_fleet_loop_advance_batch, lmpc_loop_advance_batch, lmpc_vanilla_rollout_batch and the sharded solver are what they are
+ * without this header, table or no table.  Entry points with headers of their own do read it: the vanilla rollout of a fleet with
+ * LMPC_VANILLA_PLANT_DTRACK (lmpc_hip_vanilla_fleet.h), the fused fleet LMPC period on four-wheel cars,
+ * lmpc_fleet_loop_advance_dtrack_batch (lmpc_hip_fleet_dtrack.h), and the linearisation of the controller model,
+ * lmpc_linearize_dtrack_batch (lmpc_hip_dtrack_model.h).
  *
  * The model, as the reference writes it (quirks included): GRAVITY 9.8; BOTH Fz_f and Fz_r carry lr in their static term
  * (:230,234); ax carries no air density and v_dot does (:227,260); the slip-angle denominators are v cos(beta) -/+ 0.5 tw omega
@@ -65,7 +68,8 @@ typedef struct lmpc_vehicle_dt {
 /* The double-track table: veh is a HOST array of `batch` vehicles, copied to the device as a structure of arrays (each of the 34
  * doubles of lmpc_vehicle_dt as [batch], and the integrator as int32 [batch]: a wave's 64 cars read a field as one contiguous
  * run).  The handle holds one table, independent of the car table of lmpc_hip_cars.h; a new one replaces it, whatever its batch.
- * veh = NULL or batch = 0 switches the table off and frees it; lmpc_destroy frees it too.  Every vehicle must have model_id
+ * veh = NULL or batch = 0 switches the table off and frees it (and with it the controller model of lmpc_hip_dtrack_model.h, which a
+ * replaced table keeps); lmpc_destroy frees it too.  Every vehicle must have model_id
  * LMPC_MODEL_DOUBLE_TRACK_PLANAR, integrator LMPC_INTEGRATOR_RK4 or LMPC_INTEGRATOR_EULER (it may differ from car to car),
  * tw_f + tw_r > 0 and Fz0_f, Fz0_r other than 0; anything else, or batch < 0, is LMPC_ERR_ARGUMENT and the table in effect before
  * the call stays in effect, untouched.  Blocking: it synchronises the handle's stream before the older table is freed, and copies

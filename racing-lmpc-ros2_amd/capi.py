@@ -45,6 +45,8 @@ _ABI_SYMBOLS_DTRACK = ("lmpc_dtrack_set_vehicles", "lmpc_dtrack_get_vehicles", "
 _ABI_SYMBOLS_VANILLA_FLEET = ("lmpc_vanilla_rollout_fleet_batch",)
 # the entry point of include/lmpc_hip_fleet_dtrack.h (the fused fleet LMPC period on the double-track table), in a loop of its own
 _ABI_SYMBOLS_FLEET_DTRACK = ("lmpc_fleet_loop_advance_dtrack_batch",)
+# the entry points of include/lmpc_hip_dtrack_model.h (the double-track controller model), resolved at load time in a loop of their own
+_ABI_SYMBOLS_DTRACK_MODEL = ("lmpc_linearize_dtrack_batch", "lmpc_dtrack_set_controller_model", "lmpc_dtrack_get_controller_model")
 VANILLA_PLANT = {"handle": 0, "cars": 1, "dtrack": 2}           # LMPC_VANILLA_PLANT_*
 VANILLA_RECORD = {None: 0, "applied": 1, "arrived": 2}          # LMPC_VANILLA_RECORD_*
 EKF_FALLBACK, EKF_R_REPAIRED, EKF_NOT_FINITE = 1, 2, 4   # bits of the per-car flags of Solver.ekf_update
@@ -204,6 +206,8 @@ def load_library():
         for sym in _ABI_SYMBOLS_VANILLA_FLEET:
             getattr(lib, sym)
         for sym in _ABI_SYMBOLS_FLEET_DTRACK:
+            getattr(lib, sym)
+        for sym in _ABI_SYMBOLS_DTRACK_MODEL:
             getattr(lib, sym)
         lib.lmpc_last_error.restype = C.c_char_p
         lib.lmpc_last_error.argtypes = [C.c_void_p]
@@ -543,6 +547,35 @@ class Solver:
                                            _ptr(Bm), _ptr(g))
         self._check(rc, "lmpc_linearize_batch")
         return A, Bm, g
+
+    # ---- the double-track controller model (include/lmpc_hip_dtrack_model.h) ----
+    def linearize_dtrack(self, inp: dict, out=None):
+        """lmpc_linearize_dtrack_batch: what linearize returns -- A [6, 6, N-1, B], Bm [6, 2, N-1, B], g [6, N-1, B] -- on the
+        double-track model, problem b on vehicle b of the double-track table (set_dtrack_vehicles).  `out`: an (A, Bm, g) of float64
+        tensors to write into instead of fresh ones.  Asynchronous; refused without a table or with a batch other than the table's."""
+        torch = self._torch
+        self.use_current_stream()
+        X, U, T, kap = (self._t(inp[k]) for k in ("X_ref", "U_ref", "T_ref", "curvatures"))
+        B, N = X.shape[2], self.N
+        kw = dict(dtype=torch.float64, device=self.device)
+        A, Bm, g = out if out is not None else (torch.empty((6, 6, N - 1, B), **kw), torch.empty((6, 2, N - 1, B), **kw),
+                                                torch.empty((6, N - 1, B), **kw))
+        rc = self.lib.lmpc_linearize_dtrack_batch(self._h, C.c_int32(B), _ptr(X), _ptr(U), _ptr(T), _ptr(kap), _ptr(A), _ptr(Bm), _ptr(g))
+        self._check(rc, "lmpc_linearize_dtrack_batch")
+        return A, Bm, g
+
+    def set_dtrack_controller_model(self, on: bool):
+        """lmpc_dtrack_set_controller_model: while on, solve(...) -- fp64, mixed, warm, with the safe set as arrays or by reference --
+        linearises problem b on vehicle b of the double-track table and must be given the table's batch; solve_f32 and the
+        sequential-QP solve are refused.  Needs a table; refused while a regression is in effect.  Host-only."""
+        self._check(self.lib.lmpc_dtrack_set_controller_model(self._h, C.c_int32(1 if on else 0)), "lmpc_dtrack_set_controller_model")
+
+    @property
+    def dtrack_controller_model(self) -> bool:
+        """lmpc_dtrack_get_controller_model: whether the solves run on the double-track model."""
+        on = C.c_int32(0)
+        self._check(self.lib.lmpc_dtrack_get_controller_model(self._h, C.byref(on)), "lmpc_dtrack_get_controller_model")
+        return bool(on.value)
 
     # ---- RacingMPC::solve (racing_mpc.cpp:209-372) ----
     def alloc_outputs(self, B: int, aos: bool | None = None):

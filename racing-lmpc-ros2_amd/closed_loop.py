@@ -420,10 +420,29 @@ class _DtrackPlant:
         self.plant_step = solver.plant_step_dtrack
 
 
+def _with_dtrack_controllers(run, who, tracker, learner, B, controllers_dt, plants_dt, regression):
+    """controllers_dt= of run_lmpc_fleet / run_lmpc_fleet_fused: the list is the double-track table of both handles and both solve on
+    it (Solver.set_dtrack_controller_model) while `run` runs; switch and tables are off again on the way out, whatever happened."""
+    if regression is not None:
+        raise ValueError(who + ": controllers_dt= and regression= are exclusive (the regression corrects the single-track model)")
+    if plants_dt is not None and plants_dt is not controllers_dt and list(plants_dt) != list(controllers_dt):
+        raise ValueError(who + ": the plant reads the learner's double-track table, so plants_dt= and controllers_dt= must be the same list")
+    _check_plants(None, controllers_dt, B, who, "controllers_dt")
+    try:
+        for sv in (tracker, learner):
+            sv.set_dtrack_vehicles(controllers_dt)
+            sv.set_dtrack_controller_model(True)
+        return run()
+    finally:
+        for sv in (tracker, learner):
+            sv.set_dtrack_controller_model(False)
+            sv.set_dtrack_vehicles(None)
+
+
 def run_lmpc_fleet(tracker, learner, track: dict, x0, u0, warm_laps: int = 2, learn_laps: int = 4, dt: float = 0.025,
                    n_sub: int = 2, warm_speed_scale: float = 0.7, max_steps: int = 20000, max_pts_per_lap: int = 1024,
                    record_trace: bool = False, regression: dict | None = None, plant=None, plants=None, plants_dt=None,
-                   warmup: dict | None = None, _warm_plant: str = "handle"):
+                   warmup: dict | None = None, _warm_plant: str = "handle", controllers_dt=None):
     """run_lmpc with every car learning from ITS OWN laps: the fleet safe set on `learner` (lmpc_fleet_ss_*: one recorder and one
     ring of max_lap_stored laps per car, on the device) replaces the host recorder of car 0 and the shared store.  Per period, in
     run_lmpc's order: record (x, u_prev, curvature at s, t) for all cars, query every learning car's own ring, solve, plant step,
@@ -453,11 +472,20 @@ def run_lmpc_fleet(tracker, learner, track: dict, x0, u0, warm_laps: int = 2, le
     warmup (a dict, _fleet_warm_up's): the warm laps are driven by the vanilla controller on the run's own plants in a few launches
     (warm_up_vanilla) instead of by the tracking controller; the loop starts where they end, with its clock at their end, and
     "lap_times" / "lap_kind" list only the laps closed after them, and "warmup" = {"periods", "t_end", "lap_count"} says where they
-    ended.  None: the run as it always was."""
+    ended.  None: the run as it always was.
+    controllers_dt (a list of B double-track vehicle dicts, usually plants_dt's list): the CONTROLLERS' model -- the list is the
+    double-track table of both handles and both solve on it, problem b linearised on controllers_dt[b]
+    (Solver.set_dtrack_controller_model); switch and tables are off again on return.  The plant reads the learner's table, so with
+    plants_dt= it must be the same list, and it is exclusive with regression=: ValueError otherwise."""
     import numpy as np
     import torch
 
     B = x0.shape[1]
+    if controllers_dt is not None:
+        return _with_dtrack_controllers(
+            lambda: run_lmpc_fleet(tracker, learner, track, x0, u0, warm_laps, learn_laps, dt, n_sub, warm_speed_scale, max_steps, max_pts_per_lap,
+                                   record_trace, regression, plant, plants, plants_dt, warmup, _warm_plant),
+            "run_lmpc_fleet", tracker, learner, B, controllers_dt, plants_dt, regression)
     if warmup is not None and plant is not None and _warm_plant == "handle":
         raise ValueError("run_lmpc_fleet: warmup= drives the warm laps on the learner's vehicle, plants= or plants_dt=, not on plant=")
     if plants_dt is not None:
@@ -594,7 +622,7 @@ def run_lmpc_fleet(tracker, learner, track: dict, x0, u0, warm_laps: int = 2, le
 def run_lmpc_fleet_fused(tracker, learner, track: dict, x0, u0, warm_laps: int = 2, learn_laps: int = 4, dt: float = 0.025,
                          n_sub: int = 2, warm_speed_scale: float = 0.7, max_steps: int = 20000, max_pts_per_lap: int = 1024,
                          record_trace: bool = False, regression: dict | None = None, plant=None, poll: int = 1, plants=None,
-                         warmup: dict | None = None, _warm_plant: str = "handle", plants_dt=None):
+                         warmup: dict | None = None, _warm_plant: str = "handle", plants_dt=None, controllers_dt=None):
     """run_lmpc_fleet with everything between two solves in one launch, lmpc_fleet_loop_advance_batch on `learner`: input selection
     between the two controllers' results, plant, shift, x_ic, every car's recorder and ring, the lap book, the per-car phase and the
     next query point.  Same arguments, same experiment, same return dictionary; per period the fleet query when any car learns, the
@@ -615,6 +643,8 @@ def run_lmpc_fleet_fused(tracker, learner, track: dict, x0, u0, warm_laps: int =
     lmpc_fleet_loop_advance_dtrack_batch (fleet_loop_advance(dtrack=True)), and the table is cleared at the end.
     warmup (a dict, _fleet_warm_up's): run_lmpc_fleet's -- the warm laps by the vanilla controller on the run's own plants; the
     head-only call then sends every car whose ring holds warm_laps laps straight to the learning controller.
+    controllers_dt (a list of B double-track vehicle dicts, usually plants_dt's list): run_lmpc_fleet's -- both controllers solve on the
+    four-wheel model, problem b on controllers_dt[b]; the same list as plants_dt= where both are given, exclusive with regression=.
     Raises ValueError when the two solvers differ in N or vehicle: one launch shifts both controllers' plans with one model."""
     import numpy as np
     import torch
@@ -624,6 +654,11 @@ def run_lmpc_fleet_fused(tracker, learner, track: dict, x0, u0, warm_laps: int =
     if poll < 1:
         raise ValueError("run_lmpc_fleet_fused: poll must be >= 1")
     B = x0.shape[1]
+    if controllers_dt is not None:
+        return _with_dtrack_controllers(
+            lambda: run_lmpc_fleet_fused(tracker, learner, track, x0, u0, warm_laps, learn_laps, dt, n_sub, warm_speed_scale, max_steps,
+                                         max_pts_per_lap, record_trace, regression, plant, poll, plants, warmup, _warm_plant, plants_dt),
+            "run_lmpc_fleet_fused", tracker, learner, B, controllers_dt, plants_dt, regression)
     if plants_dt is not None:
         if plants is not None:
             raise ValueError("run_lmpc_fleet_fused: plants= (single-track cars) and plants_dt= (double-track cars) are exclusive")

@@ -30,6 +30,7 @@
 #include "lmpc_fleet_loop.h"
 #include "lmpc_cars.h"
 #include "lmpc_dtrack.h"
+#include "lmpc_dtrack_model.h"
 
 namespace {
 // Move-only owner of one device (PINNED: pinned host) allocation: freed by the destructor, and by alloc() before it allocates anew.
@@ -138,6 +139,7 @@ struct __attribute__((visibility("hidden"))) lmpc_handle {  // (its members are 
   // double-track table (lmpc_dtrack_set_vehicles): one four-wheel plant vehicle per car, csrc/lmpc_dtrack.h
   dev_buf<double> dtrack_tab;  // [lmpc_dtrack_fields][dtrack_B] doubles | integrator int32 [dtrack_B]
   int dtrack_B = 0;            // 0: no table
+  bool dtrack_model = false;   // lmpc_dtrack_set_controller_model: solve_batch linearises problem b on vehicle b of the table
   // batched extended Kalman filter (lmpc_ekf_create): one filter per car, csrc/lmpc_ekf.h
   lmpc_ekf_store ekf{};  // raw copies of the two owners below, as the kernels take them
   dev_buf<double> ekf_xup;  // x [6][B] | u [2][B] | P [36][B]
@@ -599,6 +601,9 @@ int solve_batch(lmpc_handle* h, solve_args<> a) {
       !a.dU || !a.status || !a.iters)
     return fail(h, LMPC_ERR_ARGUMENT, "lmpc_solve_batch: null pointer or negative batch");
   if (const int rc = fleet_reg_batch_check(h, a.B, "lmpc_solve_batch")) return rc;
+  if (h->dtrack_model && a.B != h->dtrack_B)  // (before anything is touched: problem b is linearised on vehicle b)
+    return fail(h, LMPC_ERR_ARGUMENT, "lmpc_solve_batch: the double-track controller model is on (lmpc_dtrack_set_controller_model) and batch " +
+                                          std::to_string(a.B) + " is not the table's " + std::to_string(h->dtrack_B));
   // A configuration the mixed entry has no kernel for (the learning problem at N >= 24, the hard hull equality) is solved in fp64
   // (round 6, VERDICT r5 item 7 / weak 10: it was LMPC_ERR_UNSUPPORTED, and a caller iterating over horizons had to special-case a
   // valid reference configuration); lmpc_last_solve_precision tells the caller which it was.
@@ -614,7 +619,12 @@ int solve_batch(lmpc_handle* h, solve_args<> a) {
     if (rc != LMPC_OK) return rc;
   }
   if (h->timing) HIP_TRY(h, hipEventRecord(h->ev[0], h->stream));
-  int rc = launch_linearize(h, a.mixed ? 4 : 8, a.B, a.X_ref, a.U_ref, a.T_ref, a.curv, h->ws.get());
+  int rc = LMPC_OK;
+  if (h->dtrack_model)  // the four-wheel model of car b's vehicle into the same records (include/lmpc_hip_dtrack_model.h)
+    HIP_TRY(h, lmpc_dtrack_launch_linearize(h->stream, h->dtrack_tab.get(), h->P.N, a.B, true, a.X_ref, a.U_ref, a.T_ref, a.curv, h->ws.get(),
+                                            nullptr, nullptr));
+  else
+    rc = launch_linearize(h, a.mixed ? 4 : 8, a.B, a.X_ref, a.U_ref, a.T_ref, a.curv, h->ws.get());
   if (rc != LMPC_OK) return rc;
   if (h->reg_on) {  // error-dynamics regression onto the workspace (safe_set.cpp:182-245)
     rc = launch_regress<true>(h, a.B, a.X_ref, a.U_ref, h->ws.get(), nullptr, nullptr);
@@ -1148,6 +1158,8 @@ int lmpc_solve_batch_f32(lmpc_handle* h, int32_t batch, const float* x_ic, const
   if (h->P.learning) return fail(h, LMPC_ERR_UNSUPPORTED, "single precision is built for the tracking problem only");
   if (h->reg_on) return fail(h, LMPC_ERR_UNSUPPORTED, "the error-dynamics regression is applied in double precision only");
   if (h->freg_on) return fail(h, LMPC_ERR_UNSUPPORTED, "the per-car error-dynamics regression is applied in double precision only");
+  if (h->dtrack_model)
+    return fail(h, LMPC_ERR_UNSUPPORTED, "lmpc_solve_batch_f32: the double-track controller model is linearised in double precision only");
   if (batch == 0) return LMPC_OK;
   HIP_TRY(h, hipSetDevice(h->device));
   const launch_choice k = choose_kernel(h, SOLVE_F32);
@@ -1183,6 +1195,8 @@ int lmpc_solve_full_dynamics_batch(lmpc_handle* h, int32_t batch, const double* 
   if (batch < 0 || !X_ref || !U_ref || !X_optm || !U_optm || !dU_optm || !status || !iters || !sqp_iters || !sqp_move || !defect)
     return fail(h, LMPC_ERR_ARGUMENT, "lmpc_solve_full_dynamics_batch: null pointer or negative batch");
   if (max_sqp < 1) return fail(h, LMPC_ERR_ARGUMENT, "lmpc_solve_full_dynamics_batch: max_sqp < 1");
+  if (h->dtrack_model)  // (its defects and merit are the single-track model's: a handle corrects one model)
+    return fail(h, LMPC_ERR_UNSUPPORTED, "lmpc_solve_full_dynamics_batch: not built on the double-track controller model (lmpc_dtrack_set_controller_model)");
   if (h->P.learning && !convex_combi_optm) return fail(h, LMPC_ERR_ARGUMENT, "learning=1 needs convex_combi_optm");
   // (solve_batch refuses this too, but only after the outputs below have been overwritten with the start)
   if (h->P.learning && (!ss_x || !ss_j)) return fail(h, LMPC_ERR_ARGUMENT, "lmpc_solve_full_dynamics_batch: learning=1 needs ss_x and ss_j");
@@ -1475,6 +1489,7 @@ int lmpc_ss_query_host(lmpc_handle* h, const double* query, double* ss_x, double
 int lmpc_set_regression_laps(lmpc_handle* h, int32_t n_laps, const int32_t* n_pts, const double* x, const double* u,
                              const double* k, const double* t, const lmpc_regression_spec* spec) {
   if (!h) return LMPC_ERR_ARGUMENT;
+  if (h->dtrack_model && n_laps != 0 && spec) return fail(h, LMPC_ERR_UNSUPPORTED, std::string("lmpc_set_regression_laps") + ": the double-track controller model is on (lmpc_dtrack_set_controller_model): the regression holds residuals against the single-track model");
   HIP_TRY(h, hipSetDevice(h->device));
   HIP_TRY(h, hipStreamSynchronize(h->stream));
   reg_off(h);
@@ -1542,6 +1557,7 @@ int lmpc_set_regression_laps_rows(lmpc_handle* h, int32_t n_laps, const int32_t*
     reg_off(h);
     return LMPC_OK;
   }
+  if (h->dtrack_model) return fail(h, LMPC_ERR_UNSUPPORTED, std::string("lmpc_set_regression_laps_rows") + ": the double-track controller model is on (lmpc_dtrack_set_controller_model): the regression holds residuals against the single-track model");
   if (h->freg_on)
     return fail(h, LMPC_ERR_ARGUMENT,
                 "lmpc_set_regression_laps_rows: the per-car regression is on (lmpc_fleet_ss_set_regression / _rows); switch it off first");
@@ -1924,6 +1940,7 @@ int lmpc_dtrack_set_vehicles(lmpc_handle* h, int32_t batch, const lmpc_vehicle_d
   if (off) {
     h->dtrack_tab.release();
     h->dtrack_B = 0;
+    h->dtrack_model = false;  // (no table, no controller model: include/lmpc_hip_dtrack_model.h)
     return LMPC_OK;
   }
   const size_t nd = lmpc_dtrack_doubles((size_t)batch);
@@ -1962,6 +1979,42 @@ int lmpc_plant_step_dtrack_batch(lmpc_handle* h, int32_t batch, const lmpc_track
   if (!track_ok(track) || !x || !u || !(dt_sim > 0.0) || n_sub < 1) return fail(h, LMPC_ERR_ARGUMENT, std::string(who) + ": bad argument");
   HIP_TRY(h, hipSetDevice(h->device));
   HIP_TRY(h, lmpc_dtrack_launch_step(h->stream, h->dtrack_tab.get(), batch, *track, x, u, dt_sim, n_sub, gamma_y_or_null));
+  return LMPC_OK;
+}
+
+// ---- the double-track CONTROLLER model (include/lmpc_hip_dtrack_model.h, csrc/lmpc_dtrack_model.h, csrc/lmpc_dtrack_model_kernel.hip) ----
+int lmpc_linearize_dtrack_batch(lmpc_handle* h, int32_t batch, const double* X_ref, const double* U_ref, const double* T_ref,
+                                const double* curvatures, double* A, double* Bm, double* g) {
+  if (!h) return LMPC_ERR_ARGUMENT;
+  const char* who = "lmpc_linearize_dtrack_batch";
+  if (!h->dtrack_B) return fail(h, LMPC_ERR_ARGUMENT, std::string(who) + ": no double-track table (lmpc_dtrack_set_vehicles)");
+  if (batch != h->dtrack_B)
+    return fail(h, LMPC_ERR_ARGUMENT, std::string(who) + ": batch " + std::to_string(batch) + " is not the table's " + std::to_string(h->dtrack_B));
+  if (!X_ref || !U_ref || !T_ref || !curvatures || !A || !Bm || !g) return fail(h, LMPC_ERR_ARGUMENT, std::string(who) + ": null pointer");
+  HIP_TRY(h, hipSetDevice(h->device));
+  HIP_TRY(h, lmpc_dtrack_launch_linearize(h->stream, h->dtrack_tab.get(), h->P.N, batch, false, X_ref, U_ref, T_ref, curvatures, A, Bm, g));
+  return LMPC_OK;
+}
+
+int lmpc_dtrack_set_controller_model(lmpc_handle* h, int32_t on) {
+  if (!h) return LMPC_ERR_ARGUMENT;
+  const char* who = "lmpc_dtrack_set_controller_model";
+  if (!on) {
+    h->dtrack_model = false;
+    return LMPC_OK;
+  }
+  if (!h->dtrack_B) return fail(h, LMPC_ERR_ARGUMENT, std::string(who) + ": no double-track table (lmpc_dtrack_set_vehicles)");
+  if (h->reg_on || h->freg_on)
+    return fail(h, LMPC_ERR_UNSUPPORTED, std::string(who) + ": an error-dynamics regression is in effect (" +
+                                             (h->reg_on ? "lmpc_set_regression_laps / _rows" : "lmpc_fleet_ss_set_regression / _rows") +
+                                             "); its residuals are against the single-track model: switch it off first");
+  h->dtrack_model = true;
+  return LMPC_OK;
+}
+
+int lmpc_dtrack_get_controller_model(const lmpc_handle* h, int32_t* on) {
+  if (!h || !on) return LMPC_ERR_ARGUMENT;
+  *on = h->dtrack_model ? 1 : 0;
   return LMPC_OK;
 }
 
@@ -2080,6 +2133,7 @@ int lmpc_fleet_ss_set_regression(lmpc_handle* h, const lmpc_regression_spec* spe
     fleet_reg_off(h);
     return LMPC_OK;
   }
+  if (h->dtrack_model) return fail(h, LMPC_ERR_UNSUPPORTED, std::string("lmpc_fleet_ss_set_regression") + ": the double-track controller model is on (lmpc_dtrack_set_controller_model): the regression holds residuals against the single-track model");
   if (!h->fleet.B) return fail(h, LMPC_ERR_ARGUMENT, "lmpc_fleet_ss_set_regression: no fleet store (lmpc_fleet_ss_create)");
   if (h->reg_on)
     return fail(h, LMPC_ERR_ARGUMENT, "lmpc_fleet_ss_set_regression: lmpc_set_regression_laps is in effect; switch it off first");
@@ -2109,6 +2163,7 @@ int lmpc_fleet_ss_set_regression_rows(lmpc_handle* h, const lmpc_regression_rows
     fleet_reg_off(h);
     return LMPC_OK;
   }
+  if (h->dtrack_model) return fail(h, LMPC_ERR_UNSUPPORTED, std::string("lmpc_fleet_ss_set_regression_rows") + ": the double-track controller model is on (lmpc_dtrack_set_controller_model): the regression holds residuals against the single-track model");
   if (!h->fleet.B) return fail(h, LMPC_ERR_ARGUMENT, "lmpc_fleet_ss_set_regression_rows: no fleet store (lmpc_fleet_ss_create)");
   if (h->reg_on)
     return fail(h, LMPC_ERR_ARGUMENT,
