@@ -49,12 +49,13 @@ __device__ __forceinline__ double lmpc_knn_point(int c, int n, int& rep, int& j)
   return (double)(n - 1 - j) + (1 - rep) * (double)(n - 1);
 }
 
-// one DPP step of the arg-min: lanes outside ROW_MASK see the identity (+inf, INT_MAX)
+// one DPP step of the arg-min.  The moves carry no identity: lanes outside ROW_MASK end the step with an unspecified pair, and the
+// only lane lmpc_knn_wave_argmin reads, lane 63, is written at every one of its steps (the lane argument stands in lmpc_wave.hip.h)
 template <int CTRL, int ROW_MASK>
 __device__ __forceinline__ void lmpc_knn_argmin_step(double& d, int& i) {
-  const int od_lo = __builtin_amdgcn_update_dpp(0, __double2loint(d), CTRL, ROW_MASK, 0xf, false);
-  const int od_hi = __builtin_amdgcn_update_dpp(0x7ff00000, __double2hiint(d), CTRL, ROW_MASK, 0xf, false);
-  const int oi = __builtin_amdgcn_update_dpp(INT_MAX, i, CTRL, ROW_MASK, 0xf, false);
+  const int od_lo = __builtin_amdgcn_mov_dpp(__double2loint(d), CTRL, ROW_MASK, 0xf, false);
+  const int od_hi = __builtin_amdgcn_mov_dpp(__double2hiint(d), CTRL, ROW_MASK, 0xf, false);
+  const int oi = __builtin_amdgcn_mov_dpp(i, CTRL, ROW_MASK, 0xf, false);
   const double od = __hiloint2double(od_hi, od_lo);
   if (lmpc_knn_less(od, oi, d, i)) {
     d = od;

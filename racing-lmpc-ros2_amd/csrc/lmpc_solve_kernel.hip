@@ -1003,6 +1003,7 @@ struct Wave1 {
   static constexpr int ROW_CHUNK = lmpc_row_chunk(REAL_BYTES, KQ, KS), SITES = lmpc_opaque_sites(REAL_BYTES, KQ, KS);
   static constexpr bool OPAQUE_SLOTS = lmpc_opaque_slots(REAL_BYTES, KQ, KS), FUSE = lmpc_fuse_bwd(REAL_BYTES, KQ, KS);
   static constexpr bool NBHD = REAL_BYTES == 8 && KQ <= 7, POLISH_CALL = lmpc_polish_is_call(REAL_BYTES, KQ, KS);
+  static constexpr bool RID = lmpc_reduce_identity(REAL_BYTES, KQ, KS, 1);  // (the DPP reductions keep their identity operand)
   const int tid, lane;
   __device__ __forceinline__ Wave1() : tid(threadIdx.x), lane(threadIdx.x) {}
   template <typename real>
@@ -1016,36 +1017,36 @@ struct Wave1 {
   template <typename real>
   __device__ static __forceinline__ real exchanged(real x) { return x; }
   template <typename real>
-  __device__ static __forceinline__ real sum_of(real x) { return wave_sum(x); }
+  __device__ static __forceinline__ real sum_of(real x) { return wave_sum<RID>(x); }
   __device__ static __forceinline__ void publish(bool) { wave_sync(); }
   __device__ static __forceinline__ void after_polish() {}
   template <typename real, typename io>  // (the function itself, not a wrapper of it: what crosses the call stays by value as the caller wrote it)
   static constexpr PolishResult<real, KS> (*polish_call)(const PolishArgs<real, KQ, KS>) = &lmpc_polish_call<real, KQ, KS, io, SECOND>;
   template <typename real>
-  __device__ static __forceinline__ void sum2(real (&v)[2]) { wave_sum_n<2>(v); }
+  __device__ static __forceinline__ void sum2(real (&v)[2]) { wave_sum_n<2, RID>(v); }
   template <typename real>
-  __device__ static __forceinline__ real max(real x) { return wave_max(x); }
+  __device__ static __forceinline__ real max(real x) { return wave_max<RID>(x); }
   template <typename real>
-  __device__ static __forceinline__ real min(real x) { return wave_min(x); }
-  __device__ static __forceinline__ bool all(bool p) { return wave_min(p ? 1.0 : 0.0) > 0.5; }
+  __device__ static __forceinline__ real min(real x) { return wave_min<RID>(x); }
+  __device__ static __forceinline__ bool all(bool p) { return wave_min<RID>(p ? 1.0 : 0.0) > 0.5; }
   template <typename real>
-  __device__ static __forceinline__ real weights_sum(real q, real x) { return uni(q + wave_sum(x)); }
+  __device__ static __forceinline__ real weights_sum(real q, real x) { return uni(q + wave_sum<RID>(x)); }
   template <typename real>
-  __device__ static __forceinline__ void sum3(real (&v)[3]) { wave_sum_n<3>(v); }
+  __device__ static __forceinline__ void sum3(real (&v)[3]) { wave_sum_n<3, RID>(v); }
   template <typename real>
   __device__ static __forceinline__ void step_end(real, bool) {}  // (nothing yet: every value is reduced where it is read)
   template <typename real>
   __device__ static __forceinline__ void kkt(bool, bool, bool, bool, real, real) {}
   __device__ static __forceinline__ bool any_of(int, bool p) { return __ballot(p) != 0; }
   template <typename real>
-  __device__ static __forceinline__ real min_of(int, real x) { return wave_min(x); }
+  __device__ static __forceinline__ real min_of(int, real x) { return wave_min<RID>(x); }
   template <typename real>
-  __device__ static __forceinline__ real max_of(int, real x) { return wave_max(x); }
+  __device__ static __forceinline__ real max_of(int, real x) { return wave_max<RID>(x); }
   template <typename real>
-  __device__ static __forceinline__ real mean(real x, real inv_m) { return uni(wave_sum(x) * inv_m); }
+  __device__ static __forceinline__ real mean(real x, real inv_m) { return uni(wave_sum<RID>(x) * inv_m); }
   __device__ static __forceinline__ bool changed(bool p) { return __ballot(p) != 0; }
   template <typename real>
-  __device__ static __forceinline__ real sum(real x) { return wave_sum(x); }
+  __device__ static __forceinline__ real sum(real x) { return wave_sum<RID>(x); }
 };
 
 // KQ: slots per lane (one wave: the class's; two waves: lmpc_w2_slots of it, and the class is the team's)
@@ -1202,7 +1203,7 @@ __device__ __forceinline__ PolishResult<real, KS> lmpc_polish(const PolishArgs<r
           cand = better ? thq[q] : cand;
           cq = better ? q : cq;
         }
-        const treal best = wave_min(cand);
+        const treal best = wave_min<TEAM::RID>(cand);
         if (!(best < tinf)) break;
         const int owner = __ffsll((long long)__ballot(cand == best)) - 1;
         if (lane == owner) {
@@ -1249,8 +1250,8 @@ __device__ __forceinline__ PolishResult<real, KS> lmpc_polish(const PolishArgs<r
         for (int k = 0; k < 21; ++k) red[k] = tt[k];
 #pragma unroll
         for (int k = 0; k < 11; ++k) red[21 + k] = av[k];
-        wave_sum_split<32>(red, lane);
-        wave_sum_split<3>(red3, lane);
+        wave_sum_split<32, TEAM::RID>(red, lane);
+        wave_sum_split<3, TEAM::RID>(red3, lane);
 #pragma unroll
         for (int k = 0; k < 21; ++k) tt[k] = red[k];
 #pragma unroll
@@ -1312,7 +1313,7 @@ __device__ __forceinline__ PolishResult<real, KS> lmpc_polish(const PolishArgs<r
 #pragma unroll
           for (int c = 0; c < 6; ++c) bs[c] += uq[c] * w;
         }
-        wave_sum_split<7>(bs, lane);
+        wave_sum_split<7, TEAM::RID>(bs, lane);
         wave_fence();
         treal beta[6], h[6], nu;
 #pragma unroll
@@ -1421,7 +1422,7 @@ __device__ __forceinline__ PolishResult<real, KS> lmpc_polish(const PolishArgs<r
 #pragma unroll
           for (int c = 0; c < 6; ++c) gs[c] += uq[c] * w;
         }
-        wave_sum_split<7>(gs, lane);
+        wave_sum_split<7, TEAM::RID>(gs, lane);
         wave_fence();
         treal beta[6], h[6], nu;
 #pragma unroll
@@ -1480,7 +1481,7 @@ __device__ __forceinline__ PolishResult<real, KS> lmpc_polish(const PolishArgs<r
           for (int c = 0; c < 6; ++c) ul[c] += uq[c] * sx.lm[q];
           ul[6] += sx.lm[q];
         }
-        wave_sum_split<7>(ul, lane);
+        wave_sum_split<7, TEAM::RID>(ul, lane);
         sx.r1 = 1.0 - ul[6];
         if (lane < 6) {
           treal e = 0.0;
@@ -1879,7 +1880,7 @@ __device__ __forceinline__ void lmpc_solve_problem(
       sx.j[q] = sx.on[q] ? sx.j[q] : treal(0);
       n_on += sx.on[q] ? real(1) : real(0);
     }
-    const treal inv_on = treal(1) / treal(uni(wave_sum(n_on)));
+    const treal inv_on = treal(1) / treal(uni(wave_sum<TEAM::RID>(n_on)));
     lm_cold = inv_on;
 #pragma unroll
     for (int q = 0; q < KS; ++q) {
@@ -1900,7 +1901,7 @@ __device__ __forceinline__ void lmpc_solve_problem(
       for (int k = 0; k < 6; ++k) v += treal(P.chs2[k]) * uq[k] * uq[k];
       umax = fmax(umax, v);
     }
-    sx.tau = uni(treal(TAU_REL) * wave_max(umax));
+    sx.tau = uni(treal(TAU_REL) * wave_max<TEAM::RID>(umax));
     sx.m = 0;
   }
   const real m_tot = tm.sum(m_rows);
@@ -2099,7 +2100,7 @@ __device__ __forceinline__ void lmpc_solve_problem(
           const int f = flags(q);
           if (f & F_SIG) sgmax = fmax(sgmax, fmax((f & F_UP) ? vw[q] - hlw[q].x : real(0), (f & F_LO) ? hlw[q].y - vw[q] : real(0)));
         }
-        sigma = uni(wave_max(sgmax));
+        sigma = uni(wave_max<TEAM::RID>(sgmax));
 #pragma unroll
         for (int q = 0; q < KQ; ++q) {
           const int f = flags(q);
@@ -2122,7 +2123,7 @@ __device__ __forceinline__ void lmpc_solve_problem(
             lw[q] = sx.on[q] ? fmax(treal(P.warm_lam[(size_t)(j < S ? j : 0) * B + b]), treal(0)) : treal(0);
             lsum += lw[q];
           }
-          lsum = uni(wave_sum(lsum));
+          lsum = uni(wave_sum<TEAM::RID>(lsum));
           lam_ok = lsum > treal(0);
           const treal inv = lam_ok ? treal(1) / lsum : treal(0);
 #pragma unroll
@@ -2178,7 +2179,7 @@ __device__ __forceinline__ void lmpc_solve_problem(
 #pragma unroll
       for (int k = 0; k < 6; ++k) ul[k] += uq[k] * sx.lm[q];
     }
-    wave_sum_split<6>(ul, lane);
+    wave_sum_split<6, TEAM::RID>(ul, lane);
     if (lane < 6) {
       treal e = 0.0;
 #pragma unroll
@@ -2230,7 +2231,7 @@ __device__ __forceinline__ void lmpc_solve_problem(
 #pragma unroll
             for (int k = 0; k < 6; ++k) bs[k] += uq[k] * w;
           }
-          wave_sum_split<7>(bs, lane);
+          wave_sum_split<7, TEAM::RID>(bs, lane);
           wave_fence();
           PT_MARK(13)
           treal beta[6], h[6], nu;
@@ -2369,7 +2370,7 @@ __device__ __forceinline__ void lmpc_solve_problem(
             cand = better ? thq[q] : cand;
             cq = better ? q : cq;
           }
-          const treal best = wave_min(cand);
+          const treal best = wave_min<TEAM::RID>(cand);
           if (!(best < tinf)) break;
           const int owner = __ffsll((long long)__ballot(cand == best)) - 1;  // the lowest lane holding the minimum
           if (lane == owner) {
@@ -2420,8 +2421,8 @@ __device__ __forceinline__ void lmpc_solve_problem(
           for (int k = 0; k < 21; ++k) red[k] = tt[k];
 #pragma unroll
           for (int k = 0; k < 11; ++k) red[21 + k] = av[k];
-          wave_sum_split<32>(red, lane);
-          wave_sum_split<3>(red3, lane);
+          wave_sum_split<32, TEAM::RID>(red, lane);
+          wave_sum_split<3, TEAM::RID>(red3, lane);
 #pragma unroll
           for (int k = 0; k < 21; ++k) tt[k] = red[k];
 #pragma unroll
@@ -2643,7 +2644,7 @@ __device__ __forceinline__ void lmpc_solve_problem(
 #pragma unroll
           for (int k = 0; k < 6; ++k) gs[k] += uq[k] * w;
         }
-        wave_sum_split<7>(gs, lane);
+        wave_sum_split<7, TEAM::RID>(gs, lane);
         wave_fence();
         treal beta[6], h[6], nu;
 #pragma unroll

@@ -1,7 +1,7 @@
 // lmpc_solve_layout.hip.h -- what a solve kernel's LDS block looks like and which form of the code each instantiation takes.
 // Holds: the LDS record layout of both layouts (stage / knot / tail offsets, the lean records, slot kinds and flags, MROWS), the handles
 // onto it (Lds, SimplexRows), the per-instantiation constexpr policy functions (waves per SIMD, lean layout, polish call, row chunks,
-// opaque slot tables, fused backward sweep, chain addresses), each with the measurement that decided it, and the description of the
+// opaque slot tables, fused backward sweep, chain addresses, the reductions' identity), each with the measurement that decided it, and the description of the
 // three forms of a stage chain (ChainForm, StageCells, CHAIN_GET / CHAIN_PUT) that the one body per chain in lmpc_solve_kernel.hip is
 // written against.  Needs: lmpc_device.h (record strides) and lmpc_wave.hip.h (LDS addresses, fences).
 // Included by lmpc_solve_kernel.hip, i.e. by all three translation units (lmpc_lib.hip, lmpc_lib_minreg.hip, lmpc_lib_w2.hip).
@@ -207,6 +207,19 @@ __host__ __device__ constexpr bool lmpc_fuse_bwd(int real_bytes, int kq, int ks)
 // fused into its factorisation -- bit equal as well, but the FUSE + JOSEPH body inside the polish's call frame costs 284 B of scratch
 // per lane (672 -> 956 B in the headline kernel) and the headline 17 % (same document, section 8).
 __host__ __device__ constexpr bool lmpc_chain_addr(int real_bytes, int kq, int ks) { return real_bytes == 8 && kq <= 4 && ks == 0; }
+
+// Which instantiations keep the identity operand of the DPP reductions (lmpc_wave.hip.h: KEEP_ID).  Without it a reduction step is two
+// v_mov_b32_dpp and the operation -- no identity moves, fewer hazard nops: the headline kernel loses 311 of 11 560 instructions and
+// keeps its registers, scratch and spills -- and lane 63, the only lane read, has the same bits.  It is the default; kept are the
+// instantiations in which the shorter form made the register allocation worse (scratch bytes or spilled VGPRs up, scratch/kinfo.py on
+// the whole library: profiles/wave_reductions.md section 2):
+//   fp64 learning with KQ >= 7 -- "the most register-starved family" of lmpc_fuse_bwd above -- cold and warm:
+//     <7, 3> 258 -> 259 spilled VGPRs, <14, 2> 698 -> 702, <14, 3> 3384 -> 3416 B and 752 -> 781, warm <7, 2> 311 -> 325, warm <11, 3> 1064 -> 1084;
+//   the two-wave kernel of KQ = 14: 836 -> 852 B, 298 -> 302.
+// Every other kernel keeps or lowers both figures.  waves: wavefronts per problem.
+__host__ __device__ constexpr bool lmpc_reduce_identity(int real_bytes, int kq, int ks, int waves) {
+  return (real_bytes == 8 && kq >= 7 && ks > 0) || (waves == 2 && kq >= 14);
+}
 
 // ---- the three forms of a stage chain ----------------------------------------------------------------------------------------------
 // The Riccati factorisation and the LDS-exchange rollout (lmpc_solve_kernel.hip) each state their stage arithmetic ONCE; the vector

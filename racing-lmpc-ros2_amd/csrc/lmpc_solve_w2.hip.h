@@ -57,10 +57,11 @@ struct Wg2 {
 };
 __device__ __forceinline__ void wg_sync() { __syncthreads(); }
 
-template <class OP, int NV>
+// (RID: the wave's half keeps the identity operand of its DPP moves, lmpc_reduce_identity; only lane 63 of it is read either way)
+template <class OP, int NV, bool RID>
 __device__ __forceinline__ void wg_reduce_n(Wg2& g, double (&v)[NV]) {
   static_assert(NV <= 8, "eight values per exchange");
-  wave_reduce_n<OP, NV>(v);  // (wave-uniform)
+  wave_reduce_n<OP, NV, RID>(v);  // (wave-uniform)
   double* cell = g.red + g.par * 16;
   if ((threadIdx.x & 63) == 0) {
 #pragma unroll
@@ -71,22 +72,26 @@ __device__ __forceinline__ void wg_reduce_n(Wg2& g, double (&v)[NV]) {
   for (int k = 0; k < NV; ++k) v[k] = uni(OP::f(cell[k], cell[8 + k]));  // wave 0's share first, in both waves: the same bits
   g.par ^= 1;
 }
+template <bool RID>
 __device__ __forceinline__ double wg_sum(Wg2& g, double x) {
   double v[1] = {x};
-  wg_reduce_n<op_sum, 1>(g, v);
+  wg_reduce_n<op_sum, 1, RID>(g, v);
   return v[0];
 }
+template <bool RID>
 __device__ __forceinline__ double wg_max(Wg2& g, double x) {
   double v[1] = {x};
-  wg_reduce_n<op_max, 1>(g, v);
+  wg_reduce_n<op_max, 1, RID>(g, v);
   return v[0];
 }
+template <bool RID>
 __device__ __forceinline__ double wg_min(Wg2& g, double x) {
   double v[1] = {x};
-  wg_reduce_n<op_min, 1>(g, v);
+  wg_reduce_n<op_min, 1, RID>(g, v);
   return v[0];
 }
-__device__ __forceinline__ bool wg_any(Wg2& g, bool p) { return wg_max(g, __ballot(p) != 0 ? 1.0 : 0.0) > 0.5; }
+template <bool RID>
+__device__ __forceinline__ bool wg_any(Wg2& g, bool p) { return wg_max<RID>(g, __ballot(p) != 0 ? 1.0 : 0.0) > 0.5; }
 
 // ---- the team of two waves: lmpc_solve_problem and lmpc_polish themselves (lmpc_solve_kernel.hip), run by this team ----
 // Wave2 is what the two bodies ask of a team (the account stands with Wave1, next to the polish): the rows on 128 threads, the slots
@@ -110,6 +115,7 @@ struct Wave2 {
   static constexpr int ROW_CHUNK = KL, SITES = 0;  // (all slots of a lane in one go)
   static constexpr bool OPAQUE_SLOTS = true, FUSE = lmpc_fuse_bwd(8, KQ, 0);
   static constexpr bool NBHD = KQ <= 7, POLISH_CALL = true;
+  static constexpr bool RID = lmpc_reduce_identity(8, KQ, 0, 2);
   const int tid, lane;
   Wg2 g;
   double ex[6];  // what the last step_end / kkt exchange agreed on, by PolishSlot
@@ -120,29 +126,29 @@ struct Wave2 {
   __device__ static __forceinline__ void published() {}
   __device__ static __forceinline__ void after_chain() { wg_sync(); }
   __device__ static __forceinline__ double uniform(double x) { return x; }
-  __device__ __forceinline__ double exchanged(double x) { return wg_sum(g, x); }
+  __device__ __forceinline__ double exchanged(double x) { return wg_sum<RID>(g, x); }
   __device__ static __forceinline__ double sum_of(double x) { return x; }
   __device__ static __forceinline__ void publish(bool next) { if (!next) wg_sync(); }
   // (the polish leaves its exchange parity behind; both waves restart from the same one)
   __device__ __forceinline__ void after_polish() { g.par = 0; wg_sync(); }
   template <typename real, typename io>
   static constexpr PolishResult<double, 0> (*polish_call)(const PolishArgs<double, KL, 0>) = &lmpc_polish_call_w2<KQ, KL, CHAIN_>;
-  __device__ __forceinline__ void sum2(double (&v)[2]) { wg_reduce_n<op_sum, 2>(g, v); }
-  __device__ __forceinline__ double max(double x) { return wg_max(g, x); }
-  __device__ __forceinline__ double min(double x) { return wg_min(g, x); }
-  __device__ __forceinline__ bool all(bool p) { return wg_min(g, p ? 1.0 : 0.0) > 0.5; }
-  __device__ __forceinline__ double weights_sum(double q, double x) { return q + wg_sum(g, x); }
-  __device__ __forceinline__ void sum3(double (&v)[3]) { wg_reduce_n<op_sum, 3>(g, v); }
+  __device__ __forceinline__ void sum2(double (&v)[2]) { wg_reduce_n<op_sum, 2, RID>(g, v); }
+  __device__ __forceinline__ double max(double x) { return wg_max<RID>(g, x); }
+  __device__ __forceinline__ double min(double x) { return wg_min<RID>(g, x); }
+  __device__ __forceinline__ bool all(bool p) { return wg_min<RID>(g, p ? 1.0 : 0.0) > 0.5; }
+  __device__ __forceinline__ double weights_sum(double q, double x) { return q + wg_sum<RID>(g, x); }
+  __device__ __forceinline__ void sum3(double (&v)[3]) { wg_reduce_n<op_sum, 3, RID>(g, v); }
   __device__ __forceinline__ void step_end(double stepmax, bool bad) {
     double red[2] = {stepmax, bad ? 1.0 : 0.0};
-    wg_reduce_n<op_max, 2>(g, red);
+    wg_reduce_n<op_max, 2, RID>(g, red);
     ex[PS_STEP] = red[0];
     ex[PS_NAN] = red[1];
   }
   __device__ __forceinline__ void kkt(bool bad, bool neg, bool weak, bool viol, double ymin, double worst) {
     double vote[6] = {__ballot(bad) != 0 ? 1.0 : 0.0, __ballot(neg) != 0 ? 1.0 : 0.0, __ballot(weak) != 0 ? 1.0 : 0.0,
                       __ballot(viol) != 0 ? 1.0 : 0.0, -ymin, worst};
-    wg_reduce_n<op_max, 6>(g, vote);
+    wg_reduce_n<op_max, 6, RID>(g, vote);
 #pragma unroll
     for (int k = 0; k < 6; ++k) ex[k] = vote[k];
   }
@@ -150,9 +156,9 @@ struct Wave2 {
   __device__ __forceinline__ bool any_of(int slot, bool) const { return ex[slot] > 0.5; }
   __device__ __forceinline__ double min_of(int slot, double) const { return -ex[slot]; }  // (exchanged as a maximum of its negative)
   __device__ __forceinline__ double max_of(int slot, double) const { return ex[slot]; }
-  __device__ __forceinline__ double mean(double x, double inv_m) { return wg_sum(g, x) * inv_m; }
-  __device__ __forceinline__ bool changed(bool p) { return wg_any(g, p); }
-  __device__ __forceinline__ double sum(double x) { return wg_sum(g, x); }
+  __device__ __forceinline__ double mean(double x, double inv_m) { return wg_sum<RID>(g, x) * inv_m; }
+  __device__ __forceinline__ bool changed(bool p) { return wg_any<RID>(g, p); }
+  __device__ __forceinline__ double sum(double x) { return wg_sum<RID>(g, x); }
 };
 
 // (a call, as in the one-wave fp64 kernels: lmpc_polish_call; what crosses it stays by value)

@@ -67,15 +67,46 @@ __device__ __forceinline__ float group_bcast(float v) { return __int_as_float(__
 // Wave reductions on the VALU (DPP), not through the LDS crossbar (ds_bpermute): the LDS pipeline is this kernel's
 // tightest resource and a 6-step bpermute chain costs ~460 cycles of latency against ~130 here.  Four row_ror steps
 // leave every lane of a 16-lane row with the row's total, row_bcast15 / row_bcast31 fold the rows into lane 63.
-template <int CTRL, int ROW_MASK>
+//
+// The moves carry NO "old" operand (__builtin_amdgcn_mov_dpp, not update_dpp with an identity): a lane the DPP does not write
+// then holds an unspecified value, and the compiler no longer materialises an identity (two v_mov_b32 and usually an s_nop for
+// the DPP read hazard) in front of every step of every reduced value.  That is sound only where every lane that is READ
+// afterwards is WRITTEN at every step.  The lane argument for wave_reduce_n, whose only read is lane 63:
+//   steps 1 - 4, row_ror 8 / 4 / 2 / 1, row mask 0xf: every lane has a source in its own row and every row is enabled;
+//   step 5, row_bcast15, row mask 0xa: writes rows 1 and 3 (lanes 16 .. 31 from lane 15, lanes 48 .. 63 from lane 47);
+//           lane 63 is in row 3; its source, lane 47, is read as steps 1 - 4 left it (a DPP reads the value before its own step);
+//   step 6, row_bcast31, row mask 0xc: writes rows 2 and 3 from lane 31; lane 63 is in row 3; lane 31 is in row 1, written by
+//           steps 1 - 5.
+// Lanes of rows 0 and 2 combine an unspecified value in step 5 (rows 0 and 1 in step 6) and nobody reads them afterwards: a
+// new reader of any lane but 63 has to bring the identity back.  pair_exchange below runs full masks on controls that give
+// every lane a source, so every lane is written.
+//
+// The association order the steps produce is a contract (tests/cpp/test_wave_reduce.hip restates it on the host and compares
+// bits).  With x[r][j] lane j of row r, t = f(v, moved) at every step, and row_ror:n giving lane j the value of lane
+// (j - n) mod 16 of its row:
+//   a[j] = f(x[j], x[j - 8]);  b[j] = f(a[j], a[j - 4]);  c[j] = f(b[j], b[j - 2]);  R_r = f(c[15], c[14])    (indices mod 16)
+//   result = f(f(R_3, R_2), f(R_1, R_0))
+// f's first argument is always the lane's own value, the second the moved one (fmax / fmin of a NaN and a number is the number).
+//
+// KEEP_ID = true is the form with the identity as "old" (unwritten lanes keep it): the same bits in lane 63 and in every
+// exchanged lane, for the instantiations whose register allocation the shorter form makes worse (lmpc_reduce_identity,
+// lmpc_solve_layout.hip.h).
+template <int CTRL, int ROW_MASK, bool KEEP_ID = false>
 __device__ __forceinline__ double dpp_move(double x, double identity) {
-  const int lo = __builtin_amdgcn_update_dpp(__double2loint(identity), __double2loint(x), CTRL, ROW_MASK, 0xf, false);
-  const int hi = __builtin_amdgcn_update_dpp(__double2hiint(identity), __double2hiint(x), CTRL, ROW_MASK, 0xf, false);
-  return __hiloint2double(hi, lo);
+  if constexpr (KEEP_ID) {
+    const int lo = __builtin_amdgcn_update_dpp(__double2loint(identity), __double2loint(x), CTRL, ROW_MASK, 0xf, false);
+    const int hi = __builtin_amdgcn_update_dpp(__double2hiint(identity), __double2hiint(x), CTRL, ROW_MASK, 0xf, false);
+    return __hiloint2double(hi, lo);
+  } else {
+    const int lo = __builtin_amdgcn_mov_dpp(__double2loint(x), CTRL, ROW_MASK, 0xf, false);
+    const int hi = __builtin_amdgcn_mov_dpp(__double2hiint(x), CTRL, ROW_MASK, 0xf, false);
+    return __hiloint2double(hi, lo);
+  }
 }
-template <int CTRL, int ROW_MASK>
+template <int CTRL, int ROW_MASK, bool KEEP_ID = false>
 __device__ __forceinline__ float dpp_move(float x, float identity) {
-  return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(identity), __float_as_int(x), CTRL, ROW_MASK, 0xf, false));
+  if constexpr (KEEP_ID) return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(identity), __float_as_int(x), CTRL, ROW_MASK, 0xf, false));
+  else return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(x), CTRL, ROW_MASK, 0xf, false));
 }
 #define DPP_ROW_ROR(n) (0x120 + (n))
 #define DPP_ROW_BCAST15 0x142
@@ -93,71 +124,71 @@ struct op_min {
   template <typename real> static __device__ __forceinline__ real f(real a, real b) { return fmin(a, b); }
 };
 // NV independent reductions in lock-step (their steps interleave); results as wave-uniform scalars
-template <class OP, int NV, typename real>
+template <class OP, int NV, bool KEEP_ID = false, typename real>
 __device__ __forceinline__ void wave_reduce_n(real (&v)[NV]) {
   const real id = OP::template id<real>();
 #pragma unroll
-  for (int k = 0; k < NV; ++k) v[k] = OP::f(v[k], dpp_move<DPP_ROW_ROR(8), 0xf>(v[k], id));
+  for (int k = 0; k < NV; ++k) v[k] = OP::f(v[k], dpp_move<DPP_ROW_ROR(8), 0xf, KEEP_ID>(v[k], id));
 #pragma unroll
-  for (int k = 0; k < NV; ++k) v[k] = OP::f(v[k], dpp_move<DPP_ROW_ROR(4), 0xf>(v[k], id));
+  for (int k = 0; k < NV; ++k) v[k] = OP::f(v[k], dpp_move<DPP_ROW_ROR(4), 0xf, KEEP_ID>(v[k], id));
 #pragma unroll
-  for (int k = 0; k < NV; ++k) v[k] = OP::f(v[k], dpp_move<DPP_ROW_ROR(2), 0xf>(v[k], id));
+  for (int k = 0; k < NV; ++k) v[k] = OP::f(v[k], dpp_move<DPP_ROW_ROR(2), 0xf, KEEP_ID>(v[k], id));
 #pragma unroll
-  for (int k = 0; k < NV; ++k) v[k] = OP::f(v[k], dpp_move<DPP_ROW_ROR(1), 0xf>(v[k], id));
+  for (int k = 0; k < NV; ++k) v[k] = OP::f(v[k], dpp_move<DPP_ROW_ROR(1), 0xf, KEEP_ID>(v[k], id));
 #pragma unroll
-  for (int k = 0; k < NV; ++k) v[k] = OP::f(v[k], dpp_move<DPP_ROW_BCAST15, 0xa>(v[k], id));
+  for (int k = 0; k < NV; ++k) v[k] = OP::f(v[k], dpp_move<DPP_ROW_BCAST15, 0xa, KEEP_ID>(v[k], id));
 #pragma unroll
-  for (int k = 0; k < NV; ++k) v[k] = OP::f(v[k], dpp_move<DPP_ROW_BCAST31, 0xc>(v[k], id));
+  for (int k = 0; k < NV; ++k) v[k] = OP::f(v[k], dpp_move<DPP_ROW_BCAST31, 0xc, KEEP_ID>(v[k], id));
 #pragma unroll
   for (int k = 0; k < NV; ++k) v[k] = lane_bcast(v[k], 63);
 }
 #undef DPP_ROW_ROR
 #undef DPP_ROW_BCAST15
 #undef DPP_ROW_BCAST31
-template <typename real>
+template <bool KEEP_ID = false, typename real>
 __device__ __forceinline__ real wave_sum(real x) {
   real v[1] = {x};
-  wave_reduce_n<op_sum, 1>(v);
+  wave_reduce_n<op_sum, 1, KEEP_ID>(v);
   return v[0];
 }
-template <typename real>
+template <bool KEEP_ID = false, typename real>
 __device__ __forceinline__ real wave_max(real x) {
   real v[1] = {x};
-  wave_reduce_n<op_max, 1>(v);
+  wave_reduce_n<op_max, 1, KEEP_ID>(v);
   return v[0];
 }
-template <typename real>
+template <bool KEEP_ID = false, typename real>
 __device__ __forceinline__ real wave_min(real x) {
   real v[1] = {x};
-  wave_reduce_n<op_min, 1>(v);
+  wave_reduce_n<op_min, 1, KEEP_ID>(v);
   return v[0];
 }
-template <int NV, typename real>
+template <int NV, bool KEEP_ID = false, typename real>
 __device__ __forceinline__ void wave_sum_n(real (&v)[NV]) {
-  wave_reduce_n<op_sum, NV>(v);
+  wave_reduce_n<op_sum, NV, KEEP_ID>(v);
 }
 
 // Exchange with the partner lane that differs in bit BIT of the lane number (and, for bits 2 and 3, in the bits below:
 // the row mirrors are the involutions DPP offers there) -- every pairing used by wave_sum_split below.
-template <int BIT>
+template <int BIT, bool KEEP_ID = false>
 __device__ __forceinline__ double pair_exchange(double x) {
   if constexpr (BIT == 5) return __shfl_xor(x, 32, 64);
   if constexpr (BIT == 4)  // ds_swizzle, bit mode: and 0x1f, or 0, xor 0x10
     return __hiloint2double(__builtin_amdgcn_ds_swizzle(__double2hiint(x), 0x401F), __builtin_amdgcn_ds_swizzle(__double2loint(x), 0x401F));
-  if constexpr (BIT == 3) return dpp_move<0x140, 0xf>(x, 0.0);  // row_mirror
-  if constexpr (BIT == 2) return dpp_move<0x141, 0xf>(x, 0.0);  // row_half_mirror
-  if constexpr (BIT == 1) return dpp_move<0x4E, 0xf>(x, 0.0);   // quad_perm [2,3,0,1]
-  return dpp_move<0xB1, 0xf>(x, 0.0);                            // quad_perm [1,0,3,2]
+  if constexpr (BIT == 3) return dpp_move<0x140, 0xf, KEEP_ID>(x, 0.0);  // row_mirror
+  if constexpr (BIT == 2) return dpp_move<0x141, 0xf, KEEP_ID>(x, 0.0);  // row_half_mirror
+  if constexpr (BIT == 1) return dpp_move<0x4E, 0xf, KEEP_ID>(x, 0.0);   // quad_perm [2,3,0,1]
+  return dpp_move<0xB1, 0xf, KEEP_ID>(x, 0.0);                            // quad_perm [1,0,3,2]
 }
-template <int BIT>
-__device__ __forceinline__ float pair_exchange(float x) { return (float)pair_exchange<BIT>((double)x); }
+template <int BIT, bool KEEP_ID = false>
+__device__ __forceinline__ float pair_exchange(float x) { return (float)pair_exchange<BIT, KEEP_ID>((double)x); }
 
 // Many sums at once, for NV up to 32 (the safe-set block reduces 35 per iteration): instead of NV full reductions, each
 // step pairs the lanes across one bit of the lane number and SPLITS the values between the partners -- the lane with
 // the bit clear keeps the lower half (adding its partner's contributions), the other the upper half -- so the work
 // halves with every step: P/2 + P/4 + ... exchanges for P values instead of 6 P.  After log2 P steps lane l holds the
 // partial total of value l >> (6 - log2 P) over its group; plain pairwise sums over the remaining bits finish it.
-template <int NV, typename real>
+template <int NV, bool KEEP_ID = false, typename real>
 __device__ __forceinline__ void wave_sum_split(real (&v)[NV], int lane) {
   constexpr int P = NV <= 2 ? 2 : NV <= 4 ? 4 : NV <= 8 ? 8 : NV <= 16 ? 16 : 32;
   constexpr int LOGP = P == 2 ? 1 : P == 4 ? 2 : P == 8 ? 3 : P == 16 ? 4 : 5;
@@ -172,12 +203,12 @@ __device__ __forceinline__ void wave_sum_split(real (&v)[NV], int lane) {
     for (int k = 0; k < H; ++k) {
       const real keep = up ? a[k + H] : a[k];
       const real send = up ? a[k] : a[k + H];
-      a[k] = keep + pair_exchange<BIT>(send);
+      a[k] = keep + pair_exchange<BIT, KEEP_ID>(send);
     }
   };
   auto fold = [&](auto bit_c) {
     constexpr int BIT = decltype(bit_c)::value;
-    a[0] = a[0] + pair_exchange<BIT>(a[0]);
+    a[0] = a[0] + pair_exchange<BIT, KEEP_ID>(a[0]);
   };
   using std::integral_constant;
   // bits 5, 4, 3, 2, 1 carry the splits while more than one value is left; the rest are plain sums
