@@ -770,6 +770,9 @@ int lmpc_fleet_ss_regress_batch(lmpc_handle* h, int32_t batch, const double* X_r
 /* The double-track controller model (lmpc_linearize_dtrack_batch, lmpc_dtrack_set_controller_model, lmpc_dtrack_get_controller_model):
  * declared in lmpc_hip_dtrack_model.h. */
 #include "lmpc_hip_dtrack_model.h"
+/* The per-car single-track controller model (lmpc_linearize_cars_batch, lmpc_cars_set_controller_model, lmpc_cars_get_controller_model):
+ * declared in lmpc_hip_cars_model.h. */
+#include "lmpc_hip_cars_model.h"
 
 /* Spline track: RacingTrajectory's interpolants on the device (racing_trajectory.cpp:25-120) and the two conversions built on them.
  * The five interpolating not-a-knot cubics -- x, y, speed, left and right boundary offset over the abscissa of the waypoints, closed by

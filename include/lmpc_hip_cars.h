@@ -8,9 +8,11 @@
  *
  * What it is for: a Monte-Carlo run over model mismatch in ONE process on ONE handle -- each car's grip, mass and tyre parameters
  * drawn separately, each controller learning from its own laps (the per-car safe set and the per-car error-dynamics regression of
- * lmpc_hip.h) how ITS car differs from the nominal model.  Only the PLANT knows which car it steps.  The controllers still share
- * one model, the handle's lmpc_vehicle: the linearisation, the solve kernels, the reference rollouts (lmpc_prepare_batch,
- * lmpc_shift_batch and their fused forms) and the body width of worst_excess are not per car.  Neither are lmpc_loop_advance_batch,
+ * lmpc_hip.h) how ITS car differs from the nominal model.  This header is the PLANT.  The controllers share one model, the handle's
+ * lmpc_vehicle, unless lmpc_cars_set_controller_model (lmpc_hip_cars_model.h) puts the batched solves on this table, problem b
+ * linearised on vehicle b: the baseline of the experiment, a controller that knows its car.  Even then only the LINEARISATION is per
+ * car: the actuator and rate boxes of the solve kernels, the reference rollouts (lmpc_prepare_batch, lmpc_shift_batch and their
+ * fused forms) and the body width of worst_excess stay on the handle's vehicle.  So do lmpc_loop_advance_batch,
  * lmpc_vanilla_rollout_batch and the sharded solver: they step every car with one vehicle, table or no table.
  */
 #ifndef LMPC_HIP_CARS_H_
@@ -31,7 +33,9 @@
  * the fleet store's and lmpc_fleet_loop.plant must be NULL -- the call has one source for its plant --, either violation is
  * LMPC_ERR_ARGUMENT before anything is written.  Everything else in that call keeps the handle's vehicle: the rollouts of the
  * references (the shift's last knot, the in-place shift, the cold restart) and the body width in worst_excess.  Without a table the
- * call is what it is without this header.  No other entry point reads the table.  The same call on four-wheel cars is
+ * call is what it is without this header.  Besides it, lmpc_plant_step_cars_batch below and the fleet rollout of
+ * lmpc_hip_vanilla_fleet.h with LMPC_VANILLA_PLANT_CARS, the table is read by lmpc_hip_cars_model.h: lmpc_linearize_cars_batch, and the batched solves while lmpc_cars_set_controller_model is on.
+ * veh = NULL or batch = 0 switches that controller model off with the table; a replaced table keeps it.  The same call on four-wheel cars is
  * lmpc_fleet_loop_advance_dtrack_batch of lmpc_hip_fleet_dtrack.h, whose plant is the double-track table of lmpc_hip_dtrack.h: by
  * the same rule it is refused (LMPC_ERR_ARGUMENT) while a car table is set. */
 int lmpc_cars_set_vehicles(lmpc_handle* h, int32_t batch, const lmpc_vehicle* veh);

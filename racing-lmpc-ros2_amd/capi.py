@@ -47,6 +47,8 @@ _ABI_SYMBOLS_VANILLA_FLEET = ("lmpc_vanilla_rollout_fleet_batch",)
 _ABI_SYMBOLS_FLEET_DTRACK = ("lmpc_fleet_loop_advance_dtrack_batch",)
 # the entry points of include/lmpc_hip_dtrack_model.h (the double-track controller model), resolved at load time in a loop of their own
 _ABI_SYMBOLS_DTRACK_MODEL = ("lmpc_linearize_dtrack_batch", "lmpc_dtrack_set_controller_model", "lmpc_dtrack_get_controller_model")
+# the entry points of include/lmpc_hip_cars_model.h (the per-car single-track controller model), resolved at load time in a loop of their own
+_ABI_SYMBOLS_CARS_MODEL = ("lmpc_linearize_cars_batch", "lmpc_cars_set_controller_model", "lmpc_cars_get_controller_model")
 VANILLA_PLANT = {"handle": 0, "cars": 1, "dtrack": 2}           # LMPC_VANILLA_PLANT_*
 VANILLA_RECORD = {None: 0, "applied": 1, "arrived": 2}          # LMPC_VANILLA_RECORD_*
 EKF_FALLBACK, EKF_R_REPAIRED, EKF_NOT_FINITE = 1, 2, 4   # bits of the per-car flags of Solver.ekf_update
@@ -208,6 +210,8 @@ def load_library():
         for sym in _ABI_SYMBOLS_FLEET_DTRACK:
             getattr(lib, sym)
         for sym in _ABI_SYMBOLS_DTRACK_MODEL:
+            getattr(lib, sym)
+        for sym in _ABI_SYMBOLS_CARS_MODEL:
             getattr(lib, sym)
         lib.lmpc_last_error.restype = C.c_char_p
         lib.lmpc_last_error.argtypes = [C.c_void_p]
@@ -575,6 +579,35 @@ class Solver:
         """lmpc_dtrack_get_controller_model: whether the solves run on the double-track model."""
         on = C.c_int32(0)
         self._check(self.lib.lmpc_dtrack_get_controller_model(self._h, C.byref(on)), "lmpc_dtrack_get_controller_model")
+        return bool(on.value)
+
+    # ---- the per-car single-track controller model (include/lmpc_hip_cars_model.h) ----
+    def linearize_cars(self, inp: dict, out=None):
+        """lmpc_linearize_cars_batch: what linearize returns -- A [6, 6, N-1, B], Bm [6, 2, N-1, B], g [6, N-1, B] -- with problem b
+        linearised on vehicle b of the car table (set_car_vehicles).  `out`: an (A, Bm, g) of float64 tensors to write into instead of
+        fresh ones.  Asynchronous; refused without a table or with a batch other than the table's."""
+        torch = self._torch
+        self.use_current_stream()
+        X, U, T, kap = (self._t(inp[k]) for k in ("X_ref", "U_ref", "T_ref", "curvatures"))
+        B, N = X.shape[2], self.N
+        kw = dict(dtype=torch.float64, device=self.device)
+        A, Bm, g = out if out is not None else (torch.empty((6, 6, N - 1, B), **kw), torch.empty((6, 2, N - 1, B), **kw),
+                                                torch.empty((6, N - 1, B), **kw))
+        rc = self.lib.lmpc_linearize_cars_batch(self._h, C.c_int32(B), _ptr(X), _ptr(U), _ptr(T), _ptr(kap), _ptr(A), _ptr(Bm), _ptr(g))
+        self._check(rc, "lmpc_linearize_cars_batch")
+        return A, Bm, g
+
+    def set_cars_controller_model(self, on: bool):
+        """lmpc_cars_set_controller_model: while on, solve(...) -- fp64, mixed, warm, with the safe set as arrays or by reference --
+        and solve_f32 linearise problem b on vehicle b of the car table and must be given the table's batch; the sequential-QP solve
+        is refused.  Needs a table; refused while a regression or the double-track controller model is in effect.  Host-only."""
+        self._check(self.lib.lmpc_cars_set_controller_model(self._h, C.c_int32(1 if on else 0)), "lmpc_cars_set_controller_model")
+
+    @property
+    def cars_controller_model(self) -> bool:
+        """lmpc_cars_get_controller_model: whether the solves linearise each problem on its car's vehicle."""
+        on = C.c_int32(0)
+        self._check(self.lib.lmpc_cars_get_controller_model(self._h, C.byref(on)), "lmpc_cars_get_controller_model")
         return bool(on.value)
 
     # ---- RacingMPC::solve (racing_mpc.cpp:209-372) ----

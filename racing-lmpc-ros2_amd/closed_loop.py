@@ -439,10 +439,33 @@ def _with_dtrack_controllers(run, who, tracker, learner, B, controllers_dt, plan
             sv.set_dtrack_vehicles(None)
 
 
+def _with_cars_controllers(run, who, tracker, learner, B, controllers, plant, plants, plants_dt, controllers_dt, regression):
+    """controllers= of run_lmpc_fleet / run_lmpc_fleet_fused: the list is the car table of both handles and both solve on it
+    (Solver.set_cars_controller_model) while `run(plants)` runs; switch and tables are off again on the way out, whatever happened."""
+    if regression is not None:
+        raise ValueError(who + ": controllers= and regression= are exclusive (the regression corrects the handle's vehicle)")
+    if controllers_dt is not None or plants_dt is not None:
+        raise ValueError(who + ": controllers= (single-track cars) is exclusive with controllers_dt= and plants_dt= (double-track cars)")
+    if plant is not None:
+        raise ValueError(who + ": controllers= and plant= are exclusive (a handle with a car table steps its plant with that table)")
+    if plants is not None and plants is not controllers and list(plants) != list(controllers):
+        raise ValueError(who + ": the plant reads the learner's car table, so plants= and controllers= must be the same list")
+    _check_plants(None, controllers, B, who, "controllers")
+    try:
+        for sv in (tracker, learner):
+            sv.set_car_vehicles(controllers)
+            sv.set_cars_controller_model(True)
+        return run(controllers)
+    finally:
+        for sv in (tracker, learner):
+            sv.set_cars_controller_model(False)
+            sv.set_car_vehicles(None)
+
+
 def run_lmpc_fleet(tracker, learner, track: dict, x0, u0, warm_laps: int = 2, learn_laps: int = 4, dt: float = 0.025,
                    n_sub: int = 2, warm_speed_scale: float = 0.7, max_steps: int = 20000, max_pts_per_lap: int = 1024,
                    record_trace: bool = False, regression: dict | None = None, plant=None, plants=None, plants_dt=None,
-                   warmup: dict | None = None, _warm_plant: str = "handle", controllers_dt=None):
+                   warmup: dict | None = None, _warm_plant: str = "handle", controllers_dt=None, controllers=None):
     """run_lmpc with every car learning from ITS OWN laps: the fleet safe set on `learner` (lmpc_fleet_ss_*: one recorder and one
     ring of max_lap_stored laps per car, on the device) replaces the host recorder of car 0 and the shared store.  Per period, in
     run_lmpc's order: record (x, u_prev, curvature at s, t) for all cars, query every learning car's own ring, solve, plant step,
@@ -476,11 +499,22 @@ def run_lmpc_fleet(tracker, learner, track: dict, x0, u0, warm_laps: int = 2, le
     controllers_dt (a list of B double-track vehicle dicts, usually plants_dt's list): the CONTROLLERS' model -- the list is the
     double-track table of both handles and both solve on it, problem b linearised on controllers_dt[b]
     (Solver.set_dtrack_controller_model); switch and tables are off again on return.  The plant reads the learner's table, so with
-    plants_dt= it must be the same list, and it is exclusive with regression=: ValueError otherwise."""
+    plants_dt= it must be the same list, and it is exclusive with regression=: ValueError otherwise.
+    controllers (a list of B single-track vehicle dicts, usually plants=' list): the CONTROLLERS' model on single-track cars -- the
+    list is the car table of both handles and both solve on it, problem b linearised on controllers[b]
+    (Solver.set_cars_controller_model); switch and tables are off again on return.  The plant reads the learner's table: the cars
+    drive on the same list (plants= may be left out; where it is given it must be the same list), and controllers= is exclusive with
+    plant=, regression=, controllers_dt= and plants_dt=: ValueError otherwise.  Boxes, reference rollouts and worst_excess's body width
+    stay on the handles' vehicle (include/lmpc_hip_cars_model.h)."""
     import numpy as np
     import torch
 
     B = x0.shape[1]
+    if controllers is not None:
+        return _with_cars_controllers(
+            lambda same: run_lmpc_fleet(tracker, learner, track, x0, u0, warm_laps, learn_laps, dt, n_sub, warm_speed_scale, max_steps,
+                                        max_pts_per_lap, record_trace, None, None, same, None, warmup, _warm_plant),
+            "run_lmpc_fleet", tracker, learner, B, controllers, plant, plants, plants_dt, controllers_dt, regression)
     if controllers_dt is not None:
         return _with_dtrack_controllers(
             lambda: run_lmpc_fleet(tracker, learner, track, x0, u0, warm_laps, learn_laps, dt, n_sub, warm_speed_scale, max_steps, max_pts_per_lap,
@@ -622,7 +656,7 @@ def run_lmpc_fleet(tracker, learner, track: dict, x0, u0, warm_laps: int = 2, le
 def run_lmpc_fleet_fused(tracker, learner, track: dict, x0, u0, warm_laps: int = 2, learn_laps: int = 4, dt: float = 0.025,
                          n_sub: int = 2, warm_speed_scale: float = 0.7, max_steps: int = 20000, max_pts_per_lap: int = 1024,
                          record_trace: bool = False, regression: dict | None = None, plant=None, poll: int = 1, plants=None,
-                         warmup: dict | None = None, _warm_plant: str = "handle", plants_dt=None, controllers_dt=None):
+                         warmup: dict | None = None, _warm_plant: str = "handle", plants_dt=None, controllers_dt=None, controllers=None):
     """run_lmpc_fleet with everything between two solves in one launch, lmpc_fleet_loop_advance_batch on `learner`: input selection
     between the two controllers' results, plant, shift, x_ic, every car's recorder and ring, the lap book, the per-car phase and the
     next query point.  Same arguments, same experiment, same return dictionary; per period the fleet query when any car learns, the
@@ -645,6 +679,9 @@ def run_lmpc_fleet_fused(tracker, learner, track: dict, x0, u0, warm_laps: int =
     head-only call then sends every car whose ring holds warm_laps laps straight to the learning controller.
     controllers_dt (a list of B double-track vehicle dicts, usually plants_dt's list): run_lmpc_fleet's -- both controllers solve on the
     four-wheel model, problem b on controllers_dt[b]; the same list as plants_dt= where both are given, exclusive with regression=.
+    controllers (a list of B single-track vehicle dicts, usually plants=' list): run_lmpc_fleet's -- both controllers linearise problem b
+    on controllers[b] and the cars drive on the same list; the same list as plants= where both are given, exclusive with plant=,
+    regression=, controllers_dt= and plants_dt=.
     Raises ValueError when the two solvers differ in N or vehicle: one launch shifts both controllers' plans with one model."""
     import numpy as np
     import torch
@@ -654,6 +691,11 @@ def run_lmpc_fleet_fused(tracker, learner, track: dict, x0, u0, warm_laps: int =
     if poll < 1:
         raise ValueError("run_lmpc_fleet_fused: poll must be >= 1")
     B = x0.shape[1]
+    if controllers is not None:
+        return _with_cars_controllers(
+            lambda same: run_lmpc_fleet_fused(tracker, learner, track, x0, u0, warm_laps, learn_laps, dt, n_sub, warm_speed_scale, max_steps,
+                                              max_pts_per_lap, record_trace, None, None, poll, same, warmup, _warm_plant),
+            "run_lmpc_fleet_fused", tracker, learner, B, controllers, plant, plants, plants_dt, controllers_dt, regression)
     if controllers_dt is not None:
         return _with_dtrack_controllers(
             lambda: run_lmpc_fleet_fused(tracker, learner, track, x0, u0, warm_laps, learn_laps, dt, n_sub, warm_speed_scale, max_steps,

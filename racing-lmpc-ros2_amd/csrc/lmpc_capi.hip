@@ -31,6 +31,7 @@
 #include "lmpc_cars.h"
 #include "lmpc_dtrack.h"
 #include "lmpc_dtrack_model.h"
+#include "lmpc_cars_model.h"
 
 namespace {
 // Move-only owner of one device (PINNED: pinned host) allocation: freed by the destructor, and by alloc() before it allocates anew.
@@ -136,6 +137,7 @@ struct __attribute__((visibility("hidden"))) lmpc_handle {  // (its members are 
   // car table (lmpc_cars_set_vehicles): one plant vehicle per car, csrc/lmpc_cars.h
   dev_buf<double> cars_tab;  // [lmpc_cars_fields][cars_B] doubles | integrator int32 [cars_B]
   int cars_B = 0;            // 0: no table
+  bool cars_model = false;   // lmpc_cars_set_controller_model: the batched solves linearise problem b on vehicle b of the car table
   // double-track table (lmpc_dtrack_set_vehicles): one four-wheel plant vehicle per car, csrc/lmpc_dtrack.h
   dev_buf<double> dtrack_tab;  // [lmpc_dtrack_fields][dtrack_B] doubles | integrator int32 [dtrack_B]
   int dtrack_B = 0;            // 0: no table
@@ -604,6 +606,9 @@ int solve_batch(lmpc_handle* h, solve_args<> a) {
   if (h->dtrack_model && a.B != h->dtrack_B)  // (before anything is touched: problem b is linearised on vehicle b)
     return fail(h, LMPC_ERR_ARGUMENT, "lmpc_solve_batch: the double-track controller model is on (lmpc_dtrack_set_controller_model) and batch " +
                                           std::to_string(a.B) + " is not the table's " + std::to_string(h->dtrack_B));
+  if (h->cars_model && a.B != h->cars_B)
+    return fail(h, LMPC_ERR_ARGUMENT, "lmpc_solve_batch: the per-car controller model is on (lmpc_cars_set_controller_model) and batch " +
+                                          std::to_string(a.B) + " is not the car table's " + std::to_string(h->cars_B));
   // A configuration the mixed entry has no kernel for (the learning problem at N >= 24, the hard hull equality) is solved in fp64
   // (round 6, VERDICT r5 item 7 / weak 10: it was LMPC_ERR_UNSUPPORTED, and a caller iterating over horizons had to special-case a
   // valid reference configuration); lmpc_last_solve_precision tells the caller which it was.
@@ -623,6 +628,9 @@ int solve_batch(lmpc_handle* h, solve_args<> a) {
   if (h->dtrack_model)  // the four-wheel model of car b's vehicle into the same records (include/lmpc_hip_dtrack_model.h)
     HIP_TRY(h, lmpc_dtrack_launch_linearize(h->stream, h->dtrack_tab.get(), h->P.N, a.B, true, a.X_ref, a.U_ref, a.T_ref, a.curv, h->ws.get(),
                                             nullptr, nullptr));
+  else if (h->cars_model)  // the single-track model of car b's own vehicle into the same records (include/lmpc_hip_cars_model.h)
+    HIP_TRY(h, lmpc_cars_launch_linearize(h->stream, h->cars_tab.get(), h->P.N, a.B, true, a.X_ref, a.U_ref, a.T_ref, a.curv, h->ws.get(), nullptr,
+                                          nullptr));
   else
     rc = launch_linearize(h, a.mixed ? 4 : 8, a.B, a.X_ref, a.U_ref, a.T_ref, a.curv, h->ws.get());
   if (rc != LMPC_OK) return rc;
@@ -1160,6 +1168,9 @@ int lmpc_solve_batch_f32(lmpc_handle* h, int32_t batch, const float* x_ic, const
   if (h->freg_on) return fail(h, LMPC_ERR_UNSUPPORTED, "the per-car error-dynamics regression is applied in double precision only");
   if (h->dtrack_model)
     return fail(h, LMPC_ERR_UNSUPPORTED, "lmpc_solve_batch_f32: the double-track controller model is linearised in double precision only");
+  if (h->cars_model && batch != h->cars_B)  // (before anything is touched: problem b is linearised on vehicle b)
+    return fail(h, LMPC_ERR_ARGUMENT, "lmpc_solve_batch_f32: the per-car controller model is on (lmpc_cars_set_controller_model) and batch " +
+                                          std::to_string(batch) + " is not the car table's " + std::to_string(h->cars_B));
   if (batch == 0) return LMPC_OK;
   HIP_TRY(h, hipSetDevice(h->device));
   const launch_choice k = choose_kernel(h, SOLVE_F32);
@@ -1174,7 +1185,10 @@ int lmpc_solve_batch_f32(lmpc_handle* h, int32_t batch, const float* x_ic, const
     });
   if (rc != LMPC_OK) return rc;
   if (h->timing) HIP_TRY(h, hipEventRecord(h->ev[0], h->stream));
-  rc = launch_linearize(h, 4, batch, X_ref, U_ref, T_ref, curvatures, h->ws_f32.get());
+  if (h->cars_model)  // (include/lmpc_hip_cars_model.h: the io = float instantiation, fp64 arithmetic on car b's vehicle)
+    HIP_TRY(h, lmpc_cars_launch_linearize_f32(h->stream, h->cars_tab.get(), h->P.N, batch, X_ref, U_ref, T_ref, curvatures, h->ws_f32.get()));
+  else
+    rc = launch_linearize(h, 4, batch, X_ref, U_ref, T_ref, curvatures, h->ws_f32.get());
   if (rc != LMPC_OK) return rc;
   if (h->timing) HIP_TRY(h, hipEventRecord(h->ev[1], h->stream));
   const solve_args<float> a{batch, x_ic, u_ic, X_ref, U_ref, T_ref, bound_left, bound_right, curvatures, vel_ref, X_optm, U_optm, dU_optm, status, iters, kkt};
@@ -1197,6 +1211,8 @@ int lmpc_solve_full_dynamics_batch(lmpc_handle* h, int32_t batch, const double* 
   if (max_sqp < 1) return fail(h, LMPC_ERR_ARGUMENT, "lmpc_solve_full_dynamics_batch: max_sqp < 1");
   if (h->dtrack_model)  // (its defects and merit are the single-track model's: a handle corrects one model)
     return fail(h, LMPC_ERR_UNSUPPORTED, "lmpc_solve_full_dynamics_batch: not built on the double-track controller model (lmpc_dtrack_set_controller_model)");
+  if (h->cars_model)  // (the line search of lmpc_sqp_kernel.hip evaluates its defects on the handle's vehicle)
+    return fail(h, LMPC_ERR_UNSUPPORTED, "lmpc_solve_full_dynamics_batch: not built on the per-car controller model (lmpc_cars_set_controller_model)");
   if (h->P.learning && !convex_combi_optm) return fail(h, LMPC_ERR_ARGUMENT, "learning=1 needs convex_combi_optm");
   // (solve_batch refuses this too, but only after the outputs below have been overwritten with the start)
   if (h->P.learning && (!ss_x || !ss_j)) return fail(h, LMPC_ERR_ARGUMENT, "lmpc_solve_full_dynamics_batch: learning=1 needs ss_x and ss_j");
@@ -1490,6 +1506,7 @@ int lmpc_set_regression_laps(lmpc_handle* h, int32_t n_laps, const int32_t* n_pt
                              const double* k, const double* t, const lmpc_regression_spec* spec) {
   if (!h) return LMPC_ERR_ARGUMENT;
   if (h->dtrack_model && n_laps != 0 && spec) return fail(h, LMPC_ERR_UNSUPPORTED, std::string("lmpc_set_regression_laps") + ": the double-track controller model is on (lmpc_dtrack_set_controller_model): the regression holds residuals against the single-track model");
+  if (h->cars_model && n_laps != 0 && spec) return fail(h, LMPC_ERR_UNSUPPORTED, std::string("lmpc_set_regression_laps") + ": the per-car controller model is on (lmpc_cars_set_controller_model): the regression holds residuals against the handle's vehicle");
   HIP_TRY(h, hipSetDevice(h->device));
   HIP_TRY(h, hipStreamSynchronize(h->stream));
   reg_off(h);
@@ -1558,6 +1575,7 @@ int lmpc_set_regression_laps_rows(lmpc_handle* h, int32_t n_laps, const int32_t*
     return LMPC_OK;
   }
   if (h->dtrack_model) return fail(h, LMPC_ERR_UNSUPPORTED, std::string("lmpc_set_regression_laps_rows") + ": the double-track controller model is on (lmpc_dtrack_set_controller_model): the regression holds residuals against the single-track model");
+  if (h->cars_model) return fail(h, LMPC_ERR_UNSUPPORTED, std::string("lmpc_set_regression_laps_rows") + ": the per-car controller model is on (lmpc_cars_set_controller_model): the regression holds residuals against the handle's vehicle");
   if (h->freg_on)
     return fail(h, LMPC_ERR_ARGUMENT,
                 "lmpc_set_regression_laps_rows: the per-car regression is on (lmpc_fleet_ss_set_regression / _rows); switch it off first");
@@ -1862,6 +1880,7 @@ int lmpc_cars_set_vehicles(lmpc_handle* h, int32_t batch, const lmpc_vehicle* ve
   if (off) {
     h->cars_tab.release();
     h->cars_B = 0;
+    h->cars_model = false;  // (no table, no controller model: include/lmpc_hip_cars_model.h)
     return LMPC_OK;
   }
   const size_t B = (size_t)batch, nd = lmpc_cars_doubles(B);
@@ -1917,6 +1936,44 @@ int lmpc_plant_step_cars_batch(lmpc_handle* h, int32_t batch, const lmpc_track* 
   hipLaunchKernelGGL(lmpc_plant_cars_kernel, dim3((batch + 255) / 256), dim3(256), 0, h->stream, h->cars_tab.get(), batch, *track, x, u, dt_sim,
                      n_sub);
   HIP_TRY(h, hipGetLastError());
+  return LMPC_OK;
+}
+
+// ---- the per-car single-track CONTROLLER model (include/lmpc_hip_cars_model.h, csrc/lmpc_cars_model.h, csrc/lmpc_cars_model_kernel.hip) ----
+int lmpc_linearize_cars_batch(lmpc_handle* h, int32_t batch, const double* X_ref, const double* U_ref, const double* T_ref,
+                              const double* curvatures, double* A, double* Bm, double* g) {
+  if (!h) return LMPC_ERR_ARGUMENT;
+  const char* who = "lmpc_linearize_cars_batch";
+  if (!h->cars_B) return fail(h, LMPC_ERR_ARGUMENT, std::string(who) + ": no car table (lmpc_cars_set_vehicles)");
+  if (batch != h->cars_B)
+    return fail(h, LMPC_ERR_ARGUMENT, std::string(who) + ": batch " + std::to_string(batch) + " is not the table's " + std::to_string(h->cars_B));
+  if (!X_ref || !U_ref || !T_ref || !curvatures || !A || !Bm || !g) return fail(h, LMPC_ERR_ARGUMENT, std::string(who) + ": null pointer");
+  HIP_TRY(h, hipSetDevice(h->device));
+  HIP_TRY(h, lmpc_cars_launch_linearize(h->stream, h->cars_tab.get(), h->P.N, batch, false, X_ref, U_ref, T_ref, curvatures, A, Bm, g));
+  return LMPC_OK;
+}
+
+int lmpc_cars_set_controller_model(lmpc_handle* h, int32_t on) {
+  if (!h) return LMPC_ERR_ARGUMENT;
+  const char* who = "lmpc_cars_set_controller_model";
+  if (!on) {
+    h->cars_model = false;
+    return LMPC_OK;
+  }
+  if (!h->cars_B) return fail(h, LMPC_ERR_ARGUMENT, std::string(who) + ": no car table (lmpc_cars_set_vehicles)");
+  if (h->dtrack_model)
+    return fail(h, LMPC_ERR_UNSUPPORTED, std::string(who) + ": the double-track controller model is on (lmpc_dtrack_set_controller_model): a handle solves on one model; switch it off first");
+  if (h->reg_on || h->freg_on)
+    return fail(h, LMPC_ERR_UNSUPPORTED, std::string(who) + ": an error-dynamics regression is in effect (" +
+                                             (h->reg_on ? "lmpc_set_regression_laps / _rows" : "lmpc_fleet_ss_set_regression / _rows") +
+                                             "); its residuals are against the handle's vehicle: switch it off first");
+  h->cars_model = true;
+  return LMPC_OK;
+}
+
+int lmpc_cars_get_controller_model(const lmpc_handle* h, int32_t* on) {
+  if (!h || !on) return LMPC_ERR_ARGUMENT;
+  *on = h->cars_model ? 1 : 0;
   return LMPC_OK;
 }
 
@@ -2004,6 +2061,8 @@ int lmpc_dtrack_set_controller_model(lmpc_handle* h, int32_t on) {
     return LMPC_OK;
   }
   if (!h->dtrack_B) return fail(h, LMPC_ERR_ARGUMENT, std::string(who) + ": no double-track table (lmpc_dtrack_set_vehicles)");
+  if (h->cars_model)
+    return fail(h, LMPC_ERR_UNSUPPORTED, std::string(who) + ": the per-car controller model is on (lmpc_cars_set_controller_model): a handle solves on one model; switch it off first");
   if (h->reg_on || h->freg_on)
     return fail(h, LMPC_ERR_UNSUPPORTED, std::string(who) + ": an error-dynamics regression is in effect (" +
                                              (h->reg_on ? "lmpc_set_regression_laps / _rows" : "lmpc_fleet_ss_set_regression / _rows") +
@@ -2134,6 +2193,7 @@ int lmpc_fleet_ss_set_regression(lmpc_handle* h, const lmpc_regression_spec* spe
     return LMPC_OK;
   }
   if (h->dtrack_model) return fail(h, LMPC_ERR_UNSUPPORTED, std::string("lmpc_fleet_ss_set_regression") + ": the double-track controller model is on (lmpc_dtrack_set_controller_model): the regression holds residuals against the single-track model");
+  if (h->cars_model) return fail(h, LMPC_ERR_UNSUPPORTED, std::string("lmpc_fleet_ss_set_regression") + ": the per-car controller model is on (lmpc_cars_set_controller_model): the regression holds residuals against the handle's vehicle");
   if (!h->fleet.B) return fail(h, LMPC_ERR_ARGUMENT, "lmpc_fleet_ss_set_regression: no fleet store (lmpc_fleet_ss_create)");
   if (h->reg_on)
     return fail(h, LMPC_ERR_ARGUMENT, "lmpc_fleet_ss_set_regression: lmpc_set_regression_laps is in effect; switch it off first");
@@ -2164,6 +2224,7 @@ int lmpc_fleet_ss_set_regression_rows(lmpc_handle* h, const lmpc_regression_rows
     return LMPC_OK;
   }
   if (h->dtrack_model) return fail(h, LMPC_ERR_UNSUPPORTED, std::string("lmpc_fleet_ss_set_regression_rows") + ": the double-track controller model is on (lmpc_dtrack_set_controller_model): the regression holds residuals against the single-track model");
+  if (h->cars_model) return fail(h, LMPC_ERR_UNSUPPORTED, std::string("lmpc_fleet_ss_set_regression_rows") + ": the per-car controller model is on (lmpc_cars_set_controller_model): the regression holds residuals against the handle's vehicle");
   if (!h->fleet.B) return fail(h, LMPC_ERR_ARGUMENT, "lmpc_fleet_ss_set_regression_rows: no fleet store (lmpc_fleet_ss_create)");
   if (h->reg_on)
     return fail(h, LMPC_ERR_ARGUMENT,
