@@ -773,6 +773,9 @@ int lmpc_fleet_ss_regress_batch(lmpc_handle* h, int32_t batch, const double* X_r
 /* The per-car single-track controller model (lmpc_linearize_cars_batch, lmpc_cars_set_controller_model, lmpc_cars_get_controller_model):
  * declared in lmpc_hip_cars_model.h. */
 #include "lmpc_hip_cars_model.h"
+/* The fused estimated period (sensors, EKF, projection, plant and shift in one launch; its io struct lmpc_estimated_loop): declared
+ * in lmpc_hip_estimated.h. */
+#include "lmpc_hip_estimated.h"
 
 /* Spline track: RacingTrajectory's interpolants on the device (racing_trajectory.cpp:25-120) and the two conversions built on them.
  * The five interpolating not-a-knot cubics -- x, y, speed, left and right boundary offset over the abscissa of the waypoints, closed by

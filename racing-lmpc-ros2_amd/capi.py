@@ -49,6 +49,8 @@ _ABI_SYMBOLS_FLEET_DTRACK = ("lmpc_fleet_loop_advance_dtrack_batch",)
 _ABI_SYMBOLS_DTRACK_MODEL = ("lmpc_linearize_dtrack_batch", "lmpc_dtrack_set_controller_model", "lmpc_dtrack_get_controller_model")
 # the entry points of include/lmpc_hip_cars_model.h (the per-car single-track controller model), resolved at load time in a loop of their own
 _ABI_SYMBOLS_CARS_MODEL = ("lmpc_linearize_cars_batch", "lmpc_cars_set_controller_model", "lmpc_cars_get_controller_model")
+# the entry point of include/lmpc_hip_estimated.h (the fused estimated period), resolved at load time in a loop of its own
+_ABI_SYMBOLS_ESTIMATED = ("lmpc_loop_advance_estimated_batch",)
 VANILLA_PLANT = {"handle": 0, "cars": 1, "dtrack": 2}           # LMPC_VANILLA_PLANT_*
 VANILLA_RECORD = {None: 0, "applied": 1, "arrived": 2}          # LMPC_VANILLA_RECORD_*
 EKF_FALLBACK, EKF_R_REPAIRED, EKF_NOT_FINITE = 1, 2, 4   # bits of the per-car flags of Solver.ekf_update
@@ -129,6 +131,17 @@ class CFleetLoop(C.Structure):
                 + [(n, C.c_int32) for n in "n_sub restart_failed warm_laps learn_laps switch_phase n_rec".split()]
                 + [("plant", C.POINTER(CVehicle))]
                 + [(n, C.c_void_p) for n in "phase n_learn lap_time lap_kind counters x_ic query distance worst_excess n_fail".split()])
+
+
+class CEstimatedLoop(C.Structure):
+    """lmpc_estimated_loop of include/lmpc_hip_estimated.h: everything lmpc_loop_advance_estimated_batch takes beside the handle, the
+    batch and the two tracks."""
+    _fields_ = ([(n, C.c_void_p) for n in "X_optm U_optm status x u_prev x_ic X_ref U_ref T_ref bound_left bound_right curvatures vel_ref".split()]
+                + [(n, C.c_double) for n in "dt dt_sim speed_scale speed_limit".split()]
+                + [(n, C.c_int32) for n in "n_sub restart_failed obs_vel obs_pose".split()]
+                + [("t_vel_ns", C.c_int64), ("t_pose_ns", C.c_int64)]
+                + [(n, C.c_void_p) for n in "noise_vel R_vel noise_pose R_pose x_est z_vel z_pose ekf_flags track_status distance worst_excess "
+                                            "n_fail sq_err".split()])
 
 
 class CEkfConfig(C.Structure):
@@ -212,6 +225,8 @@ def load_library():
         for sym in _ABI_SYMBOLS_DTRACK_MODEL:
             getattr(lib, sym)
         for sym in _ABI_SYMBOLS_CARS_MODEL:
+            getattr(lib, sym)
+        for sym in _ABI_SYMBOLS_ESTIMATED:
             getattr(lib, sym)
         lib.lmpc_last_error.restype = C.c_char_p
         lib.lmpc_last_error.argtypes = [C.c_void_p]
@@ -1228,6 +1243,39 @@ class Solver:
         ns, init = C.c_int64(0), C.c_int32(0)
         self._check(self.lib.lmpc_ekf_get(self._h, C.c_int32(B), _ptr(x), _ptr(P), _ptr(K), C.byref(ns), C.byref(init)), "lmpc_ekf_get")
         return {"x": x, "P": P, "K": K, "timestamp_ns": int(ns.value), "initialized": bool(init.value)}
+
+    # ---- the fused estimated period (include/lmpc_hip_estimated.h) ----
+    def loop_advance_estimated(self, track: dict, spline: SplineTrack, inp: dict, sol: dict, x, u_prev, x_ic, dt: float, dt_sim: float, n_sub: int,
+                               obs_vel: int, obs_pose: int, t_vel_ns: int, t_pose_ns: int, noise_vel, R_vel, noise_pose, R_pose,
+                               speed_scale: float = 1.0, speed_limit: float | None = None, restart_failed: bool = True, x_est=None, z_vel=None,
+                               z_pose=None, ekf_flags=None, track_status=None, distance=None, worst_excess=None, n_fail=None, sq_err=None):
+        """lmpc_loop_advance_estimated_batch: one period of the estimated closed loop behind a solve, in one launch -- the input applied
+        (to u_prev and to the filter), the TRUTH x [6][B] stepped in two halves with the velocity observation (rows of obs_vel, plus
+        noise_vel [nz_v][B]) between them and the pose observation (rows of obs_pose, plus noise_pose [nz_p][B]; a NaN drops the
+        car's measurement) behind them, the two filter updates at t_vel_ns and t_pose_ns, the estimate projected into x_ic [6][B]
+        (seeded with the incoming x_ic[0]), and the next references in `inp` (shift; for a failed car the old plan shifted in place
+        or, restart_failed, a cold start at the new x_ic).  x, u_prev, x_ic and inp's seven arrays are updated in place.  Optional:
+        x_est [6][B] (global estimate), z_vel, z_pose (the measurements formed), and the accumulators ekf_flags int32 [B] (|=),
+        track_status int32 [B] (max), distance, worst_excess [B], n_fail int64 [B], sq_err [6][B].  The tensors are passed as they are
+        (float64 / int32 / int64, contiguous, on the device).  Asynchronous; no torch operation, nothing read back."""
+        self.use_current_stream()
+        ct = self._ctrack(track)
+        if speed_limit is None:
+            speed_limit = float(self.config["x_max"][3])
+        io = CEstimatedLoop()
+        ptrs = dict(X_optm=sol["X_optm"], U_optm=sol["U_optm"], status=sol["status"], x=x, u_prev=u_prev, x_ic=x_ic, noise_vel=noise_vel, R_vel=R_vel,
+                    noise_pose=noise_pose, R_pose=R_pose, x_est=x_est, z_vel=z_vel, z_pose=z_pose, ekf_flags=ekf_flags, track_status=track_status,
+                    distance=distance, worst_excess=worst_excess, n_fail=n_fail, sq_err=sq_err,
+                    **{k: inp[k] for k in ("X_ref", "U_ref", "T_ref", "bound_left", "bound_right", "curvatures", "vel_ref")})
+        for name, t in ptrs.items():
+            if t is not None and not t.is_contiguous():
+                raise ValueError(f"loop_advance_estimated: {name} must be contiguous (it is passed by pointer)")
+            setattr(io, name, None if t is None else t.data_ptr())
+        io.dt, io.dt_sim, io.speed_scale, io.speed_limit = float(dt), float(dt_sim), float(speed_scale), float(speed_limit)
+        io.n_sub, io.restart_failed, io.obs_vel, io.obs_pose = int(n_sub), 1 if restart_failed else 0, int(obs_vel), int(obs_pose)
+        io.t_vel_ns, io.t_pose_ns = int(t_vel_ns), int(t_pose_ns)
+        rc = self.lib.lmpc_loop_advance_estimated_batch(self._h, C.c_int32(x.shape[1]), C.byref(ct), spline._p, C.byref(io))
+        self._check(rc, "lmpc_loop_advance_estimated_batch")
 
     # ---- batched time-varying LQR, one controller per car (racing_lqr.cpp:45-96; include/lmpc_hip.h) ----
     def lqr_create(self, cfg: dict, max_batch: int):

@@ -270,6 +270,93 @@ def run_estimated(solver, track: dict, spline, x0, u0, steps: int, dt: float = 0
     return res
 
 
+def run_estimated_fused(solver, track: dict, spline, x0, u0, steps: int, dt: float = 0.025, n_sub: int = 2, speed_scale: float = 0.9,
+                        restart_failed: bool = True, sensors: dict | None = None, seed: int = 0, record_trace: bool = False, poll: int = 0):
+    """`run_estimated` with everything between two solves in ONE launch, lmpc_loop_advance_estimated_batch
+    (include/lmpc_hip_estimated.h): a period is the solve and that call, with no torch operation on the stream between them.  The same
+    arguments and result keys.  The noise is drawn from the same torch.Generator in the same order -- randn(6, B) for the start, then
+    per period randn(2, B), randn(3, B), rand(B) -- and a dropout is a NaN in noise_pose[0], so the two loops see identical sensors;
+    the statistics differ from run_estimated's only by the rounding of the fused kernel's arithmetic and by "rms_error" summing the
+    cars last (per-car sums of squares on the device, one mean at the end).
+    poll: how many periods run between host reads.  The loop itself reads nothing back; every `poll` periods the host waits for the
+    stream (which bounds the queue of launches and noise buffers ahead of the device), and poll = 0 waits once, at the end.
+    record_trace=True adds "trace" as run_estimated does, from per-period output buffers of the call; the estimate after a velocity
+    update is not an output of the fused call, so that entry's last member is None."""
+    import math
+
+    import torch
+
+    if n_sub % 2:
+        raise ValueError("run_estimated_fused: n_sub must be even (the velocity observation sits at mid-period)")
+    sn = dict(SENSORS, **(sensors or {}))
+    trk = solver.device_track(track)
+    x, u_prev = x0.clone(), u0.clone()
+    B, dev = x.shape[1], x.device
+    kw = dict(dtype=torch.float64, device=dev)
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(int(seed))
+    col = lambda v: torch.as_tensor(v, **kw)[:, None]  # noqa: E731
+    sig_v, sig_p, sd0 = col(sn["sig_vel"]), col(sn["sig_pose"]), col(sn["sd0"])
+    R_v = torch.diag(sig_v[:, 0] ** 2)[:, :, None].repeat(1, 1, B).contiguous()
+    R_p = torch.diag(sig_p[:, 0] ** 2)[:, :, None].repeat(1, 1, B).contiguous()
+    inf = math.inf
+    cfg = {"x0": [0.0] * 6, "P0": torch.diag(sd0[:, 0] ** 2).cpu().numpy(), "Q": torch.diag(torch.as_tensor(sn["Q"], dtype=torch.float64)).numpy(),
+           "x_min": [-inf] * 3 + [-float(c) for c in sn["clip"]], "x_max": [inf] * 3 + [float(c) for c in sn["clip"]]}
+    solver.ekf_create(B, **cfg)
+    o_vel, o_pose = solver.ekf_register_observation((3, 5)), solver.ekf_register_observation((0, 1, 2))
+    pose = solver.frenet_to_global(spline, x)
+    x_est = torch.cat([pose, x[3:6]]) + 0.5 * torch.randn((6, B), generator=gen, **kw) * sd0
+    x_est[3].clamp_(min=0.5)
+    x_est0 = x_est.clone()
+    P0 = torch.diag(sd0[:, 0] ** 2)[:, :, None].repeat(1, 1, B).contiguous()
+    solver.ekf_set_state(x_est, P0)
+    solver.ekf_initialize(0)
+    frenet, status = solver.global_to_frenet(spline, x_est[0:3].contiguous())
+    track_status = status.clone()
+    x_ic = torch.cat([frenet, x_est[3:6]]).contiguous()
+    inp = solver.prepare(trk, x_ic, dt, speed_scale=speed_scale)
+    out = solver.alloc_outputs(B)
+    dist, worst_excess = torch.zeros(B, **kw), torch.zeros(B, **kw)
+    n_fail = torch.zeros(B, dtype=torch.int64, device=dev)
+    flags_or = torch.zeros(B, dtype=torch.int32, device=dev)
+    sq_err = torch.zeros((6, B), **kw)
+    dt_ns = int(round(dt * 1e9))
+    dropout = float(sn["dropout"])
+    nan = torch.full((B,), math.nan, **kw)
+    trace = []
+    stream = torch.cuda.current_stream(dev)
+    for k in range(steps):
+        inp["x_ic"], inp["u_ic"] = x_ic, u_prev
+        solver.solve(inp, out)
+        # this period's sensors, in run_estimated's order of draws (fresh buffers: the launch that reads them is only queued)
+        noise_v = (sig_v * torch.randn((2, B), generator=gen, **kw)).contiguous()
+        noise_p = (sig_p * torch.randn((3, B), generator=gen, **kw)).contiguous()
+        noise_p[0] = torch.where(torch.rand((B,), generator=gen, **kw) < dropout, nan, noise_p[0])
+        ts_v, ts_p = k * dt_ns + dt_ns // 2, (k + 1) * dt_ns
+        rec = dict(x_est=x_est)
+        if record_trace:
+            rec = dict(x_est=torch.empty((6, B), **kw), z_vel=torch.empty((2, B), **kw), z_pose=torch.empty((3, B), **kw))
+            u_rec = torch.empty((2, B), **kw)
+        solver.loop_advance_estimated(trk, spline, inp, out, x, u_rec if record_trace else u_prev, x_ic, dt, dt / n_sub, n_sub, o_vel, o_pose,
+                                      ts_v, ts_p, noise_v, R_v, noise_p, R_p, speed_scale=speed_scale, restart_failed=restart_failed,
+                                      ekf_flags=flags_or, track_status=track_status, distance=dist, worst_excess=worst_excess, n_fail=n_fail,
+                                      sq_err=sq_err, **rec)
+        if record_trace:
+            u_prev = u_rec
+            x_est = rec["x_est"]
+            trace.append((o_vel, rec["z_vel"], R_v, u_rec, ts_v, None))
+            trace.append((o_pose, rec["z_pose"], R_p, u_rec, ts_p, x_est))
+        if poll and (k + 1) % poll == 0:
+            stream.synchronize()
+    stream.synchronize()
+    res = {"x": x, "distance": dist, "worst_excess": worst_excess, "n_fail": n_fail, "track_status": track_status, "warm_hit_rate": None,
+           "x_est": x_est, "rms_error": torch.sqrt(sq_err.mean(dim=1) / max(steps, 1)), "ekf_flags": flags_or, "x_est0": x_est0, "P0": P0,
+           "ekf_config": cfg}
+    if record_trace:
+        res["trace"] = trace
+    return res
+
+
 def record_laps(solver, track: dict, speed_scales=(0.80, 0.85, 0.90, 0.95, 1.0), dt: float = 0.03, n_sub: int = 3):
     """The laps SURVEY.md 8d config 3 stores in the safe set: "running config 1's tracking loop for 5 laps with seed-indexed speed
     scales {0.80, 0.85, 0.90, 0.95, 1.0}", one sample per 0.03 s (the recorder's period upstream, racing_mpc_node.cpp:66).  One

@@ -32,6 +32,7 @@
 #include "lmpc_dtrack.h"
 #include "lmpc_dtrack_model.h"
 #include "lmpc_cars_model.h"
+#include "lmpc_estimated.h"
 
 namespace {
 // Move-only owner of one device (PINNED: pinned host) allocation: freed by the destructor, and by alloc() before it allocates anew.
@@ -2572,6 +2573,54 @@ int lmpc_frenet_to_global_batch(lmpc_handle* h, const lmpc_spline_track* track, 
   HIP_TRY(h, hipSetDevice(h->device));
   hipLaunchKernelGGL(lmpc_track_to_global_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, h->stream, track->view, count, X, pose);
   HIP_TRY(h, hipGetLastError());
+  return LMPC_OK;
+}
+
+// ---- the fused estimated period (include/lmpc_hip_estimated.h, csrc/lmpc_estimated.h, csrc/lmpc_estimated_loop_kernel.hip) ----
+// Every check stands in front of the launch and of the clock: a refused call has written nothing and moved nothing.
+int lmpc_loop_advance_estimated_batch(lmpc_handle* h, int32_t batch, const lmpc_track* track, const lmpc_spline_track* spline,
+                                      const lmpc_estimated_loop* io) {
+  if (!h) return LMPC_ERR_ARGUMENT;
+  const std::string who = "lmpc_loop_advance_estimated_batch";
+  if (!io) return fail(h, LMPC_ERR_ARGUMENT, who + ": null io");
+  int rc = ekf_check(h, batch, who.c_str());
+  if (rc != LMPC_OK) return rc;
+  if (!h->ekf_initialized) return fail(h, LMPC_ERR_ARGUMENT, who + ": the filter is not initialised (lmpc_ekf_initialize)");
+  const int32_t n_obs = (int32_t)h->ekf_obs.size();
+  if (io->obs_vel < 0 || io->obs_vel >= n_obs || io->obs_pose < 0 || io->obs_pose >= n_obs)
+    return fail(h, LMPC_ERR_ARGUMENT, who + ": an observation id that was not registered");
+  if (!track_ok(track)) return fail(h, LMPC_ERR_ARGUMENT, who + ": null or empty track table");
+  rc = spline_track_check(h, spline, who.c_str());
+  if (rc != LMPC_OK) return rc;
+  if (!io->X_optm || !io->U_optm || !io->status || !io->x || !io->u_prev || !io->x_ic || !io->X_ref || !io->U_ref || !io->T_ref ||
+      !io->bound_left || !io->bound_right || !io->curvatures || !io->vel_ref || !io->noise_vel || !io->R_vel || !io->noise_pose || !io->R_pose)
+    return fail(h, LMPC_ERR_ARGUMENT, who + ": null required pointer");
+  if (!(io->dt > 0.0) || !(io->dt_sim > 0.0)) return fail(h, LMPC_ERR_ARGUMENT, who + ": dt and dt_sim must be positive");
+  if (io->n_sub < 2 || io->n_sub % 2) return fail(h, LMPC_ERR_ARGUMENT, who + ": n_sub must be even and at least 2 (the velocity observation sits at mid-period)");
+  if (io->X_ref == io->X_optm || io->U_ref == io->U_optm) return fail(h, LMPC_ERR_ARGUMENT, who + ": the references must not alias the solution");
+  if (h->out_aos) return fail(h, LMPC_ERR_UNSUPPORTED, who + " reads the solution in the [component][knot][batch] layout");
+  if (h->cars_model || h->dtrack_model)
+    return fail(h, LMPC_ERR_UNSUPPORTED, who + ": a controller-model switch is on (lmpc_cars_set_controller_model / lmpc_dtrack_set_controller_model): this call rolls out on the handle's vehicle");
+  lmpc_estimated_consts K;
+  K.obs_vel = h->ekf_obs[(size_t)io->obs_vel];
+  K.obs_pose = h->ekf_obs[(size_t)io->obs_pose];
+  bool families = K.obs_vel.nz <= 3 && K.obs_pose.nz <= 3;
+  for (int a = 0; families && a < K.obs_vel.nz; ++a) families = K.obs_vel.rows[a] >= 3;
+  for (int a = 0; families && a < K.obs_pose.nz; ++a) families = K.obs_pose.rows[a] <= 2;
+  if (!families)
+    return fail(h, LMPC_ERR_UNSUPPORTED, who + ": obs_vel must observe 1 - 3 rows within {3, 4, 5} and obs_pose 1 - 3 rows within {0, 1, 2}");
+  HIP_TRY(h, hipSetDevice(h->device));
+  K.veh = h->P.veh;
+  K.N = h->P.N;
+  K.max_vel_ref_diff = h->P.max_vel_ref_diff;
+  std::memcpy(K.ekf.Q, h->ekf_cfg.Q, sizeof(K.ekf.Q));
+  std::memcpy(K.ekf.x_min, h->ekf_cfg.x_min, sizeof(K.ekf.x_min));
+  std::memcpy(K.ekf.x_max, h->ekf_cfg.x_max, sizeof(K.ekf.x_max));
+  // the two spans by lmpc_ekf_update_batch's expression, from the clock two such calls would have kept
+  K.dt_vel = (double)(io->t_vel_ns - h->ekf_ns) * 1e-9;
+  K.dt_pose = (double)(io->t_pose_ns - io->t_vel_ns) * 1e-9;
+  HIP_TRY(h, lmpc_estimated_launch(h->stream, K, h->ekf, *track, spline->view, *io));
+  h->ekf_ns = io->t_pose_ns;
   return LMPC_OK;
 }
 

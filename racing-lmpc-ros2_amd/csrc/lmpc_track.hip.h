@@ -91,6 +91,81 @@ __device__ __forceinline__ double track_align_yaw(double yaw_1, double yaw_2) {
   return atan2(sin(d), cos(d)) + yaw_2;
 }
 
+// RacingTrajectory::global_to_frenet for one pose (px, py, phi), the body of lmpc_track_project_kernel (lmpc_track_kernel.hip has the
+// method's description) and of the projection step of lmpc_estimated_loop_kernel: the seed `s` where have_seed, else the abscissa
+// of the nearest waypoint; Newton on g(s) = (r(s) - p) . r'(s); the outputs as the host class forms them.  The waypoint loop is
+// wave-uniform over the lanes that CALL this (every lane of a wave that has one unseeded lane walks it): call it from code that
+// every lane whose result is wanted reaches together.  No lane reads another's data.
+struct track_frenet {
+  double s, t, xi;
+  int status;
+};
+__device__ __forceinline__ track_frenet track_project(const lmpc_spline_view& T, double px, double py, double phi, double s, bool have_seed) {
+#pragma clang fp contract(off)
+  const bool bad = !(isfinite(px) && isfinite(py) && isfinite(phi));
+  if (bad) px = T.wp_xy[0], py = T.wp_xy[1], phi = 0.0;
+  if (__any(!have_seed)) {
+    double best = INFINITY;
+    int ibest = 0;
+#pragma unroll 4
+    for (int j = 0; j < T.n_wp; ++j) {
+      const double wx = T.wp_xy[2 * (size_t)j], wy = T.wp_xy[2 * (size_t)j + 1];  // wave-uniform address: scalar loads
+      const double d = (wx - px) * (wx - px) + (wy - py) * (wy - py);
+      if (d < best) best = d, ibest = j;
+    }
+    if (!have_seed) s = T.wp_s[ibest];
+  }
+  const double hbar = T.hbar, tol = 1e-13 * fmax(1.0, T.L);
+  int piece = 0, st = LMPC_TRACK_NOT_CONVERGED;
+  s = track_mod(s, T.L);
+  track_point r = track_eval(T, s, piece);
+  double ex = r.x - px, ey = r.y - py;
+  double g = ex * r.dx + ey * r.dy;
+  for (int it = 0; it < 30; ++it) {
+    const double v2 = r.dx * r.dx + r.dy * r.dy;
+    const double H = v2 + (ex * r.d2x + ey * r.d2y);
+    double step = H > 1e-3 * v2 ? -g / H : -(double)((g > 0.0) - (g < 0.0)) * hbar;
+    step = fmin(fmax(step, -2.0 * hbar), 2.0 * hbar);
+    double a = 1.0, sn, gn;
+    track_point rn;
+    for (int k = 0;; ++k) {
+      sn = s + a * step;
+      rn = track_eval(T, sn, piece);
+      gn = (rn.x - px) * rn.dx + (rn.y - py) * rn.dy;
+      if (!(fabs(gn) > fabs(g)) || k == 6) break;
+      a *= 0.5;
+    }
+    s = sn, r = rn, g = gn;
+    ex = r.x - px, ey = r.y - py;
+    if (fabs(a * step) < tol) {
+      st = 0;
+      break;
+    }
+  }
+  // the outputs, exactly as the host class forms them (racing_trajectory.cpp:170-180)
+  const double so = track_mod(s, T.L);
+  const track_point o = track_eval(T, so, piece);
+  const double yaw = atan2(o.dy, o.dx);
+  const double sg = cos(yaw) * (py - o.y) - sin(yaw) * (px - o.x);  // lateral_sign (utils.hpp)
+  double t = hypot(px - o.x, py - o.y) * (double)((sg > 0.0) - (sg < 0.0));
+  double xi = track_align_yaw(phi, yaw) - yaw;
+  double s_out = so;
+  if (bad) s_out = t = xi = NAN, st = LMPC_TRACK_BAD_INPUT;
+  return {s_out, t, xi, st};
+}
+
+// RacingTrajectory::frenet_to_global for one (s, e_y, e_psi): the body of lmpc_track_to_global_kernel
+struct track_pose {
+  double x, y, yaw;
+};
+__device__ __forceinline__ track_pose track_to_global(const lmpc_spline_view& T, double s, double t, double xi) {
+#pragma clang fp contract(off)
+  int piece = 0;
+  const track_point r = track_eval(T, s, piece);
+  const double yaw0 = atan2(r.dy, r.dx);
+  return {r.x - sin(yaw0) * t, r.y + cos(yaw0) * t, track_align_yaw(yaw0 + xi, 0.0)};
+}
+
 // periodic linear interpolation on a uniform table of M samples over [0, L)
 __device__ __forceinline__ double track_lookup(const double* __restrict__ tab, int M, double L, double s) {
   double u = fmod(s, L);

@@ -43,67 +43,19 @@ __global__ __launch_bounds__(64) void lmpc_track_project_kernel(lmpc_spline_view
   const int gb = blockIdx.x * 64 + threadIdx.x;
   const bool live = gb < B;
   const int b = live ? gb : B - 1;
-  double px = pose[b], py = pose[(size_t)B + b], phi = pose[2 * (size_t)B + b];
-  const bool bad = !(isfinite(px) && isfinite(py) && isfinite(phi));
-  if (bad) px = T.wp_xy[0], py = T.wp_xy[1], phi = 0.0;
+  const double px = pose[b], py = pose[(size_t)B + b], phi = pose[2 * (size_t)B + b];
   double s = 0.0;
   bool have_seed = false;
   if (s0 && (!seeded || seeded[b] != 0)) {
     s = s0[b];
     have_seed = isfinite(s);
   }
-  if (__any(!have_seed)) {
-    double best = INFINITY;
-    int ibest = 0;
-#pragma unroll 4
-    for (int j = 0; j < T.n_wp; ++j) {
-      const double wx = T.wp_xy[2 * (size_t)j], wy = T.wp_xy[2 * (size_t)j + 1];  // wave-uniform address: scalar loads
-      const double d = (wx - px) * (wx - px) + (wy - py) * (wy - py);
-      if (d < best) best = d, ibest = j;
-    }
-    if (!have_seed) s = T.wp_s[ibest];
-  }
-  const double hbar = T.hbar, tol = 1e-13 * fmax(1.0, T.L);
-  int piece = 0, st = LMPC_TRACK_NOT_CONVERGED;
-  s = track_mod(s, T.L);
-  track_point r = track_eval(T, s, piece);
-  double ex = r.x - px, ey = r.y - py;
-  double g = ex * r.dx + ey * r.dy;
-  for (int it = 0; it < 30; ++it) {
-    const double v2 = r.dx * r.dx + r.dy * r.dy;
-    const double H = v2 + (ex * r.d2x + ey * r.d2y);
-    double step = H > 1e-3 * v2 ? -g / H : -(double)((g > 0.0) - (g < 0.0)) * hbar;
-    step = fmin(fmax(step, -2.0 * hbar), 2.0 * hbar);
-    double a = 1.0, sn, gn;
-    track_point rn;
-    for (int k = 0;; ++k) {
-      sn = s + a * step;
-      rn = track_eval(T, sn, piece);
-      gn = (rn.x - px) * rn.dx + (rn.y - py) * rn.dy;
-      if (!(fabs(gn) > fabs(g)) || k == 6) break;
-      a *= 0.5;
-    }
-    s = sn, r = rn, g = gn;
-    ex = r.x - px, ey = r.y - py;
-    if (fabs(a * step) < tol) {
-      st = 0;
-      break;
-    }
-  }
-  // the outputs, exactly as the host class forms them (racing_trajectory.cpp:170-180)
-  const double so = track_mod(s, T.L);
-  const track_point o = track_eval(T, so, piece);
-  const double yaw = atan2(o.dy, o.dx);
-  const double sg = cos(yaw) * (py - o.y) - sin(yaw) * (px - o.x);  // lateral_sign (utils.hpp)
-  double t = hypot(px - o.x, py - o.y) * (double)((sg > 0.0) - (sg < 0.0));
-  double xi = track_align_yaw(phi, yaw) - yaw;
-  double s_out = so;
-  if (bad) s_out = t = xi = NAN, st = LMPC_TRACK_BAD_INPUT;
+  const track_frenet f = track_project(T, px, py, phi, s, have_seed);  // (every lane: the cars past the batch redo the last one)
   if (live) {
-    frenet[b] = s_out;
-    frenet[(size_t)B + b] = t;
-    frenet[2 * (size_t)B + b] = xi;
-    status[b] = st;
+    frenet[b] = f.s;
+    frenet[(size_t)B + b] = f.t;
+    frenet[2 * (size_t)B + b] = f.xi;
+    status[b] = f.status;
   }
 }
 
@@ -115,12 +67,10 @@ __global__ __launch_bounds__(256) void lmpc_track_to_global_kernel(lmpc_spline_v
   const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
   if (e >= count) return;
   const double s = X[e], t = X[count + e], xi = X[2 * count + e];
-  int piece = 0;
-  const track_point r = track_eval(T, s, piece);
-  const double yaw0 = atan2(r.dy, r.dx);
-  pose[e] = r.x - sin(yaw0) * t;
-  pose[count + e] = r.y + cos(yaw0) * t;
-  pose[2 * count + e] = track_align_yaw(yaw0 + xi, 0.0);
+  const track_pose p = track_to_global(T, s, t, xi);
+  pose[e] = p.x;
+  pose[count + e] = p.y;
+  pose[2 * count + e] = p.yaw;
 }
 
 // The interpolants at abscissa s[j] (s != NULL) or at s_j = j L / n, the sample points of an lmpc_track with M = n (s == NULL).
