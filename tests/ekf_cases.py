@@ -166,13 +166,13 @@ class Filter:
         return xn.copy(), Pn.copy(), Kz, flags
 
 
-def scenario(B: int, periods: int = 400, seed: int = 3, dt_ns: int = 10_000_000, veh=None):
+def scenario(B: int, periods: int = 400, seed: int = 3, dt_ns: int = 10_000_000, veh=None, lon=None):
     """The issue's scenario for B cars: BARC vehicle, period 10 ms; per period the control u = (0.0008 + 0.001 sin(1.3 t + phi),
     0.2 sin(0.9 t + phi)), a velocity observation (rows 3, 5; sigma 0.05) at mid-period and a pose observation (rows 0, 1, 2; sigma
     0.02, 0.02, 0.01; yaw wrapped to (-pi, pi]) at the period, the pose dropped (NaN in z[0]) for 10 % of the cars; truth starts at
     vx ~ U(1.5, 2.5), yaw ~ U(-3, 3); the filters start at truth + 0.5 N(0, 1) sd0 (vx floored at 0.5) with P0 = diag(sd0^2).
     Returns {"veh", "cfg", "x0" [B, 6], "P0" [B, 6, 6], "updates": list of (obs, z [B, nz], R [B, nz, nz], u [B, 2], timestamp_ns),
-    "truth": [periods, B, 6]} -- obs 0 is the velocity observation, 1 the pose."""
+    "truth": [periods, B, 6]} -- obs 0 is the velocity observation, 1 the pose.  `lon`: another u_lon, a function of (period k, phi [B])."""
     veh = OP.barc_vehicle() if veh is None else veh
     rng = np.random.default_rng(seed)
     dt = dt_ns * 1e-9
@@ -187,7 +187,7 @@ def scenario(B: int, periods: int = 400, seed: int = 3, dt_ns: int = 10_000_000,
     updates, truth = [], []
     for k in range(periods):
         t = k * dt
-        u = np.stack([0.0008 + 0.001 * np.sin(1.3 * t + ph), 0.2 * np.sin(0.9 * t + ph)], axis=1)
+        u = np.stack([0.0008 + 0.001 * np.sin(1.3 * t + ph) if lon is None else lon(k, ph), 0.2 * np.sin(0.9 * t + ph)], axis=1)
         xt = D.rk4(xt, u, 0.0, dt / 2, veh)
         zv = xt[:, list(ROWS_VEL)] + rng.normal(0, SIG_VEL, (B, 2))
         updates.append((0, zv, Rv, u, k * dt_ns + dt_ns // 2))

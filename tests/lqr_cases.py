@@ -169,14 +169,14 @@ def solve(veh, cfg: dict, x_ic, X_ref, U_ref, T=np.float64) -> dict:
             "flags": np.where(fin, 0, NOT_FINITE).astype(np.int32)}
 
 
-def reference_trajectory(kind: str, M: int, dt: float, B: int, seed: int):
+def reference_trajectory(kind: str, M: int, dt: float, B: int, seed: int, veh=None):
     """A reference of M knots that is itself an open-loop RK4 rollout (k = 0) of its U_ref from a random start, and x_ic = the start
     plus a small offset.  Returns (veh, x_ic [B, 6], X_ref [B, 6, M], U_ref [B, 2, M-1]).
       barc: vx in [1.5, 3], yaw ~ N(0, 0.3^2), vy ~ N(0, 0.05^2), omega ~ N(0, 0.2^2), positions in [-1, 1]; u_lon ~ N(0, 0.003^2)
             held, steer 0.1 sin(8 t + phi); offset [0.1, 0.1, 0.03, 0.1, 0.02, 0.1] N(0, 1)
       iac:  vx in [32, 48], the same yaw, vy ~ N(0, 0.2^2), omega ~ N(0, 0.05^2); u_lon ~ N(0, 0.2^2) held, steer 0.03 sin(0.3 i + phi);
             offset [1, 0.5, 0.02, 2, 0.2, 0.05] N(0, 1)"""
-    veh = vehicle(kind)
+    veh = vehicle(kind) if veh is None else veh   # (another vehicle of the same scale)
     rng = np.random.default_rng(seed)
     barc = kind == "barc"
     x = np.zeros((B, 6))
@@ -198,8 +198,8 @@ def reference_trajectory(kind: str, M: int, dt: float, B: int, seed: int):
     return veh, x_ic, X_ref, U_ref
 
 
-def scenario(kind: str, N: int, dt: float, seed: int, B: int = B_TEST, general: bool = False) -> dict:
-    veh, x_ic, X_ref, U_ref = reference_trajectory(kind, N, dt, B, seed)
+def scenario(kind: str, N: int, dt: float, seed: int, B: int = B_TEST, general: bool = False, veh=None) -> dict:
+    veh, x_ic, X_ref, U_ref = reference_trajectory(kind, N, dt, B, seed, veh)
     return {"kind": kind, "veh": veh, "cfg": general_config(N, dt) if general else config(N, dt), "x_ic": x_ic, "X_ref": X_ref, "U_ref": U_ref}
 
 

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import cars_model_cases as MC
+import envelope_cases as E
 import stream_cases as SC
 from tolerances import TOL_LINEARIZE_REL
 
@@ -39,7 +40,9 @@ def scene(pkg):
             inp, veh = MC.lin_draws(pkg, B, N)
             want = MC.reference(inp, veh)
             assert all(np.isfinite(w).all() for w in want)
-            cache[B, N] = dict(B=B, N=N, inp=inp, veh=veh, want=want, dev={k: dev(inp[k]) for k in KEYS})
+            cs = E.complex_step(inp, veh)
+            assert all(np.isfinite(c).all() for c in cs)
+            cache[B, N] = dict(B=B, N=N, inp=inp, veh=veh, want=want, cs=cs, dev={k: dev(inp[k]) for k in KEYS})
         return cache[B, N]
 
     yield dict(solver=solver, get=get, pkg=pkg)
@@ -53,9 +56,15 @@ def linearize(scene, d, veh=None):
     return [t.cpu().numpy() for t in s.linearize_cars(d["dev"])]
 
 
-def stage_errors(got, want):
-    """per stage, (error, bound) of A, Bm and g as tests/test_gpu_timestep.py scales them"""
+def stage_errors(got, want, cs=None):
+    """per stage, (error, bound) of A, Bm and g as tests/test_gpu_timestep.py scales them; with the complex-step Jacobian `cs` of the
+    same table also, per array, the (problem, stage) that comes closest to its own bound in the per-problem measure of
+    tests/envelope_cases.py -- a stage's largest entry belongs to its slowest car and hides an error in a fast one"""
     out = []
+    if cs is not None:
+        for name, e, b in zip(("A per problem", "Bm per problem", "g per problem"), E.errors(got, cs), E.bounds(want, cs)):
+            j = np.unravel_index(np.argmax(e / b), e.shape)
+            out.append((int(j[0]), name, float(e[j]), float(b[j])))
     for i in range(want[2].shape[1]):
         for j, tol in ((0, TOL_LINEARIZE_REL), (1, TOL_LINEARIZE_REL), (2, 10 * TOL_LINEARIZE_REL)):
             g, w = (got[j][:, :, i], want[j][:, :, i]) if j < 2 else (got[j][:, i], want[j][:, i])
@@ -69,7 +78,9 @@ def test_each_problem_is_linearised_on_its_own_vehicle(scene, B, N):
     d = scene["get"](B, N)
     got = linearize(scene, d)
     assert all(np.isfinite(g).all() for g in got)
-    errs = stage_errors(got, d["want"])
+    errs = stage_errors(got, d["want"], d["cs"])
+    print("B = %d N = %d, per problem against the complex step, the point closest to its bound: " % (B, N)
+          + ", ".join("%s %.2e (bound %.2e)" % (m, e, t) for _, m, e, t in errs if m.endswith("per problem")))
     worst = {n: max(e for _, m, e, _ in errs if m == n) for n in ("A", "Bm", "g")}
     print("B = %d N = %d: max over stages of |device - reference| / (the stage's largest entry): A %.2e, Bm %.2e, g %.2e (bounds %.0e, %.0e, %.0e)"
           % (B, N, worst["A"], worst["Bm"], worst["g"], TOL_LINEARIZE_REL, TOL_LINEARIZE_REL, 10 * TOL_LINEARIZE_REL))

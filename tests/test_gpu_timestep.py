@@ -72,6 +72,9 @@ def test_linearize_matches_complex_step_on_nonuniform_steps(pkg, N, integrator):
         assert eA[i].max() <= TOL_LINEARIZE_REL * np.abs(Ar[i]).max(), i
         assert eB[i].max() <= TOL_LINEARIZE_REL * np.abs(Br[i]).max(), i
         assert eg[i].max() <= 10 * TOL_LINEARIZE_REL * max(1.0, np.abs(gr[i]).max()), i
+    # and per problem: a stage's largest entry belongs to its slowest car and hides an error in a fast one (tests/envelope_cases.py)
+    import envelope_cases as E
+    E.held_per_problem("N = %d %s" % (N, integrator), (A, Bm, g), inp, veh)
 
 
 # ---- fp64, every case --------------------------------------------------------------------------------------------------------------------
